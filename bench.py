@@ -2,15 +2,23 @@
 """Benchmark of the north-star path: fused INT8 attention forward (fa_tc_int8_b) at
 BASELINE config 4, B16 H16 N4096 d64 per GPU, through the C-ABI (qmha_solve_ex).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one qmha_solve_ex call = one full B x H attention forward (quantisation
 pre-pass + fused kernel) with fp32 Q/K/V already resident in HBM.  Multi-GPU: one process
 per GPU, each rank owns its own batch shard of 16 sequences (weak scaling, BASELINE
-config 5 at N=8), no collective inside the timed region; the RCCL all-gather of the
-per-shard outputs named by the north star is timed separately (allgather_ms).
+config 5 at N=8), no collective inside the timed region.
 Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set-up, W warm-up calls, K timed calls, the
+result line (with the roofline figures derived from those same K calls).  --dump-outputs DIR
+also writes what the last timed call computed (DIR/O.npy, float32).  --full adds every other
+measurement, each a run of its own: the fp16 / fp32 / per-tensor / unfused siblings, the
+reference's own configuration, the standalone quantisation op, U[0, 1) inputs, the torch_ext
+and one-solve-per-sequence calling patterns, the CPU baselines, the in-kernel clock probe with
+the device's sysfs state and the ISA identity of the code that ran, and (under a launcher) the
+RCCL all-gather legs named by the north star (allgather_ms); the --no-* options prune it.
 """
 import argparse
 import json
@@ -159,6 +167,30 @@ def run_variant(variant, B, H, N, d, steps, warmup, dev, rank, world, profile=Tr
         "inputs": (Q, K, V),
         "O": O,
     }
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much
+DUMP_SAMPLE_BYTES = 32 << 20  # size of the row sample of an output larger than that
+DUMP_SEED = 20240
+
+
+def dump_outputs(out_dir, O, rank, world):
+    """--dump-outputs: write the [B, N, H*d] fp32 output of the last timed call (what a caller of
+    qmha_solve_ex receives) as <out_dir>/O.npy, one file per rank when there are several.  An output
+    above DUMP_MAX_BYTES is written as a [rows, H*d] sample of its B*N rows: DUMP_SAMPLE_BYTES worth of
+    distinct rows drawn by numpy's default_rng(DUMP_SEED) and sorted, so the same shape always yields the
+    same rows and two builds can be compared element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    flat = O.reshape(-1, O.shape[-1])
+    if flat.numel() * 4 * world > DUMP_MAX_BYTES:  # the bound holds for all ranks' files together
+        keep = max(1, min(flat.shape[0], DUMP_SAMPLE_BYTES // (4 * flat.shape[1] * world)))
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.shape[0], size=keep, replace=False))
+        arr = flat[torch.from_numpy(rows).to(flat.device)]
+    else:
+        arr = O
+    arr = arr.to(torch.float32).cpu().numpy()
+    assert arr.nbytes * world <= DUMP_MAX_BYTES
+    np.save(os.path.join(out_dir, "O.npy" if world == 1 else f"O_rank{rank}.npy"), arr)
 
 
 def time_solve_calls(variant, B, H, N, d, dev, reps=3):
@@ -439,6 +471,14 @@ def main():
     ap.add_argument("--H", type=int, default=16)
     ap.add_argument("--N", type=int, default=4096)
     ap.add_argument("--d", type=int, default=64)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (siblings, reference configuration, quantisation op, "
+                         "uniform inputs, calling patterns, CPU baselines, clock probe / device state / ISA "
+                         "identity, all-gather legs); the --no-* options below prune that set")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last of them computed as DIR/O.npy (float32; "
+                         "DIR/O_rank<r>.npy per rank when --gpus > 1): the whole [B, N, H*d] output, or, "
+                         f"above {DUMP_MAX_BYTES >> 20} MB, its rows picked by a fixed seed")
     ap.add_argument("--no-siblings", action="store_true", help="skip the fp16 / fp32 sibling measurements")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-solve-calls", action="store_true",
@@ -452,6 +492,9 @@ def main():
                     help="launcher plumbing only (CPU, gloo): spawn, rendezvous, barriers, max-over-ranks "
                          "timing and the chunked all-gather, with a tensor copy as the step; no kernel, no value")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    full = a.full
 
     launched = "WORLD_SIZE" in os.environ
     if not launched and a.gpus > 1:
@@ -480,12 +523,12 @@ def main():
         else:
             dist.init_process_group("nccl", device_id=dev)
 
-    # The side measurements run BEFORE the headline: they are independent of it, and they bring
+    # The side measurements (--full) run BEFORE the headline: they are independent of it, and they bring
     # the GPU out of its idle clock state, so the headline's W warm-up calls start from a busy
     # GPU (a fresh process otherwise ramps over its first ~20-30 calls, tools/ramp.py ->
     # profiles/r02/clock_ramp.txt).  The headline itself is still W untimed + K timed calls.
     side = {}
-    if not a.no_siblings and not dry:
+    if full and not a.no_siblings and not dry:
         sib = {}
         # fa_tc_v1a at C3 (= the C4 shape), fa (the scalar no-matrix-core kernel BASELINE C2 names)
         # and its fp32-MFMA sibling fa_mfma at C2, and the reference's unfused 3-kernel baseline
@@ -509,13 +552,15 @@ def main():
                       "peak": f"{PEAKS[v]} TFLOP/s {PEAK_KIND[v]}"}
             del rv
         side["siblings"] = sib
-    if not a.no_refconfig and not dry and world == 1:
+    if full and not a.no_refconfig and not dry and world == 1:
         side["reference_config"] = reference_config(a.variant, dev, rank, world)
-    if not a.no_siblings and not dry and world == 1:
+    if full and not a.no_siblings and not dry and world == 1:
         side["quantize_int8"] = time_quantize_int8(B, H, N, d, dev)
 
-    sampler = None if dry else SysfsSampler(device_state(dev).get("hwmon"))
+    sampler = SysfsSampler(device_state(dev).get("hwmon")) if full and not dry else None
     r = run_variant(a.variant, B, H, N, d, a.steps, a.warmup, dev, rank, world, dry_run=dry, sampler=sampler)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, r["O"], rank, world)
     total_flops = flops(B, H, N, d) * world
     value = total_flops / r["elapsed_s"] * a.steps / 1e12
     peak = PEAKS.get(a.variant, INT8_PEAK_TOPS)
@@ -563,7 +608,7 @@ def main():
                            "hbm_algorithmic_bytes_per_call": hbm_alg,
                            "hbm_GBs_per_call": round(hbm_alg / (r["ms_per_step"] * 1e-3) / 1e9, 1),
                            "mfma_busy_pct": busy, "mfma_busy_source": busy_src}
-    if not dry:
+    if full and not dry:
         # reproducibility across boxes (round-5 VERDICT item 2): the clock this box holds under the kernel's
         # mix, measured right after the headline, its power cap, and the identity of the code that ran
         probe = clock_probe(dev)
@@ -586,7 +631,7 @@ def main():
             # clock-free form: the tile's time in units of the probe's own unit time on the same box (the
             # ratio of two wall times; DESIGN.md 7.1: constant to +-0.3 % over five boxes)
             res["probe_units_per_tile"] = round(r["main_kernel_ms"] * 1e6 / tiles / probe["ns_per_unit_per_simd"], 4)
-    if dist.is_initialized():
+    if full and dist.is_initialized():
         ag_ms = time_allgather(r["O"], max(3, a.steps // 2), dev, world)
         sg_ms = time_solve_gather(a.variant, r["inputs"], H, d, max(3, a.steps // 2), dev, world,
                                   a.gather_chunks, dry_run=dry)
@@ -614,7 +659,7 @@ def main():
         busy_pt, busy_pt_src = pmc_sq("fa_tc_int8_pt", B, H, N, d)
         res["int8_per_tensor"].update({"traffic": tr, "traffic_source": tr_src, "mfma_busy_pct": busy_pt,
                                        "mfma_busy_source": busy_pt_src})
-    if not a.no_siblings and not dry and world == 1:
+    if full and not a.no_siblings and not dry and world == 1:
         # the same call on the reference's profiling input distribution U[0, 1) (a side line; the headline
         # above is N(0, 0.5^2))
         ru = run_variant(a.variant, B, H, N, d, max(10, a.steps // 2), 10, dev, rank, world, uniform=True)
@@ -624,11 +669,11 @@ def main():
                                  "main_kernel_ms": round(ru["main_kernel_ms"], 4)}
         del ru
         res["torch_ext"] = time_torch_ext(B, H, N, d, dev)
-    if rank == 0 and world == 1 and not a.no_siblings and not a.no_solve_calls and not dry:
+    if full and rank == 0 and world == 1 and not a.no_siblings and not a.no_solve_calls and not dry:
         ms = time_solve_calls(a.variant, B, H, N, d, dev)
         res["solve_calls"] = {"pattern": f"{B} blocking solve() calls, one per sequence (reference usage)",
                               "ms_per_step": round(ms, 4), "tflops": round(flops(B, H, N, d) / (ms * 1e-3) / 1e12, 3)}
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not dry:
+    if full and rank == 0 and world == 1 and not a.no_cpu_baseline and not dry:
         res["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         print(json.dumps(res), flush=True)

@@ -102,7 +102,27 @@ def main():
                        "source": "inputs/data.cu:9-30 generator + utils/verify.cu cpu_reference (RoPE), "
                                  "compiled from /root/reference"},
                       open(os.path.join(dst, "meta.json"), "w"), indent=2)
+    write_rope_normal()
     print("golden fixtures written under", GOLD)
+
+
+def write_rope_normal():
+    """rope_normal/: the reference's cpu_reference (RoPE) on N(0, 1) inputs at N96 d_model64 h2 (d = 32, a row
+    count that is no multiple of 64), in the same two cache formats.  It is the stored form of
+    tests/test_oracle.py::test_cpu_reference_rope_matches_live_reference, which therefore also runs where the
+    reference sources are absent."""
+    N, dm, h = 96, 64, 2
+    rng = np.random.default_rng(7)
+    Q, K, V = (rng.standard_normal((N, dm)).astype(np.float32) for _ in range(3))
+    out = oracle.ref_cpu_reference(Q, K, V, dm, h)
+    dst = os.path.join(GOLD, "rope_normal")
+    os.makedirs(dst, exist_ok=True)
+    write_inputs_cache(os.path.join(dst, f"input_normal_N{N}_d{dm}.bin"), N, dm, Q, K, V)
+    write_ref_cache(os.path.join(dst, f"ref_N{N}_d{dm}.bin"), N, dm, out)
+    json.dump({"N": N, "d_model": dm, "h": h,
+               "source": "numpy default_rng(7) standard_normal Q, K, V + utils/verify.cu cpu_reference (RoPE), "
+                         "compiled unmodified from the reference's sources"},
+              open(os.path.join(dst, "meta.json"), "w"), indent=2)
 
 
 if __name__ == "__main__":

@@ -146,7 +146,7 @@ def test_bench_spawns_ranks_dry_run():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "2",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-run", "--full", "--steps", "2",
                         "--warmup", "1"], capture_output=True, text=True, timeout=240, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -187,7 +187,7 @@ def test_bench_torchrun_world1_gpu(tmp_path):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr",
            "127.0.0.1", f"--master-port={_free_port()}", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2",
-           "--warmup", "1", "--B", "2", "--N", "512", "--no-siblings", "--no-cpu-baseline", "--no-refconfig"]
+           "--warmup", "1", "--B", "2", "--N", "512", "--full", "--no-siblings", "--no-cpu-baseline", "--no-refconfig"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=180, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

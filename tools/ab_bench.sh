@@ -8,7 +8,7 @@ TAG=${1:-ab}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 for rep in 1 2; do
   for lib in default $2; do
     if [ "$lib" = default ]; then LP=""; else LP=$PWD/quantizedmha_amd/alt_lib/$lib/libqmha.so; fi
-    env QMHA_LIB_PATH=$LP timeout -k 10 200 python bench.py --no-siblings --no-cpu-baseline --no-solve-calls $3 > $OUT/${lib}_$rep.json 2>$OUT/${lib}_$rep.err
+    env QMHA_LIB_PATH=$LP timeout -k 10 200 python bench.py --full --no-siblings --no-cpu-baseline --no-solve-calls $3 > $OUT/${lib}_$rep.json 2>$OUT/${lib}_$rep.err
     rc=$?; [ $rc -ne 0 ] && { echo "bench $lib rc=$rc"; tail -3 $OUT/${lib}_$rep.err; exit $rc; }
     python - "$lib" $OUT/${lib}_$rep.json <<'PY'
 import json,sys

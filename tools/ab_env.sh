@@ -11,7 +11,7 @@ for rep in 1 2; do
     name=${arm%%=*}; rest=${arm#*=}; lib=${rest%%:*}; envs=${rest#*:}
     [ "$envs" = "$rest" ] && envs=""
     LP=""; [ "$lib" != default ] && LP=$PWD/quantizedmha_amd/alt_lib/$lib/libqmha.so
-    env QMHA_LIB_PATH=$LP ${envs//,/ } timeout -k 10 240 python bench.py --no-siblings --no-cpu-baseline --no-solve-calls $ARGS > $OUT/${name}_$rep.json 2>$OUT/${name}_$rep.err
+    env QMHA_LIB_PATH=$LP ${envs//,/ } timeout -k 10 240 python bench.py --full --no-siblings --no-cpu-baseline --no-solve-calls $ARGS > $OUT/${name}_$rep.json 2>$OUT/${name}_$rep.err
     rc=$?; [ $rc -ne 0 ] && { echo "bench $name rc=$rc"; tail -3 $OUT/${name}_$rep.err; exit $rc; }
     python - "$name" $OUT/${name}_$rep.json <<'PY'
 import json,sys

@@ -16,7 +16,7 @@ rc2=$?
 echo "smoke rc=$rc2"; tail -3 $OUT/smoke.log
 if [ $rc2 -ne 0 ] && [ $rc2 -ne 1 ]; then exit $rc2; fi
 [ -n "$NO_BENCH" ] && exit $(( rc | rc2 ))
-timeout -k 10 600 python bench.py ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 600 python bench.py --full ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err
 rc3=$?
 echo "bench rc=$rc3"; head -c 3000 $OUT/bench.json; tail -3 $OUT/bench.err
 exit $(( rc | rc2 | rc3 ))

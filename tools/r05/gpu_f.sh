@@ -12,9 +12,9 @@ for v in fa_tc_int8_b fa_tc_int8_pt; do
   BENCH_ARGS="--no-solve-calls --variant $v" bash tools/pmc_sq.sh ${T}_sq_$v > /dev/null || exit $?
   python3 tools/pmc_summary.py gpurun_out/${T}_sq_$v --kernel qmha --json-out gpurun_out/${T}_sq_$v/pmc_sq_$v.json --shape 16 16 4096 64 > gpurun_out/${T}_sq_$v/summary.txt || exit $?
 done
-timeout -k 10 500 python bench.py > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 500 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 head -c 600 $O/bench.json; echo
-timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- python3 bench.py --no-cpu-baseline > $O/trace.log 2>&1 || { tail -20 $O/trace.log; exit 1; }
+timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- python3 bench.py --full --no-cpu-baseline > $O/trace.log 2>&1 || { tail -20 $O/trace.log; exit 1; }
 find $O/trace -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats.csv \;
 find $O/trace -name "*kernel_trace.csv" -exec cp {} $O/kernel_trace.csv \;
 rm -rf $O/trace

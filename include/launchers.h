@@ -83,6 +83,24 @@ size_t qmha_workspace_size(int B, int N, int d_model, int h, int variant);
 int qmha_solve_ws(const float *Q, const float *K, const float *V, float *O, int B, int N, int d_model, int h,
                   int variant, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Option flags of qmha_solve_opts. */
+enum {
+    QMHA_FLAG_CAUSAL = 1 /* query row r attends keys j <= r of its own sequence (Nq = Nk = N) */
+};
+
+/*
+ * qmha_solve_opts -- qmha_solve_ex / qmha_solve_ws with option flags.  workspace == NULL: the
+ * library-owned, leased workspace of qmha_solve_ex (workspace_bytes is ignored).  Otherwise the
+ * qmha_solve_ws rules: caller-owned scratch of >= qmha_workspace_size bytes (the same size with or
+ * without flags), no allocation, no synchronisation, capturable in a hipGraph.  flags == 0 enqueues
+ * exactly what qmha_solve_ex / qmha_solve_ws enqueue.  Unknown flag bits: QMHA_ERR_INVALID.
+ * QMHA_FLAG_CAUSAL is built for fa_tc_int8_b at d = 32, 64, 128 and fa_tc_v1a at d = 64, 128; every
+ * other variant or head size returns QMHA_ERR_NOSYS (qmha_last_error names the variant and d) before
+ * anything is launched, leaving O untouched.
+ */
+int qmha_solve_opts(const float *Q, const float *K, const float *V, float *O, int B, int N, int d_model, int h,
+                    int variant, unsigned flags, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Blocking convenience used by the per-variant `solve` shims and the JAX raw-pointer
  * binding (extensions/jax/jax_ext.cpp:12-28): batch 1, synchronises the device stream. */
 int qmha_solve_variant(const float *Q, const float *K, const float *V, float *O, int N, int d_model, int h,

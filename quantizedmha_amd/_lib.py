@@ -15,12 +15,14 @@ LIB_PATH = os.environ.get("QMHA_LIB_PATH") or os.path.join(LIB_DIR, "libqmha.so"
 VARIANTS = {"fa": 0, "fa_tc_v1a": 1, "fa_tc_int8_b": 2, "unfused": 3, "fa_mfma": 4, "fa_tc_int8_pt": 5}
 DEFAULT_KERNEL = "fa_tc_int8_b"
 QMHA_OK = 0
+QMHA_FLAG_CAUSAL = 1  # qmha_solve_opts: query row r attends keys j <= r
 
 # every symbol include/launchers.h declares, with its ctypes signature
 _i, _sz, _vp, _cp = ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_char_p
 SIGNATURES = {
     "solve": (None, [_vp, _vp, _vp, _vp, _i, _i, _i]),
     "qmha_solve_ex": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "qmha_solve_opts": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_uint, _vp, _sz, _vp]),
     "qmha_workspace_size": (_sz, [_i, _i, _i, _i, _i]),
     "qmha_solve_ws": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "qmha_solve_variant": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i]),

@@ -42,7 +42,8 @@ void parallel_rows(int total, int threads, Fn fn) {
 
 // One output row of one head; rope selects verify.cu (true) or plain attention (false).
 void attention_row(const float* Q, const float* K, const float* V, float* out, int N, int d_model, int dh, int col,
-                   int i, bool rope, std::vector<float>& scratch) {
+                   int i, bool rope, bool causal, std::vector<float>& scratch) {
+    const int NK = causal ? i + 1 : N;  // causal: keys j > i are masked
     const float alpha = 1.0f / std::sqrt((float)dh);
     scratch.resize((size_t)N + 3 * dh);
     float* scores = scratch.data();
@@ -52,7 +53,7 @@ void attention_row(const float* Q, const float* K, const float* V, float* out, i
     for (int kk = 0; kk < dh; ++kk) q[kk] = Q[(size_t)i * d_model + col + kk];
     if (rope) rope_inplace(q, i, dh);
     float mx = -INFINITY;
-    for (int j = 0; j < N; ++j) {
+    for (int j = 0; j < NK; ++j) {
         for (int kk = 0; kk < dh; ++kk) k[kk] = K[(size_t)j * d_model + col + kk];
         if (rope) rope_inplace(k, j, dh);
         float s = 0.0f;
@@ -62,14 +63,14 @@ void attention_row(const float* Q, const float* K, const float* V, float* out, i
         if (s > mx) mx = s;
     }
     float sum = 0.0f;
-    for (int j = 0; j < N; ++j) {
+    for (int j = 0; j < NK; ++j) {
         const float e = std::exp(scores[j] - mx);
         scores[j] = e;
         sum += e;
     }
-    for (int j = 0; j < N; ++j) scores[j] /= sum;
+    for (int j = 0; j < NK; ++j) scores[j] /= sum;
     for (int kk = 0; kk < dh; ++kk) acc[kk] = 0.0f;
-    for (int j = 0; j < N; ++j) {
+    for (int j = 0; j < NK; ++j) {
         const float w = scores[j];
         for (int kk = 0; kk < dh; ++kk) acc[kk] += w * V[(size_t)j * d_model + col + kk];
     }
@@ -77,27 +78,27 @@ void attention_row(const float* Q, const float* K, const float* V, float* out, i
 }
 
 void run_all(const std::vector<float>& Q, const std::vector<float>& K, const std::vector<float>& V,
-             std::vector<float>& out, int N, int d_model, int h, int threads, bool rope) {
+             std::vector<float>& out, int N, int d_model, int h, int threads, bool rope, bool causal) {
     out.assign((size_t)N * d_model, 0.0f);
     const int dh = d_model / h;
     parallel_rows(N * h, threads, [&](int lo, int hi) {
         std::vector<float> scratch;
         for (int w = lo; w < hi; ++w)
             attention_row(Q.data(), K.data(), V.data(), out.data(), N, d_model, dh, (w / N) * dh, w % N, rope,
-                          scratch);
+                          causal, scratch);
     });
 }
 
 }  // namespace
 
 void cpu_reference(const std::vector<float>& Q, const std::vector<float>& K, const std::vector<float>& V,
-                   std::vector<float>& out, int N, int d_model, int h, int threads) {
-    run_all(Q, K, V, out, N, d_model, h, threads, true);
+                   std::vector<float>& out, int N, int d_model, int h, int threads, bool causal) {
+    run_all(Q, K, V, out, N, d_model, h, threads, true, causal);
 }
 
 void cpu_attention(const std::vector<float>& Q, const std::vector<float>& K, const std::vector<float>& V,
-                   std::vector<float>& out, int N, int d_model, int h, int threads) {
-    run_all(Q, K, V, out, N, d_model, h, threads, false);
+                   std::vector<float>& out, int N, int d_model, int h, int threads, bool causal) {
+    run_all(Q, K, V, out, N, d_model, h, threads, false, causal);
 }
 
 bool verify_results(const std::vector<float>& got, const std::vector<float>& ref, float eps, float rel,

@@ -81,6 +81,24 @@ int check_shape(const void* Q, const void* K, const void* V, const void* O, int 
     return QMHA_OK;
 }
 
+// qmha_solve_opts' flags, checked before any launch: unknown bits are invalid; QMHA_FLAG_CAUSAL is built
+// for fa_tc_int8_b at d = 32 / 64 / 128 and fa_tc_v1a at d = 64 / 128
+int check_flags(int variant, int D, unsigned flags) {
+    if (flags & ~(unsigned)QMHA_FLAG_CAUSAL) {
+        g_last_error = "unknown flag bits " + std::to_string(flags & ~(unsigned)QMHA_FLAG_CAUSAL);
+        return QMHA_ERR_INVALID;
+    }
+    if (flags & QMHA_FLAG_CAUSAL) {
+        const bool int8 = variant == QMHA_FA_TC_INT8_B;
+        if ((!int8 && variant != QMHA_FA_TC_V1A) || !qmha::causal_supported(int8, D)) {
+            g_last_error = std::string("causal attention is not built for variant ") + qmha_variant_name(variant) +
+                           " at d = " + std::to_string(D) + " (fa_tc_int8_b: d = 32, 64, 128; fa_tc_v1a: d = 64, 128)";
+            return QMHA_ERR_NOSYS;
+        }
+    }
+    return QMHA_OK;
+}
+
 // ---- profiling --------------------------------------------------------------------------
 // Per call: event pairs around every pre-pass launch (on the pre-pass stream) and every main
 // launch (on the caller's stream); qmha_profile_collect sums them per call.
@@ -266,8 +284,9 @@ qmha::F16Workspace f16_slice(const qmha::F16Workspace& w, size_t b0, int N, int 
 }
 
 int run(const float* Q, const float* K, const float* V, float* O, int B, int N, int d_model, int h, int variant,
-        void* ws, size_t ws_bytes, hipStream_t stream) {
+        void* ws, size_t ws_bytes, hipStream_t stream, unsigned flags = 0) {
     const int D = d_model / h;
+    const bool causal = flags & QMHA_FLAG_CAUSAL;  // check_flags passed: int8 / fp16 at a built head size
     const size_t need = workspace_bytes(B, N, h, D, variant);
     if (ws_bytes < need) {
         g_last_error = "workspace too small";
@@ -333,7 +352,13 @@ int run(const float* Q, const float* K, const float* V, float* O, int B, int N, 
             const int b0 = (int)((long long)B * c / nc), b1 = (int)((long long)B * (c + 1) / nc), nb = b1 - b0;
             if (nc > 1) QMHA_HIP_TRY(hipStreamWaitEvent(stream, side->ready[c], 0), "hipStreamWaitEvent");
             QMHA_MARK(rec.main, stream, true);
-            if (variant == QMHA_FA_TC_INT8_B) {
+            if (causal && variant == QMHA_FA_TC_INT8_B) {
+                QMHA_HIP_TRY(qmha::launch_fa_int8_causal_main(int8_slice(w8, b0, N, h, D), Q + b0 * slab, O + b0 * slab, nb, N,
+                                                              h, D, d_model, stream), "fa_int8 causal launch");
+            } else if (causal) {
+                QMHA_HIP_TRY(qmha::launch_fa_f16_causal_main(f16_slice(w16, b0, N, h, D), Q + b0 * slab, O + b0 * slab, nb, N,
+                                                             h, D, d_model, stream), "fa_f16 causal launch");
+            } else if (variant == QMHA_FA_TC_INT8_B) {
                 QMHA_HIP_TRY(qmha::launch_fa_int8_main(int8_slice(w8, b0, N, h, D), Q + b0 * slab, O + b0 * slab, nb, N, h, D,
                                                        d_model, stream), "fa_int8 launch");
             } else {
@@ -414,6 +439,22 @@ int qmha_solve_ex(const float* Q, const float* K, const float* V, float* O, int 
     st = lease_workspace(need, (hipStream_t)stream, &ws);
     if (st != QMHA_OK) return st;
     return run(Q, K, V, O, B, N, d_model, h, variant, ws.ptr, need, (hipStream_t)stream);
+}
+
+int qmha_solve_opts(const float* Q, const float* K, const float* V, float* O, int B, int N, int d_model, int h,
+                    int variant, unsigned flags, void* workspace, size_t workspace_bytes_, void* stream) {
+    int D = 0;
+    int st = check_shape(Q, K, V, O, B, N, d_model, h, variant, &D);
+    if (st != QMHA_OK) return st;
+    st = check_flags(variant, D, flags);
+    if (st != QMHA_OK) return st;
+    if (workspace)  // caller-owned scratch: the qmha_solve_ws rules
+        return run(Q, K, V, O, B, N, d_model, h, variant, workspace, workspace_bytes_, (hipStream_t)stream, flags);
+    const size_t need = workspace_bytes(B, N, h, D, variant);
+    WsLease ws;  // held until every kernel of this call is enqueued
+    st = lease_workspace(need, (hipStream_t)stream, &ws);
+    if (st != QMHA_OK) return st;
+    return run(Q, K, V, O, B, N, d_model, h, variant, ws.ptr, need, (hipStream_t)stream, flags);
 }
 
 size_t qmha_workspace_size(int B, int N, int d_model, int h, int variant) {

@@ -76,6 +76,15 @@ hipError_t launch_convert_f16(const float* Q, const float* K, const float* V, co
 hipError_t launch_fa_f16_main(const F16Workspace& w, const float* Qf, float* O, int B, int N, int H, int D, int d_model,
                               hipStream_t stream);
 
+// ---- causal main kernels (qmha_fa_causal.hip) ---------------------------------
+// the same workspaces as the non-causal paths (the pre-pass is unchanged); query row r attends keys
+// j <= r.  int8: d in {32, 64, 128}; fp16: d in {64, 128} (causal_supported); other d: hipErrorInvalidValue
+bool causal_supported(bool int8, int D);
+hipError_t launch_fa_int8_causal_main(const Int8Workspace& w, const float* Qf, float* O, int B, int N, int H, int D,
+                                      int d_model, hipStream_t stream);
+hipError_t launch_fa_f16_causal_main(const F16Workspace& w, const float* Qf, float* O, int B, int N, int H, int D,
+                                     int d_model, hipStream_t stream);
+
 // ---- FP32 (fa: scalar VALU kernel; fa_mfma: the same contract on v_mfma_f32_32x32x2_f32) -----
 hipError_t launch_fa_f32(const float* Q, const float* K, const float* V, float* O, int B, int N, int H, int D,
                          int d_model, bool mfma, hipStream_t stream);

@@ -10,6 +10,7 @@
 //   * a 3-D [B, N, d_model] input is B sequences in one launch;
 //   * the work is enqueued on PyTorch's current HIP stream (ordered with the caller's other
 //     ops) instead of private streams plus a blocking device synchronisation;
+//   * `causal` (trailing, default false): causal attention through qmha_solve_opts;
 //   * a rejected shape raises (TORCH_CHECK on the C-ABI status) instead of a device assert.
 #include <torch/extension.h>
 // ROCm PyTorch reports HIP devices as device type "cuda": the guard / current-stream
@@ -24,7 +25,7 @@
 using torch::Tensor;
 
 static Tensor flash_solve(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t d_model, int64_t num_heads,
-                          const std::string& kernel = "fa_tc_int8_b") {
+                          const std::string& kernel = "fa_tc_int8_b", bool causal = false) {
     TORCH_CHECK(Q.is_cuda() && K.is_cuda() && V.is_cuda(), "Inputs must be CUDA tensors");
     TORCH_CHECK(Q.dtype() == torch::kFloat32, "Q must be float32");
     TORCH_CHECK(K.dtype() == torch::kFloat32, "K must be float32");
@@ -49,9 +50,11 @@ static Tensor flash_solve(const Tensor& Q, const Tensor& K, const Tensor& V, int
     auto out = torch::empty_like(Qc);
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(Qc.device());
     const hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(Qc.device().index()).stream();
-    const int st = qmha_solve_ex(Qc.data_ptr<float>(), Kc.data_ptr<float>(), Vc.data_ptr<float>(),
-                                 out.data_ptr<float>(), static_cast<int>(B), static_cast<int>(N),
-                                 static_cast<int>(d_model), static_cast<int>(num_heads), variant, stream);
+    // causal = false enqueues exactly what qmha_solve_ex does (flags == 0)
+    const int st = qmha_solve_opts(Qc.data_ptr<float>(), Kc.data_ptr<float>(), Vc.data_ptr<float>(),
+                                   out.data_ptr<float>(), static_cast<int>(B), static_cast<int>(N),
+                                   static_cast<int>(d_model), static_cast<int>(num_heads), variant,
+                                   causal ? QMHA_FLAG_CAUSAL : 0u, nullptr, 0, stream);
     TORCH_CHECK(st == QMHA_OK, "flash_solve(", kernel, "): ", qmha_status_string(st), ": ", qmha_last_error());
     return out;
 }
@@ -65,7 +68,8 @@ PYBIND11_MODULE(torch_ext, m) {
           "  V: Value tensor [N, d_model]\n"
           "  d_model: Model dimension\n"
           "  num_heads: Number of attention heads\n"
-          "  kernel: Kernel variant (default: 'fa_tc_int8_b')",
+          "  kernel: Kernel variant (default: 'fa_tc_int8_b')\n"
+          "  causal: query row r attends keys j <= r (default: False)",
           pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("d_model"),
-          pybind11::arg("num_heads"), pybind11::arg("kernel") = "fa_tc_int8_b");
+          pybind11::arg("num_heads"), pybind11::arg("kernel") = "fa_tc_int8_b", pybind11::arg("causal") = false);
 }

@@ -11,7 +11,7 @@ from __future__ import annotations
 from . import _lib, jax_ext
 
 
-def flash_solve_jax(q, k, v, d_model, num_heads, kernel: str = _lib.DEFAULT_KERNEL):
+def flash_solve_jax(q, k, v, d_model, num_heads, kernel: str = _lib.DEFAULT_KERNEL, causal: bool = False):
     import jax.dlpack as jdlpack  # noqa: F401  (ImportError if JAX is absent)
     import torch
 
@@ -23,5 +23,5 @@ def flash_solve_jax(q, k, v, d_model, num_heads, kernel: str = _lib.DEFAULT_KERN
     out = torch.empty_like(qt)
     torch.cuda.synchronize(qt.device)
     jax_ext.flash_solve(qt.data_ptr(), kt.data_ptr(), vt.data_ptr(), out.data_ptr(), int(qt.shape[0]),
-                        int(d_model), int(num_heads), kernel)
+                        int(d_model), int(num_heads), kernel, causal)
     return jdlpack.from_dlpack(out)

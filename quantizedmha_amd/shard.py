@@ -70,7 +70,8 @@ def gather_outputs(O_local: torch.Tensor, batch: int, group=None) -> torch.Tenso
 
 def solve_shard_gather(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, d_model: int, num_heads: int,
                        batch: int, kernel: str = "fa_tc_int8_b", group=None, chunks: int = 1,
-                       solve_fn: Optional[Callable] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       solve_fn: Optional[Callable] = None, out: Optional[torch.Tensor] = None,
+                       causal: bool = False) -> torch.Tensor:
     """This rank's shard [b_r, N, d_model] in; the full [batch, N, d_model] out on every rank.
 
     Copy-free: the result tensor `out` is allocated once (or passed in) and every rank's kernels
@@ -86,7 +87,9 @@ def solve_shard_gather(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, d_mode
     rank), so a subgroup whose members are not global ranks 0..W-1 exchanges correctly.
 
     solve_fn (CPU tests: the oracle) returns a new tensor that is copied into the slab; the
-    default HIP path writes in place."""
+    default HIP path writes in place.  causal: passed on as `causal=True` (the mask is per sequence, so batch
+    sharding does not interact with it); a solve_fn is given the keyword only when it is set."""
+    kw = {"causal": True} if causal else {}
     world, rank = _world(group)
     lo, hi = batch_shard(batch, rank, world)
     if Q.shape[0] != hi - lo:
@@ -99,9 +102,9 @@ def solve_shard_gather(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, d_mode
     def compute(q, k, v, dst):
         if solve_fn is None:
             from .torch_ext import flash_solve  # HIP path; raises if the library is absent
-            flash_solve(q, k, v, d_model, num_heads, kernel, out=dst)
+            flash_solve(q, k, v, d_model, num_heads, kernel, out=dst, **kw)
         else:
-            dst.copy_(solve_fn(q, k, v, d_model, num_heads, kernel))
+            dst.copy_(solve_fn(q, k, v, d_model, num_heads, kernel, **kw))
 
     if world == 1:
         compute(Q, K, V, out)
@@ -135,7 +138,7 @@ def solve_shard_gather(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, d_mode
 def solve_sharded(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, d_model: int, num_heads: int,
                   kernel: str = "fa_tc_int8_b", gather: bool = True, group=None,
                   solve_fn: Optional[Callable] = None, batch: Optional[int] = None,
-                  chunks: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  chunks: int = 1, out: Optional[torch.Tensor] = None, causal: bool = False) -> torch.Tensor:
     """Batch-sharded attention forward.
 
     batch=None: Q, K, V are the FULL batch [B, N, d_model] (or views of it) and rank r slices
@@ -144,7 +147,7 @@ def solve_sharded(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, d_model: in
     Rank r computes its shard with `solve_fn` (default: torch_ext.flash_solve, the HIP
     kernels) and, if `gather`, returns the full [B, N, d_model] output on every rank
     (point-to-point exchange overlapped with compute when chunks > 1; written into `out` when
-    given), else its own shard.
+    given), else its own shard.  causal: passed to the solve as `causal=True`.
     """
     if Q.dim() != 3:
         raise ValueError("solve_sharded expects [B, N, d_model] inputs")
@@ -159,5 +162,5 @@ def solve_sharded(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, d_model: in
         lo, hi = batch_shard(batch, rank, world)
         if Q.shape[0] != hi - lo:
             raise ValueError(f"rank {rank} of {world}: expected its shard of {hi - lo} sequences, got {Q.shape[0]}")
-        return solve_fn(Q, K, V, d_model, num_heads, kernel)
-    return solve_shard_gather(Q, K, V, d_model, num_heads, batch, kernel, group, chunks, solve_fn, out)
+        return solve_fn(Q, K, V, d_model, num_heads, kernel, **({"causal": True} if causal else {}))
+    return solve_shard_gather(Q, K, V, d_model, num_heads, batch, kernel, group, chunks, solve_fn, out, causal)

@@ -2,6 +2,7 @@
 
 Same name, arguments, return value and error behaviour as the reference:
   flash_solve(Q, K, V, d_model, num_heads, kernel='fa_tc_int8_b') -> Tensor shaped like Q
+  (additive trailing arguments: out=None, causal=False)
   * non-GPU inputs        -> RuntimeError("Inputs must be CUDA tensors")       (:14)
   * non-fp32 inputs       -> RuntimeError("Q must be float32") etc.            (:15-17)
   * numel % d_model != 0  -> RuntimeError("Q.numel() must be divisible by d_model")  (:24)
@@ -35,10 +36,13 @@ def _shape(Q: torch.Tensor, d_model: int):
 
 
 def flash_solve(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, d_model: int, num_heads: int,
-                kernel: str = _lib.DEFAULT_KERNEL, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                kernel: str = _lib.DEFAULT_KERNEL, out: Optional[torch.Tensor] = None,
+                causal: bool = False) -> torch.Tensor:
     """FlashAttention solve (HIP).  Q, K, V: [N, d_model] (or [B, N, d_model]) fp32 on the GPU.
     out (additive): a contiguous fp32 tensor of Q's shape on Q's device to write the result into
-    (the batch-shard path writes each rank's rows straight into the gathered result)."""
+    (the batch-shard path writes each rank's rows straight into the gathered result).
+    causal (additive): query row r attends keys j <= r of its own sequence (fa_tc_int8_b at
+    d = 32 / 64 / 128, fa_tc_v1a at d = 64 / 128; anything else raises)."""
     if not (Q.is_cuda and K.is_cuda and V.is_cuda):
         raise RuntimeError("Inputs must be CUDA tensors")
     for name, t in (("Q", Q), ("K", K), ("V", V)):
@@ -61,8 +65,12 @@ def flash_solve(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, d_model: int,
     lib = _lib.load()
     with torch.cuda.device(Qc.device):
         stream = torch.cuda.current_stream(Qc.device).cuda_stream
-        st = lib.qmha_solve_ex(Qc.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), out.data_ptr(), B, N, d_model,
-                               num_heads, _lib.variant_id(kernel), stream)
+        if causal:
+            st = lib.qmha_solve_opts(Qc.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), out.data_ptr(), B, N, d_model,
+                                     num_heads, _lib.variant_id(kernel), _lib.QMHA_FLAG_CAUSAL, None, 0, stream)
+        else:
+            st = lib.qmha_solve_ex(Qc.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), out.data_ptr(), B, N, d_model,
+                                   num_heads, _lib.variant_id(kernel), stream)
     _lib.check(st, f"flash_solve({kernel})")
     return out
 

@@ -14,7 +14,6 @@
 #include <mutex>
 #include <string>
 #include <thread>
-#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -27,10 +26,11 @@ namespace {
 
 thread_local std::string g_last_error;
 
-int hip_fail(hipError_t e, const char* what) {
-    g_last_error = std::string(what) + ": " + hipGetErrorString(e);
-    return QMHA_ERR_HIP;
+int fail(int status, std::string why) {
+    g_last_error = std::move(why);
+    return status;
 }
+int hip_fail(hipError_t e, const char* what) { return fail(QMHA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
 
 #define QMHA_HIP_TRY(expr, what)                 \
     do {                                         \
@@ -38,63 +38,82 @@ int hip_fail(hipError_t e, const char* what) {
         if (_e != hipSuccess) return hip_fail(_e, what); \
     } while (0)
 
+// ---- the variants: one row each, read by every name / size / head-size question below ----
+// A head-size mask has bit d / 32 set for every built d (d % 32 == 0, d <= 256).
+template <class... T>
+constexpr unsigned d_mask(T... d) {
+    return (0u | ... | (1u << (d / 32)));
+}
+constexpr unsigned kEveryD = d_mask(32, 64, 96, 128, 160, 192, 224, 256), kTunedD = d_mask(32, 64, 128);
+
+struct VariantRow {
+    int id;
+    const char* name;
+    size_t (*ws_bytes)(int B, int N, int H, int D);  // nullptr: no scratch
+    unsigned plain, causal;                          // built head sizes without / with QMHA_FLAG_CAUSAL
+};
+constexpr VariantRow kVariants[] = {
+    {QMHA_FA, "fa", nullptr, kEveryD, 0},
+    {QMHA_FA_TC_V1A, "fa_tc_v1a", qmha::f16_workspace_bytes, kEveryD, d_mask(64, 128)},
+    {QMHA_FA_TC_INT8_B, "fa_tc_int8_b", [](int B, int N, int H, int D) { return qmha::int8_workspace_bytes(B, N, H, D); },
+     kEveryD, kTunedD},
+    {QMHA_UNFUSED, "unfused", qmha::unfused_workspace_bytes, kEveryD, 0},
+    {QMHA_FA_MFMA, "fa_mfma", nullptr, kEveryD, 0},
+    {QMHA_FA_TC_INT8_PT, "fa_tc_int8_pt", qmha::int8_pt_workspace_bytes, kTunedD, 0},  // no reference counterpart
+};
+
+const VariantRow* find_variant(int id) {
+    for (const VariantRow& r : kVariants)
+        if (r.id == id) return &r;
+    return nullptr;
+}
+
+bool built(unsigned mask, int D) { return D > 0 && D <= 256 && D % 32 == 0 && ((mask >> (D / 32)) & 1u); }
+
+std::string d_list(unsigned mask) {  // "32, 64, 128"
+    std::string s;
+    for (int d = 32; d <= 256; d += 32)
+        if (built(mask, d)) s += (s.empty() ? "" : ", ") + std::to_string(d);
+    return s;
+}
+
+size_t workspace_bytes(int B, int N, int H, int D, int variant) {
+    const VariantRow* v = find_variant(variant);
+    return v && v->ws_bytes ? v->ws_bytes(B, N, H, D) : 0;
+}
+
 int check_shape(const void* Q, const void* K, const void* V, const void* O, int B, int N, int d_model, int h,
                 int variant, int* D_out) {
-    if (!Q || !K || !V || !O) {
-        g_last_error = "null tensor pointer";
-        return QMHA_ERR_INVALID;
-    }
-    if (B < 1 || N < 1 || d_model < 1 || h < 1) {
-        g_last_error = "B, N, d_model and h must be positive";
-        return QMHA_ERR_INVALID;
-    }
-    if (d_model % h != 0) {  // config.h:27
-        g_last_error = "d_model must be divisible by h";
-        return QMHA_ERR_INVALID;
-    }
-    if (N % 32 != 0) {  // fa_tc_int8_b.cu:422-423 (N % Br), Br = Bc = 32
-        g_last_error = "N must be a multiple of 32";
-        return QMHA_ERR_INVALID;
-    }
+    if (!Q || !K || !V || !O) return fail(QMHA_ERR_INVALID, "null tensor pointer");
+    if (B < 1 || N < 1 || d_model < 1 || h < 1) return fail(QMHA_ERR_INVALID, "B, N, d_model and h must be positive");
+    if (d_model % h != 0) return fail(QMHA_ERR_INVALID, "d_model must be divisible by h");  // config.h:27
+    // fa_tc_int8_b.cu:422-423 (N % Br), Br = Bc = 32
+    if (N % 32 != 0) return fail(QMHA_ERR_INVALID, "N must be a multiple of 32");
     const int D = d_model / h;
-    if (variant < QMHA_FA || variant > QMHA_FA_TC_INT8_PT) {
-        g_last_error = "unknown variant";
-        return QMHA_ERR_INVALID;
-    }
-    if (D % 32 != 0) {  // config.h:32: static_assert(d % 32 == 0)
-        g_last_error = "head size d = d_model/h must be a multiple of 32";
-        return QMHA_ERR_INVALID;
-    }
-    if (D > 256) {  // the reference has no upper bound; here the int8 magic-biased accumulator's range
-        g_last_error = "head size d = d_model/h above 256 is not built";
-        return QMHA_ERR_NOSYS;
-    }
-    if (variant == QMHA_FA_TC_INT8_PT && D != 32 && D != 64 && D != 128) {  // no reference counterpart
-        g_last_error = "fa_tc_int8_pt is built for d = 32, 64, 128 only";
-        return QMHA_ERR_NOSYS;
-    }
-    if ((size_t)B * N * d_model > (size_t)INT32_MAX * 4) {
-        g_last_error = "tensor too large";
-        return QMHA_ERR_INVALID;
-    }
+    const VariantRow* v = find_variant(variant);
+    if (!v) return fail(QMHA_ERR_INVALID, "unknown variant");
+    // config.h:32: static_assert(d % 32 == 0)
+    if (D % 32 != 0) return fail(QMHA_ERR_INVALID, "head size d = d_model/h must be a multiple of 32");
+    // the reference has no upper bound; here the int8 magic-biased accumulator's range
+    if (D > 256) return fail(QMHA_ERR_NOSYS, "head size d = d_model/h above 256 is not built");
+    if (!built(v->plain, D))
+        return fail(QMHA_ERR_NOSYS, std::string(v->name) + " is built for d = " + d_list(v->plain) + " only");
+    if ((size_t)B * N * d_model > (size_t)INT32_MAX * 4) return fail(QMHA_ERR_INVALID, "tensor too large");
     *D_out = D;
     return QMHA_OK;
 }
 
 // qmha_solve_opts' flags, checked before any launch: unknown bits are invalid; QMHA_FLAG_CAUSAL is built
-// for fa_tc_int8_b at d = 32 / 64 / 128 and fa_tc_v1a at d = 64 / 128
+// for the variants and head sizes of the table's `causal` column
 int check_flags(int variant, int D, unsigned flags) {
-    if (flags & ~(unsigned)QMHA_FLAG_CAUSAL) {
-        g_last_error = "unknown flag bits " + std::to_string(flags & ~(unsigned)QMHA_FLAG_CAUSAL);
-        return QMHA_ERR_INVALID;
-    }
-    if (flags & QMHA_FLAG_CAUSAL) {
-        const bool int8 = variant == QMHA_FA_TC_INT8_B;
-        if ((!int8 && variant != QMHA_FA_TC_V1A) || !qmha::causal_supported(int8, D)) {
-            g_last_error = std::string("causal attention is not built for variant ") + qmha_variant_name(variant) +
-                           " at d = " + std::to_string(D) + " (fa_tc_int8_b: d = 32, 64, 128; fa_tc_v1a: d = 64, 128)";
-            return QMHA_ERR_NOSYS;
-        }
+    const unsigned unknown = flags & ~(unsigned)QMHA_FLAG_CAUSAL;
+    if (unknown) return fail(QMHA_ERR_INVALID, "unknown flag bits " + std::to_string(unknown));
+    if ((flags & QMHA_FLAG_CAUSAL) && !built(find_variant(variant)->causal, D)) {
+        std::string have;
+        for (const VariantRow& r : kVariants)
+            if (r.causal) have += (have.empty() ? "" : "; ") + std::string(r.name) + ": d = " + d_list(r.causal);
+        return fail(QMHA_ERR_NOSYS, std::string("causal attention is not built for variant ") + qmha_variant_name(variant) +
+                                        " at d = " + std::to_string(D) + " (" + have + ")");
     }
     return QMHA_OK;
 }
@@ -102,8 +121,9 @@ int check_flags(int variant, int D, unsigned flags) {
 // ---- profiling --------------------------------------------------------------------------
 // Per call: event pairs around every pre-pass launch (on the pre-pass stream) and every main
 // launch (on the caller's stream); qmha_profile_collect sums them per call.
+using Marks = std::vector<std::pair<hipEvent_t, hipEvent_t>>;
 struct ProfRec {
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pre, main;
+    Marks pre, main;
 };
 std::mutex g_prof_mu;
 bool g_prof_on = false;
@@ -121,67 +141,41 @@ hipEvent_t take_event() {
     return e;
 }
 
-// ---- pre-pass / main-kernel overlap (int8 and fp16 paths) ------------------------------
-// The HBM-bound pre-pass (quantise / convert) of batch chunk c+1 runs on a library-owned
-// second stream while the compute-bound main kernel of chunk c runs on the caller's stream.
-// Chunks are disjoint slices of the same workspace arrays, so only "pre(c) before main(c)"
-// and "previous call done before pre(0)" need ordering.  QMHA_OVERLAP_CHUNKS (default 1 =
-// off: measured slower at C4, the co-running pre-pass slows the main kernel more than it hides,
-// profiles/r01/overlap_sweep.txt) sets the number of chunks.
-struct SideStream {
-    hipStream_t s = nullptr;
-    hipEvent_t start = nullptr;
-    std::vector<hipEvent_t> ready;
-};
-std::mutex g_side_mu;
-std::map<std::tuple<int, void*, std::thread::id>, SideStream> g_side;  // keyed like the workspace slots
-
-std::atomic<int> g_overlap_chunks{-1};  // -1: not yet read from QMHA_OVERLAP_CHUNKS
-
-int overlap_chunks(int B) {
-    int c = g_overlap_chunks.load();
-    if (c < 0) {
-#ifdef QMHA_ABLATION  // profiling builds: QMHA_OVERLAP_CHUNKS sets the default (production: the API only)
-        const char* e = std::getenv("QMHA_OVERLAP_CHUNKS");
-        c = e ? std::atoi(e) : 1;
-#else
-        c = 1;
-#endif
-        c = c < 1 ? 1 : (c > 16 ? 16 : c);
-        g_overlap_chunks.store(c);
+// one profiling event recorded on `s`: it opens a new pair of `v` (begin) or closes the last one
+int mark(Marks& v, hipStream_t s, bool begin) {
+    hipEvent_t e;
+    {
+        std::lock_guard<std::mutex> lk(g_prof_mu);
+        e = take_event();
     }
-    return c > B ? B : c;
-}
-
-int get_side(hipStream_t stream, int nchunks, SideStream** out) {
-    int dev = 0;
-    QMHA_HIP_TRY(hipGetDevice(&dev), "hipGetDevice");
-    std::lock_guard<std::mutex> lk(g_side_mu);
-    SideStream& ss = g_side[{dev, (void*)stream, stream == hipStreamPerThread ? std::this_thread::get_id() : std::thread::id()}];
-    if (!ss.s) {
-        QMHA_HIP_TRY(hipStreamCreateWithFlags(&ss.s, hipStreamNonBlocking), "hipStreamCreate");
-        QMHA_HIP_TRY(hipEventCreateWithFlags(&ss.start, hipEventDisableTiming), "hipEventCreate");
-    }
-    while ((int)ss.ready.size() < nchunks) {
-        hipEvent_t e = nullptr;
-        QMHA_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
-        ss.ready.push_back(e);
-    }
-    *out = &ss;
+    if (!e) return fail(QMHA_ERR_HIP, "hipEventCreate failed");
+    if (begin) v.push_back({e, nullptr});
+    else v.back().second = e;
+    QMHA_HIP_TRY(hipEventRecord(e, s), "hipEventRecord");
     return QMHA_OK;
 }
 
-// ---- library-owned workspaces, one per (device, stream) --------------------------------
-// Threading contract (INTEGRATION.md): any number of host threads may call every entry point at once.
+// enqueue one launch on `s`, between a pair of profiling events when `marks` is given
+template <class Launch>
+int timed(Marks* marks, hipStream_t s, const char* what, Launch&& launch) {
+    int st = marks ? mark(*marks, s, true) : QMHA_OK;
+    if (st != QMHA_OK) return st;
+    QMHA_HIP_TRY(launch(), what);
+    return marks ? mark(*marks, s, false) : QMHA_OK;
+}
+
+// ---- library-owned per-stream state, one slot per (device, stream) ---------------------
+// Threading contract (INTEGRATION.md 7): any number of host threads may call every entry point at once.
 // The reference gets that from per-call cudaMalloc'd scratch and private streams (include/launchers.h:
-// 27-33, freed at :64-71); here the scratch is cached, so a call LEASES its (device, stream) slot: the
-// slot's mutex is held from the moment the buffer is handed out until the call's last kernel that uses
-// it has been enqueued.  Calls on one stream therefore enqueue one whole call after another (pre-pass and
-// main kernel of a call are never separated by another call's pre-pass), and the stream runs them in that
-// order.  Calls on different streams use different slots.  hipStreamPerThread names a different stream
-// in every thread, so its slot key carries the thread id.  A slot that must grow never frees the buffer
-// other enqueued work may still read: the old buffer is retired behind an event recorded on the slot's
-// stream and freed once that event has completed (checked at the slot's next lease, or at release).
+// 27-33, freed at :64-71); here the scratch and the overlap side stream are cached, so a call LEASES its
+// (device, stream) slot: the slot's mutex is held from before the call's first HIP call until its last
+// kernel has been enqueued, and nothing in a slot is touched outside its lease.  Calls on one stream
+// therefore enqueue one whole call after another (pre-pass and main kernel of a call are never separated
+// by another call's pre-pass), and the stream runs them in that order.  Calls on different streams use
+// different slots.  hipStreamPerThread names a different stream in every thread, so its slot key carries
+// the thread id.  A slot that must grow never frees the buffer other enqueued work may still read: the
+// old buffer is retired behind an event recorded on the slot's stream and freed once that event has
+// completed (checked at the slot's next lease for scratch, or at release).
 struct WsKey {
     int dev;
     void* stream;
@@ -197,8 +191,12 @@ struct WsSlot {
     void* ptr = nullptr;
     size_t bytes = 0;
     std::vector<std::pair<void*, hipEvent_t>> retired;  // grown-out buffers, freed once their event completed
+    // pre-pass / main-kernel overlap (run_chunked), created at the first call with more than one chunk
+    hipStream_t side = nullptr;
+    hipEvent_t start = nullptr;
+    std::vector<hipEvent_t> ready;  // one per chunk
 };
-std::mutex g_ws_mu;  // guards the map only (slots are never erased while the library is in use)
+std::mutex g_ws_mu;  // guards the map only (slots are never erased); never held while waiting for a lease by a caller
 std::map<WsKey, std::unique_ptr<WsSlot>> g_ws;
 
 // free the retired buffers whose last reader has completed (all when `wait`); caller holds the lease
@@ -216,28 +214,28 @@ void reap_retired(WsSlot& s, bool wait) {
     }
 }
 
-// A held workspace: the buffer stays this call's until the lease is destroyed (after the last enqueue).
+// A held slot: slot and buffer stay this call's until the lease is destroyed (after the last enqueue).
 struct WsLease {
     std::unique_lock<std::mutex> lk;
-    void* ptr = nullptr;
+    WsSlot* slot = nullptr;
+    void* ptr = nullptr;  // >= `need` bytes (nullptr for need == 0: a call that brings its own scratch, or none)
 };
 
 int lease_workspace(size_t need, hipStream_t stream, WsLease* out) {
     out->ptr = nullptr;
     int dev = 0;
     QMHA_HIP_TRY(hipGetDevice(&dev), "hipGetDevice");
-    WsSlot* slot;
     {
         std::lock_guard<std::mutex> lk(g_ws_mu);
         const WsKey key{dev, (void*)stream, stream == hipStreamPerThread ? std::this_thread::get_id() : std::thread::id()};
         std::unique_ptr<WsSlot>& sp = g_ws[key];
         if (!sp) sp.reset(new WsSlot);
-        slot = sp.get();
+        out->slot = sp.get();
     }
-    out->lk = std::unique_lock<std::mutex>(slot->lease);
-    WsSlot& s = *slot;
+    out->lk = std::unique_lock<std::mutex>(out->slot->lease);
+    WsSlot& s = *out->slot;
+    if (need == 0) return QMHA_OK;  // no HIP call beyond hipGetDevice: qmha_solve_ws stays capturable in a graph
     if (!s.retired.empty()) reap_retired(s, false);
-    if (need == 0) return QMHA_OK;
     if (s.bytes < need) {
         if (s.ptr) {
             // work already enqueued on this stream may still read the old buffer: retire it behind an event
@@ -255,8 +253,7 @@ int lease_workspace(size_t need, hipStream_t stream, WsLease* out) {
         const size_t alloc = qmha::align_up(need + need / 8, 1 << 20);
         if (hipMalloc(&s.ptr, alloc) != hipSuccess) {
             s.ptr = nullptr;
-            g_last_error = "hipMalloc of workspace failed";
-            return QMHA_ERR_NOMEM;
+            return fail(QMHA_ERR_NOMEM, "hipMalloc of workspace failed");
         }
         s.bytes = alloc;
     }
@@ -264,137 +261,198 @@ int lease_workspace(size_t need, hipStream_t stream, WsLease* out) {
     return QMHA_OK;
 }
 
-size_t workspace_bytes(int B, int N, int H, int D, int variant) {
-    switch (variant) {
-        case QMHA_FA_TC_INT8_B: return qmha::int8_workspace_bytes(B, N, H, D);
-        case QMHA_FA_TC_INT8_PT: return qmha::int8_pt_workspace_bytes(B, N, H, D);
-        case QMHA_FA_TC_V1A: return qmha::f16_workspace_bytes(B, N, H, D);
-        case QMHA_UNFUSED: return qmha::unfused_workspace_bytes(B, N, H, D);
-        default: return 0;
+// ---- pre-pass / main-kernel overlap (int8 and fp16 paths) ------------------------------
+// The HBM-bound pre-pass (quantise / convert) of batch chunk c+1 runs on the slot's side stream
+// while the compute-bound main kernel of chunk c runs on the caller's stream.
+// Chunks are disjoint slices of the same workspace arrays, so only "pre(c) before main(c)"
+// and "previous call done before pre(0)" need ordering.  QMHA_OVERLAP_CHUNKS (default 1 =
+// off: measured slower at C4, the co-running pre-pass slows the main kernel more than it hides,
+// profiles/r01/overlap_sweep.txt) sets the number of chunks.
+constexpr int kMaxChunks = 16;
+std::atomic<int> g_overlap_chunks{-1};  // -1: not yet read from QMHA_OVERLAP_CHUNKS
+
+int clamp_chunks(int c) { return c < 1 ? 1 : (c > kMaxChunks ? kMaxChunks : c); }
+
+int overlap_chunks(int B) {
+    int c = g_overlap_chunks.load();
+    if (c < 0) {
+#ifdef QMHA_ABLATION  // profiling builds: QMHA_OVERLAP_CHUNKS sets the default (production: the API only)
+        const char* e = std::getenv("QMHA_OVERLAP_CHUNKS");
+        c = clamp_chunks(e ? std::atoi(e) : 1);
+#else
+        c = 1;
+#endif
+        g_overlap_chunks.store(c);
     }
+    return c > B ? B : c;
 }
 
-qmha::Int8Workspace int8_slice(const qmha::Int8Workspace& w, size_t b0, int N, int H, int D) {
+// the slot's side stream with `nchunks` ready events; caller holds the lease
+int ensure_side(WsSlot& s, int nchunks) {
+    if (!s.side) QMHA_HIP_TRY(hipStreamCreateWithFlags(&s.side, hipStreamNonBlocking), "hipStreamCreate");
+    if (!s.start) QMHA_HIP_TRY(hipEventCreateWithFlags(&s.start, hipEventDisableTiming), "hipEventCreate");
+    while ((int)s.ready.size() < nchunks) {
+        hipEvent_t e = nullptr;
+        QMHA_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
+        s.ready.push_back(e);
+    }
+    return QMHA_OK;
+}
+
+struct Chunk {  // sequences [b0, b0 + nb) of the batch
+    size_t b0;
+    int nb;
+};
+
+// A call of a chunked variant: pre(chunk, s) / main(chunk) enqueue one chunk's pre-pass on stream s / its
+// main kernel on the caller's stream.  Every pre-pass is enqueued first (the side stream runs ahead).
+template <class Pre, class Main>
+int run_chunked(int B, hipStream_t stream, WsSlot& slot, Marks* pre_m, Marks* main_m, const char* pre_what, Pre&& pre,
+                const char* main_what, Main&& main) {
+    const int nc = overlap_chunks(B);
+    hipStream_t pre_s = stream;
+    if (nc > 1) {
+        int st = ensure_side(slot, nc);
+        if (st != QMHA_OK) return st;
+        QMHA_HIP_TRY(hipEventRecord(slot.start, stream), "hipEventRecord");
+        QMHA_HIP_TRY(hipStreamWaitEvent(slot.side, slot.start, 0), "hipStreamWaitEvent");
+        pre_s = slot.side;
+    }
+    Chunk ch[kMaxChunks];
+    for (int c = 0; c < nc; ++c) {
+        const long long b0 = (long long)B * c / nc, b1 = (long long)B * (c + 1) / nc;
+        ch[c] = Chunk{(size_t)b0, (int)(b1 - b0)};
+        int st = timed(pre_m, pre_s, pre_what, [&] { return pre(ch[c], pre_s); });
+        if (st != QMHA_OK) return st;
+        if (nc > 1) QMHA_HIP_TRY(hipEventRecord(slot.ready[c], pre_s), "hipEventRecord");
+    }
+    for (int c = 0; c < nc; ++c) {
+        if (nc > 1) QMHA_HIP_TRY(hipStreamWaitEvent(stream, slot.ready[c], 0), "hipStreamWaitEvent");
+        int st = timed(main_m, stream, main_what, [&] { return main(ch[c]); });
+        if (st != QMHA_OK) return st;
+    }
+    return QMHA_OK;
+}
+
+qmha::Int8Workspace int8_slice(qmha::Int8Workspace w, size_t b0, int N, int H, int D) {
     const size_t e = b0 * H * N * D, g = b0 * H * (N / 32);  // 32-row quantisation groups
-    return qmha::Int8Workspace{nullptr, w.Ki + e, w.Vh + e, nullptr, w.sK + g, w.sV + g};
+    w.Ki += e, w.Vh += e, w.sK += g, w.sV += g;
+    return w;
 }
-qmha::F16Workspace f16_slice(const qmha::F16Workspace& w, size_t b0, int N, int H, int D) {
+qmha::F16Workspace f16_slice(qmha::F16Workspace w, size_t b0, int N, int H, int D) {
     const size_t e = b0 * H * N * D;
-    return qmha::F16Workspace{nullptr, w.Kh + e, w.Vt + e};
+    w.Kh += e, w.Vt += e;
+    return w;
 }
 
+// Enqueue one checked call on `stream`; `ws` holds workspace_bytes(...) bytes and `slot` is leased by the caller.
 int run(const float* Q, const float* K, const float* V, float* O, int B, int N, int d_model, int h, int variant,
-        void* ws, size_t ws_bytes, hipStream_t stream, unsigned flags = 0) {
+        unsigned flags, void* ws, WsSlot& slot, hipStream_t stream) {
     const int D = d_model / h;
     const bool causal = flags & QMHA_FLAG_CAUSAL;  // check_flags passed: int8 / fp16 at a built head size
-    const size_t need = workspace_bytes(B, N, h, D, variant);
-    if (ws_bytes < need) {
-        g_last_error = "workspace too small";
-        return QMHA_ERR_INVALID;
-    }
     bool prof;
     {
         std::lock_guard<std::mutex> lk(g_prof_mu);
         prof = g_prof_on;
     }
     ProfRec rec;
-    auto mark = [&](std::vector<std::pair<hipEvent_t, hipEvent_t>>& v, hipStream_t s, bool begin) -> int {
-        if (!prof) return QMHA_OK;
-        hipEvent_t e;
-        {
-            std::lock_guard<std::mutex> lk(g_prof_mu);
-            e = take_event();
+    Marks *pre_m = prof ? &rec.pre : nullptr, *main_m = prof ? &rec.main : nullptr;
+    const size_t slab = (size_t)N * d_model;  // floats per sequence
+    int st;
+    switch (variant) {
+        case QMHA_FA_TC_INT8_B: {
+            const qmha::Int8Workspace w8 = qmha::int8_carve(ws, B, N, h, D);
+            const auto launch_main = causal ? qmha::launch_fa_int8_causal_main : qmha::launch_fa_int8_main;
+            st = run_chunked(
+                B, stream, slot, pre_m, main_m, "quant_int8 launch",
+                [&](Chunk c, hipStream_t s) {
+                    const qmha::Int8Workspace w = int8_slice(w8, c.b0, N, h, D);
+                    return qmha::launch_quant_int8(Q + c.b0 * slab, K + c.b0 * slab, V + c.b0 * slab, w, w.Vh, /*v_mode=*/1,
+                                                   c.nb, N, h, D, d_model, s, /*first_tensor=*/1);
+                },
+                causal ? "fa_int8 causal launch" : "fa_int8 launch",
+                [&](Chunk c) {
+                    return launch_main(int8_slice(w8, c.b0, N, h, D), Q + c.b0 * slab, O + c.b0 * slab, c.nb, N, h, D, d_model,
+                                       stream);
+                });
+            break;
         }
-        if (!e) {
-            g_last_error = "hipEventCreate failed";
-            return QMHA_ERR_HIP;
+        case QMHA_FA_TC_V1A: {
+            const qmha::F16Workspace w16 = qmha::f16_carve(ws, B, N, h, D);
+            const auto launch_main = causal ? qmha::launch_fa_f16_causal_main : qmha::launch_fa_f16_main;
+            st = run_chunked(
+                B, stream, slot, pre_m, main_m, "convert_f16 launch",
+                [&](Chunk c, hipStream_t s) {
+                    return qmha::launch_convert_f16(Q + c.b0 * slab, K + c.b0 * slab, V + c.b0 * slab,
+                                                    f16_slice(w16, c.b0, N, h, D), c.nb, N, h, D, d_model, s);
+                },
+                causal ? "fa_f16 causal launch" : "fa_f16 launch",
+                [&](Chunk c) {
+                    return launch_main(f16_slice(w16, c.b0, N, h, D), Q + c.b0 * slab, O + c.b0 * slab, c.nb, N, h, D, d_model,
+                                       stream);
+                });
+            break;
         }
-        if (begin) v.push_back({e, nullptr});
-        else v.back().second = e;
-        QMHA_HIP_TRY(hipEventRecord(e, s), "hipEventRecord");
-        return QMHA_OK;
-    };
-#define QMHA_MARK(vec, s, begin)                       \
-    do {                                               \
-        int _st = mark(vec, s, begin);                 \
-        if (_st != QMHA_OK) return _st;                \
-    } while (0)
-
-    if (variant == QMHA_FA_TC_INT8_B || variant == QMHA_FA_TC_V1A) {
-        const size_t slab = (size_t)N * d_model;  // floats per sequence
-        const int nc = overlap_chunks(B);
-        SideStream* side = nullptr;
-        if (nc > 1) {
-            int st = get_side(stream, nc, &side);
-            if (st != QMHA_OK) return st;
-            QMHA_HIP_TRY(hipEventRecord(side->start, stream), "hipEventRecord");
-            QMHA_HIP_TRY(hipStreamWaitEvent(side->s, side->start, 0), "hipStreamWaitEvent");
+        case QMHA_FA_TC_INT8_PT: {
+            // per-tensor mode: group absmax of Q, K, V + K/V quantisation with the head-slice scales
+            // (two pre-pass launches), then the main kernel (Q quantised in registers)
+            const qmha::Int8Workspace w = qmha::int8_pt_carve(ws, B, N, h, D);
+            st = timed(pre_m, stream, "quant_int8_pt launch",
+                       [&] { return qmha::launch_quant_int8_pt(Q, K, V, w, B, N, h, D, d_model, stream); });
+            if (st == QMHA_OK)
+                st = timed(main_m, stream, "fa_int8_pt launch",
+                           [&] { return qmha::launch_fa_int8_pt_main(w, Q, O, B, N, h, D, d_model, stream); });
+            break;
         }
-        const hipStream_t pre_s = nc > 1 ? side->s : stream;
-        const qmha::Int8Workspace w8 = variant == QMHA_FA_TC_INT8_B ? qmha::int8_carve(ws, B, N, h, D) : qmha::Int8Workspace{};
-        const qmha::F16Workspace w16 = variant == QMHA_FA_TC_V1A ? qmha::f16_carve(ws, B, N, h, D) : qmha::F16Workspace{};
-        // every pre-pass is enqueued first (the side stream runs ahead), then the main kernels
-        for (int c = 0; c < nc; ++c) {
-            const int b0 = (int)((long long)B * c / nc), b1 = (int)((long long)B * (c + 1) / nc), nb = b1 - b0;
-            QMHA_MARK(rec.pre, pre_s, true);
-            if (variant == QMHA_FA_TC_INT8_B) {
-                const qmha::Int8Workspace w = int8_slice(w8, b0, N, h, D);
-                QMHA_HIP_TRY(qmha::launch_quant_int8(Q + b0 * slab, K + b0 * slab, V + b0 * slab, w, w.Vh, /*v_mode=*/1, nb, N, h, D,
-                                                     d_model, pre_s, /*first_tensor=*/1), "quant_int8 launch");
-            } else {
-                QMHA_HIP_TRY(qmha::launch_convert_f16(Q + b0 * slab, K + b0 * slab, V + b0 * slab, f16_slice(w16, b0, N, h, D),
-                                                      nb, N, h, D, d_model, pre_s), "convert_f16 launch");
-            }
-            QMHA_MARK(rec.pre, pre_s, false);
-            if (nc > 1) QMHA_HIP_TRY(hipEventRecord(side->ready[c], pre_s), "hipEventRecord");
-        }
-        for (int c = 0; c < nc; ++c) {
-            const int b0 = (int)((long long)B * c / nc), b1 = (int)((long long)B * (c + 1) / nc), nb = b1 - b0;
-            if (nc > 1) QMHA_HIP_TRY(hipStreamWaitEvent(stream, side->ready[c], 0), "hipStreamWaitEvent");
-            QMHA_MARK(rec.main, stream, true);
-            if (causal && variant == QMHA_FA_TC_INT8_B) {
-                QMHA_HIP_TRY(qmha::launch_fa_int8_causal_main(int8_slice(w8, b0, N, h, D), Q + b0 * slab, O + b0 * slab, nb, N,
-                                                              h, D, d_model, stream), "fa_int8 causal launch");
-            } else if (causal) {
-                QMHA_HIP_TRY(qmha::launch_fa_f16_causal_main(f16_slice(w16, b0, N, h, D), Q + b0 * slab, O + b0 * slab, nb, N,
-                                                             h, D, d_model, stream), "fa_f16 causal launch");
-            } else if (variant == QMHA_FA_TC_INT8_B) {
-                QMHA_HIP_TRY(qmha::launch_fa_int8_main(int8_slice(w8, b0, N, h, D), Q + b0 * slab, O + b0 * slab, nb, N, h, D,
-                                                       d_model, stream), "fa_int8 launch");
-            } else {
-                QMHA_HIP_TRY(qmha::launch_fa_f16_main(f16_slice(w16, b0, N, h, D), Q + b0 * slab, O + b0 * slab, nb, N, h, D,
-                                                      d_model, stream), "fa_f16 launch");
-            }
-            QMHA_MARK(rec.main, stream, false);
-        }
-    } else if (variant == QMHA_FA_TC_INT8_PT) {
-        // per-tensor mode: group absmax of Q, K, V + K/V quantisation with the head-slice scales
-        // (two pre-pass launches), then the main kernel (Q quantised in registers)
-        const qmha::Int8Workspace w = qmha::int8_pt_carve(ws, B, N, h, D);
-        QMHA_MARK(rec.pre, stream, true);
-        QMHA_HIP_TRY(qmha::launch_quant_int8_pt(Q, K, V, w, B, N, h, D, d_model, stream), "quant_int8_pt launch");
-        QMHA_MARK(rec.pre, stream, false);
-        QMHA_MARK(rec.main, stream, true);
-        QMHA_HIP_TRY(qmha::launch_fa_int8_pt_main(w, Q, O, B, N, h, D, d_model, stream), "fa_int8_pt launch");
-        QMHA_MARK(rec.main, stream, false);
-    } else if (variant == QMHA_FA || variant == QMHA_FA_MFMA) {
-        QMHA_MARK(rec.main, stream, true);
-        QMHA_HIP_TRY(qmha::launch_fa_f32(Q, K, V, O, B, N, h, D, d_model, variant == QMHA_FA_MFMA, stream),
-                     "fa_f32 launch");
-        QMHA_MARK(rec.main, stream, false);
-    } else if (variant == QMHA_UNFUSED) {
-        QMHA_MARK(rec.main, stream, true);
-        QMHA_HIP_TRY(qmha::launch_unfused(Q, K, V, O, ws, B, N, h, D, d_model, stream), "unfused launch");
-        QMHA_MARK(rec.main, stream, false);
-    } else {
-        g_last_error = "unknown variant";
-        return QMHA_ERR_INVALID;
+        case QMHA_FA:
+        case QMHA_FA_MFMA:
+            st = timed(main_m, stream, "fa_f32 launch",
+                       [&] { return qmha::launch_fa_f32(Q, K, V, O, B, N, h, D, d_model, variant == QMHA_FA_MFMA, stream); });
+            break;
+        case QMHA_UNFUSED:
+            st = timed(main_m, stream, "unfused launch",
+                       [&] { return qmha::launch_unfused(Q, K, V, O, ws, B, N, h, D, d_model, stream); });
+            break;
+        default: return fail(QMHA_ERR_INVALID, "unknown variant");
     }
-#undef QMHA_MARK
+    if (st != QMHA_OK) return st;
     if (prof) {
         std::lock_guard<std::mutex> lk(g_prof_mu);
         g_prof_recs.push_back(std::move(rec));
     }
+    return QMHA_OK;
+}
+
+// The one solve path behind qmha_solve_ex / _ws / _opts: checks (before any HIP call), the slot's lease held
+// until the last kernel is enqueued, run().  caller_owned: scratch is the caller's `caller_bytes` at caller_ws,
+// else the slot's own.  A caller workspace leases the slot all the same (need == 0): the overlap side
+// stream lives there.
+int solve_on(const float* Q, const float* K, const float* V, float* O, int B, int N, int d_model, int h, int variant,
+             unsigned flags, bool caller_owned, void* caller_ws, size_t caller_bytes, hipStream_t stream) {
+    int D = 0;
+    int st = check_shape(Q, K, V, O, B, N, d_model, h, variant, &D);
+    if (st != QMHA_OK) return st;
+    st = check_flags(variant, D, flags);
+    if (st != QMHA_OK) return st;
+    const size_t need = workspace_bytes(B, N, h, D, variant);
+    if (caller_owned && caller_bytes < need) return fail(QMHA_ERR_INVALID, "workspace too small");
+    WsLease lease;
+    st = lease_workspace(caller_owned ? 0 : need, stream, &lease);
+    if (st != QMHA_OK) return st;
+    return run(Q, K, V, O, B, N, d_model, h, variant, flags, caller_owned ? caller_ws : lease.ptr, *lease.slot, stream);
+}
+
+// The debug hooks' skeleton: `need` bytes of the null stream's slot, body(ws) enqueues the pre-pass and the
+// dumping kernel there, then the lease is dropped and the stream waited for (the hooks are blocking).
+template <class Body>
+int debug_run(size_t need, Body&& body) {
+    WsLease lease;
+    int st = lease_workspace(need, nullptr, &lease);
+    if (st != QMHA_OK) return st;
+    st = body(lease.ptr);
+    if (st != QMHA_OK) return st;
+    lease.lk.unlock();
+    QMHA_HIP_TRY(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
     return QMHA_OK;
 }
 
@@ -423,38 +481,20 @@ extern "C" {
 
 int qmha_solve_ws(const float* Q, const float* K, const float* V, float* O, int B, int N, int d_model, int h,
                   int variant, void* workspace, size_t workspace_bytes_, void* stream) {
-    int D = 0;
-    int st = check_shape(Q, K, V, O, B, N, d_model, h, variant, &D);
-    if (st != QMHA_OK) return st;
-    return run(Q, K, V, O, B, N, d_model, h, variant, workspace, workspace_bytes_, (hipStream_t)stream);
+    // always the caller's scratch: a null one holds no bytes, whatever size is claimed
+    return solve_on(Q, K, V, O, B, N, d_model, h, variant, 0, true, workspace, workspace ? workspace_bytes_ : 0,
+                    (hipStream_t)stream);
 }
 
 int qmha_solve_ex(const float* Q, const float* K, const float* V, float* O, int B, int N, int d_model, int h,
                   int variant, void* stream) {
-    int D = 0;
-    int st = check_shape(Q, K, V, O, B, N, d_model, h, variant, &D);
-    if (st != QMHA_OK) return st;
-    const size_t need = workspace_bytes(B, N, h, D, variant);
-    WsLease ws;  // held until every kernel of this call is enqueued
-    st = lease_workspace(need, (hipStream_t)stream, &ws);
-    if (st != QMHA_OK) return st;
-    return run(Q, K, V, O, B, N, d_model, h, variant, ws.ptr, need, (hipStream_t)stream);
+    return solve_on(Q, K, V, O, B, N, d_model, h, variant, 0, false, nullptr, 0, (hipStream_t)stream);
 }
 
 int qmha_solve_opts(const float* Q, const float* K, const float* V, float* O, int B, int N, int d_model, int h,
                     int variant, unsigned flags, void* workspace, size_t workspace_bytes_, void* stream) {
-    int D = 0;
-    int st = check_shape(Q, K, V, O, B, N, d_model, h, variant, &D);
-    if (st != QMHA_OK) return st;
-    st = check_flags(variant, D, flags);
-    if (st != QMHA_OK) return st;
-    if (workspace)  // caller-owned scratch: the qmha_solve_ws rules
-        return run(Q, K, V, O, B, N, d_model, h, variant, workspace, workspace_bytes_, (hipStream_t)stream, flags);
-    const size_t need = workspace_bytes(B, N, h, D, variant);
-    WsLease ws;  // held until every kernel of this call is enqueued
-    st = lease_workspace(need, (hipStream_t)stream, &ws);
-    if (st != QMHA_OK) return st;
-    return run(Q, K, V, O, B, N, d_model, h, variant, ws.ptr, need, (hipStream_t)stream, flags);
+    return solve_on(Q, K, V, O, B, N, d_model, h, variant, flags, workspace != nullptr, workspace, workspace_bytes_,
+                    (hipStream_t)stream);
 }
 
 size_t qmha_workspace_size(int B, int N, int d_model, int h, int variant) {
@@ -479,18 +519,13 @@ int qmha_quantize_int8(const float* X, int B, int N, int d_model, int h, int8_t*
     int D = 0;
     int st = check_shape(X, X, X, Xi, B, N, d_model, h, QMHA_FA_TC_INT8_B, &D);
     if (st != QMHA_OK) return st;
-    if (!scales || layout < 0 || layout > 2) {
-        g_last_error = "bad scales pointer or layout";
-        return QMHA_ERR_INVALID;
-    }
-    if (layout == 2 && D != 32 && D != 64 && D != 128) {  // the per-tensor mode's quantiser
-        g_last_error = "layout 2 (per-tensor scales) is built for d = 32, 64, 128 only";
-        return QMHA_ERR_NOSYS;
-    }
-    if (layout == 2) {  // per-tensor (head-slice) scales: the single-read pass (slice counters in a workspace)
-        const size_t need = qmha::align_up((size_t)6 * B * h * sizeof(uint32_t), 256);
-        WsLease ws;  // held until the pass is enqueued
-        st = lease_workspace(need, (hipStream_t)stream, &ws);
+    if (!scales || layout < 0 || layout > 2) return fail(QMHA_ERR_INVALID, "bad scales pointer or layout");
+    if (layout == 2) {  // per-tensor (head-slice) scales: the per-tensor mode's single-read pass
+        const unsigned have = find_variant(QMHA_FA_TC_INT8_PT)->plain;
+        if (!built(have, D))
+            return fail(QMHA_ERR_NOSYS, "layout 2 (per-tensor scales) is built for d = " + d_list(have) + " only");
+        WsLease ws;  // the slice counters; held until the pass is enqueued
+        st = lease_workspace(qmha::pt_slice_sync_bytes(B, h), (hipStream_t)stream, &ws);
         if (st != QMHA_OK) return st;
         qmha::Int8Workspace w{};
         w.Ki = Xi;  // the K role: int8 rows
@@ -522,21 +557,13 @@ int qmha_debug_qk_int32(const float* Q, const float* K, int N, int d_model, int 
     int D = 0;
     int st = check_shape(Q, K, Q, S, 1, N, d_model, h, QMHA_FA_TC_INT8_B, &D);
     if (st != QMHA_OK) return st;
-    if (head < 0 || head >= h) {
-        g_last_error = "head out of range";
-        return QMHA_ERR_INVALID;
-    }
-    const size_t need = qmha::int8_workspace_bytes(1, N, h, D, /*with_q=*/true);
-    WsLease lease;
-    st = lease_workspace(need, nullptr, &lease);
-    if (st != QMHA_OK) return st;
-    void* ws = lease.ptr;
-    qmha::Int8Workspace w = qmha::int8_carve(ws, 1, N, h, D, /*with_q=*/true);
-    QMHA_HIP_TRY(qmha::launch_quant_int8(Q, K, Q, w, w.Vh, 1, 1, N, h, D, d_model, nullptr), "quant_int8 launch");
-    QMHA_HIP_TRY(qmha::launch_debug_qk_int32(w, N, D, head, S, nullptr), "debug_qk launch");
-    lease.lk.unlock();
-    QMHA_HIP_TRY(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
-    return QMHA_OK;
+    if (head < 0 || head >= h) return fail(QMHA_ERR_INVALID, "head out of range");
+    return debug_run(qmha::int8_workspace_bytes(1, N, h, D, /*with_q=*/true), [&](void* ws) -> int {
+        const qmha::Int8Workspace w = qmha::int8_carve(ws, 1, N, h, D, /*with_q=*/true);
+        QMHA_HIP_TRY(qmha::launch_quant_int8(Q, K, Q, w, w.Vh, 1, 1, N, h, D, d_model, nullptr), "quant_int8 launch");
+        QMHA_HIP_TRY(qmha::launch_debug_qk_int32(w, N, D, head, S, nullptr), "debug_qk launch");
+        return QMHA_OK;
+    });
 }
 
 int qmha_debug_fa_int8_dump(const float* Q, const float* K, const float* V, float* O, int B, int N, int d_model,
@@ -544,23 +571,17 @@ int qmha_debug_fa_int8_dump(const float* Q, const float* K, const float* V, floa
     int D = 0;
     int st = check_shape(Q, K, V, O, B, N, d_model, h, QMHA_FA_TC_INT8_B, &D);
     if (st != QMHA_OK) return st;
-    if (!S || !Qi || !sQ || ((D == 32 || D == 64 || D == 128) && N < 64)) {
-        g_last_error = "debug dump: needs S/Qi/sQ buffers and, at d = 32 / 64 / 128, N >= 64 (the pipelined kernel)";
-        return QMHA_ERR_INVALID;
-    }
-    const size_t need = qmha::int8_workspace_bytes(B, N, h, D);
-    WsLease lease;
-    st = lease_workspace(need, nullptr, &lease);
-    if (st != QMHA_OK) return st;
-    void* ws = lease.ptr;
-    const qmha::Int8Workspace w = qmha::int8_carve(ws, B, N, h, D);
-    QMHA_HIP_TRY(qmha::launch_quant_int8(Q, K, V, w, w.Vh, /*v_mode=*/1, B, N, h, D, d_model, nullptr, /*first_tensor=*/1),
-                 "quant_int8 launch");
-    QMHA_HIP_TRY(qmha::launch_fa_int8_dump(w, Q, O, B, N, h, D, d_model, qmha::QkDump{S, Qi, sQ}, nullptr),
-                 "fa_int8 dump launch");
-    lease.lk.unlock();
-    QMHA_HIP_TRY(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
-    return QMHA_OK;
+    if (!S || !Qi || !sQ || ((D == 32 || D == 64 || D == 128) && N < 64))
+        return fail(QMHA_ERR_INVALID,
+                    "debug dump: needs S/Qi/sQ buffers and, at d = 32 / 64 / 128, N >= 64 (the pipelined kernel)");
+    return debug_run(qmha::int8_workspace_bytes(B, N, h, D), [&](void* ws) -> int {
+        const qmha::Int8Workspace w = qmha::int8_carve(ws, B, N, h, D);
+        QMHA_HIP_TRY(qmha::launch_quant_int8(Q, K, V, w, w.Vh, /*v_mode=*/1, B, N, h, D, d_model, nullptr, /*first_tensor=*/1),
+                     "quant_int8 launch");
+        QMHA_HIP_TRY(qmha::launch_fa_int8_dump(w, Q, O, B, N, h, D, d_model, qmha::QkDump{S, Qi, sQ}, nullptr),
+                     "fa_int8 dump launch");
+        return QMHA_OK;
+    });
 }
 
 int qmha_debug_fa_int8_pt_dump(const float* Q, const float* K, const float* V, float* O, int B, int N, int d_model,
@@ -568,45 +589,26 @@ int qmha_debug_fa_int8_pt_dump(const float* Q, const float* K, const float* V, f
     int D = 0;
     int st = check_shape(Q, K, V, O, B, N, d_model, h, QMHA_FA_TC_INT8_PT, &D);
     if (st != QMHA_OK) return st;
-    if (!S || !Qi || !sQ) {
-        g_last_error = "debug dump: needs S/Qi/sQ buffers";
-        return QMHA_ERR_INVALID;
-    }
-    const size_t need = qmha::int8_pt_workspace_bytes(B, N, h, D);
-    WsLease lease;
-    st = lease_workspace(need, nullptr, &lease);
-    if (st != QMHA_OK) return st;
-    void* ws = lease.ptr;
-    const qmha::Int8Workspace w = qmha::int8_pt_carve(ws, B, N, h, D);
-    QMHA_HIP_TRY(qmha::launch_quant_int8_pt(Q, K, V, w, B, N, h, D, d_model, nullptr), "quant_int8_pt launch");
-    QMHA_HIP_TRY(qmha::launch_fa_int8_pt_dump(w, Q, O, B, N, h, D, d_model, qmha::QkDump{S, Qi, sQ}, nullptr),
-                 "fa_int8_pt dump launch");
-    lease.lk.unlock();
-    QMHA_HIP_TRY(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
-    return QMHA_OK;
+    if (!S || !Qi || !sQ) return fail(QMHA_ERR_INVALID, "debug dump: needs S/Qi/sQ buffers");
+    return debug_run(qmha::int8_pt_workspace_bytes(B, N, h, D), [&](void* ws) -> int {
+        const qmha::Int8Workspace w = qmha::int8_pt_carve(ws, B, N, h, D);
+        QMHA_HIP_TRY(qmha::launch_quant_int8_pt(Q, K, V, w, B, N, h, D, d_model, nullptr), "quant_int8_pt launch");
+        QMHA_HIP_TRY(qmha::launch_fa_int8_pt_dump(w, Q, O, B, N, h, D, d_model, qmha::QkDump{S, Qi, sQ}, nullptr),
+                     "fa_int8_pt dump launch");
+        return QMHA_OK;
+    });
 }
 
 int qmha_variant_from_name(const char* name) {
     if (!name) return -1;
-    if (!std::strcmp(name, "fa")) return QMHA_FA;
-    if (!std::strcmp(name, "fa_tc_v1a")) return QMHA_FA_TC_V1A;
-    if (!std::strcmp(name, "fa_tc_int8_b")) return QMHA_FA_TC_INT8_B;
-    if (!std::strcmp(name, "unfused")) return QMHA_UNFUSED;
-    if (!std::strcmp(name, "fa_mfma")) return QMHA_FA_MFMA;
-    if (!std::strcmp(name, "fa_tc_int8_pt")) return QMHA_FA_TC_INT8_PT;
+    for (const VariantRow& r : kVariants)
+        if (!std::strcmp(name, r.name)) return r.id;
     return -1;
 }
 
 const char* qmha_variant_name(int v) {
-    switch (v) {
-        case QMHA_FA: return "fa";
-        case QMHA_FA_TC_V1A: return "fa_tc_v1a";
-        case QMHA_FA_TC_INT8_B: return "fa_tc_int8_b";
-        case QMHA_UNFUSED: return "unfused";
-        case QMHA_FA_MFMA: return "fa_mfma";
-        case QMHA_FA_TC_INT8_PT: return "fa_tc_int8_pt";
-        default: return "unknown";
-    }
+    const VariantRow* r = find_variant(v);
+    return r ? r->name : "unknown";
 }
 
 const char* qmha_status_string(int s) {
@@ -628,7 +630,7 @@ int64_t qmha_debug_set_pt_wait(int64_t ticks) { return qmha::set_pt_wait_ticks(t
 
 int qmha_set_overlap_chunks(int n) {
     const int prev = overlap_chunks(1 << 30);
-    g_overlap_chunks.store(n < 1 ? 1 : (n > 16 ? 16 : n));
+    g_overlap_chunks.store(clamp_chunks(n));
     return prev;
 }
 
@@ -670,18 +672,8 @@ int qmha_profile_collect(double* main_ms, long long* launches, double* prepass_m
 }
 
 void qmha_release_workspaces(void) {
-    {
-        std::lock_guard<std::mutex> lk(g_side_mu);
-        for (auto& kv : g_side) {
-            (void)hipStreamSynchronize(kv.second.s);
-            for (hipEvent_t e : kv.second.ready) (void)hipEventDestroy(e);
-            (void)hipEventDestroy(kv.second.start);
-            (void)hipStreamDestroy(kv.second.s);
-        }
-        g_side.clear();
-    }
-    // each slot under its lease: a call still enqueueing on it finishes first; the buffers are freed
-    // after the device has drained (work on any stream may still read them)
+    // each slot under its lease: a call still enqueueing on it finishes first; buffers, side stream and
+    // events go after the device has drained (work on any stream may still use them)
     std::lock_guard<std::mutex> lk(g_ws_mu);
     for (auto& kv : g_ws) {
         WsSlot& s = *kv.second;
@@ -691,6 +683,13 @@ void qmha_release_workspaces(void) {
         if (s.ptr) (void)hipFree(s.ptr);
         s.ptr = nullptr;
         s.bytes = 0;
+        if (s.side) (void)hipStreamSynchronize(s.side);  // a slot of another device than the current one
+        for (hipEvent_t e : s.ready) (void)hipEventDestroy(e);
+        s.ready.clear();
+        if (s.start) (void)hipEventDestroy(s.start);
+        if (s.side) (void)hipStreamDestroy(s.side);
+        s.start = nullptr;
+        s.side = nullptr;
     }
 }
 

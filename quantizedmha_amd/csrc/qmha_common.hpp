@@ -84,6 +84,14 @@ __host__ __device__ constexpr int slot_of_kv_f16(int kv) {
     return 16 * (kv >> 4) + 8 * ((kv >> 2) & 1) + (kv & 3) + 4 * ((kv >> 3) & 1);
 }
 
+// The 16x16-MFMA kernels (fp16 v3, per-tensor int8 v3, fp16 causal) read the K rows of a tile in the key
+// order kap16(kb, m), which leaves each lane group's eight keys per query exactly where the P@V B operand
+// wants them: B element j of lane group g is V^T slot 8 g + j.
+__host__ __device__ constexpr int kap16(int kb, int m) { return 16 * (m >> 3) + 4 * ((m >> 2) & 1) + (m & 3) + 8 * kb; }
+static_assert(kap16(0, 0) == kv_of_slot_f16(0) && kap16(1, 3) == kv_of_slot_f16(7) && kap16(0, 4) == kv_of_slot_f16(8) &&
+                  kap16(1, 7) == kv_of_slot_f16(15) && kap16(0, 8) == kv_of_slot_f16(16) && kap16(1, 15) == kv_of_slot_f16(31),
+              "lane group g's PV slots 8 g + j hold keys kap16(j >> 2, 4 g + (j & 3))");
+
 // LDS layout of a row of RB bytes read as 16-byte chunks by ds_read_b128 with one row per lane
 // (rows 0..31 of a 32 x RB operand).  swz_pos<RB>(row, c) = the LDS chunk slot holding source
 // chunk c of `row`; swz_src<RB>(row, j) = the source chunk stored in slot j.  Power-of-two chunk
@@ -187,6 +195,13 @@ __device__ __forceinline__ float qmha_scale_from_absmax(float absmax) {
 __device__ __forceinline__ int qmha_quant_i8(float v, float inv) {
     int q = __float2int_rn(v * inv);
     return q < -128 ? -128 : (q > 127 ? 127 : q);
+}
+// A NaN in the caller's Q becomes 0 before the quantiser sees it, explicitly (integer test on the
+// bits): the reference's fmaxf drops a NaN from the group absmax and __float2int_rn maps it to 0
+// (the oracle's fp32_to_int8sram restatement).  The main kernels are built with -fno-honor-nans, so a
+// float self-compare would be folded away (round-3 ADVICE).
+__device__ __forceinline__ float nan_to_zero(float x) {
+    return (__float_as_uint(x) & 0x7fffffffu) > 0x7f800000u ? 0.0f : x;
 }
 
 // x / 127 and 1 / x with two fma corrections (Markstein): the correctly rounded quotient

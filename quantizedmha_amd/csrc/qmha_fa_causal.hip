@@ -35,15 +35,8 @@
 
 namespace qmha {
 
-static constexpr float kLog2eC = 1.4426950408889634f;
 static constexpr float kLazySumCapC = 4096.0f;  // the fp16 lazy base's cap
 constexpr int kCausalWaves = 4, kCausalSG = 2;
-
-// the reference quantiser drops a NaN of Q from the absmax and maps it to 0 (see qmha_fa_int8.hip);
-// an integer test, because this file is built with -fno-honor-nans
-__device__ __forceinline__ float causal_nan_to_zero(float x) {
-    return (__float_as_uint(x) & 0x7fffffffu) > 0x7f800000u ? 0.0f : x;
-}
 
 // Launch index -> (bh, q-block pair): a workgroup runs q-block nqb - 1 - pi and then its mirror pi, so every
 // workgroup of a head costs the same nqb + 1 q-block units (the middle q-block of an odd nqb runs alone);
@@ -138,7 +131,7 @@ __global__ __launch_bounds__(kCausalWaves * 64, D > 64 ? 2 : 4) void qmha_fa_int
                 x[s][c4] = *reinterpret_cast<const v4f*>(qrow + 32 * s + 16 * half + 4 * c4);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    x[s][c4][e] = causal_nan_to_zero(x[s][c4][e]);
+                    x[s][c4][e] = nan_to_zero(x[s][c4][e]);
                     amax = fmaxf(amax, fabsf(x[s][c4][e]));
                 }
             }
@@ -313,14 +306,9 @@ __global__ __launch_bounds__(kCausalWaves * 64, D > 64 ? 2 : 4) void qmha_fa_int
 
 // ---------------------------------------------------------------------------------------
 // fp16: 16x16 accumulator map (qmha_fa_f16_v3_kernel).  Lane l = 16 grp + r16 holds, per query block
-// qb, S^T[kap16c(kb, 4 grp + i)][16 qb + r16] (kb = 0, 1, i = 0..3): on the diagonal tile that score
-// is masked when kap16c(kb, 4 grp + i) > 16 qb + r16.
+// qb, S^T[kap16(kb, 4 grp + i)][16 qb + r16] (kb = 0, 1, i = 0..3): on the diagonal tile that score
+// is masked when kap16(kb, 4 grp + i) > 16 qb + r16.
 // ---------------------------------------------------------------------------------------
-__host__ __device__ constexpr int kap16c(int kb, int m) { return 16 * (m >> 3) + 4 * ((m >> 2) & 1) + (m & 3) + 8 * kb; }
-static_assert(kap16c(0, 0) == kv_of_slot_f16(0) && kap16c(1, 3) == kv_of_slot_f16(7) && kap16c(0, 4) == kv_of_slot_f16(8) &&
-                  kap16c(1, 7) == kv_of_slot_f16(15) && kap16c(0, 8) == kv_of_slot_f16(16) && kap16c(1, 15) == kv_of_slot_f16(31),
-              "lane group g's PV slots 8 g + j hold keys kap16c(j >> 2, 4 g + (j & 3))");
-
 template <int D>
 __global__ __launch_bounds__(kCausalWaves * 64, D > 64 ? 2 : 4) void qmha_fa_f16_causal_kernel(
     const float* __restrict__ Qf, const _Float16* __restrict__ Kh, const _Float16* __restrict__ Vt,
@@ -396,7 +384,7 @@ __global__ __launch_bounds__(kCausalWaves * 64, D > 64 ? 2 : 4) void qmha_fa_f16
     auto issue = [&](int buf, int st) {
         stg.issue(lds[buf], kbase, N * RB, vbase, N * D * 2, st, min(SG, qg_last + 1 - st * SG), wave);
     };
-    // S^T blocks [kb][qb] of tile gi: rows kap16c(kb, .) of the K tile against query block qb
+    // S^T blocks [kb][qb] of tile gi: rows kap16(kb, .) of the K tile against query block qb
     struct S4 {
         v4f v[2][2];
     };
@@ -404,7 +392,7 @@ __global__ __launch_bounds__(kCausalWaves * 64, D > 64 ? 2 : 4) void qmha_fa_f16
         S4 s;
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
-            const int krow = gi * 32 + kap16c(kb, r16);
+            const int krow = gi * 32 + kap16(kb, r16);
             s.v[kb][0] = s.v[kb][1] = v4f{};
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
@@ -415,7 +403,7 @@ __global__ __launch_bounds__(kCausalWaves * 64, D > 64 ? 2 : 4) void qmha_fa_f16
         }
         return s;
     };
-    const int key0 = kap16c(0, 4 * grp);  // this lane's keys of the tile: key0 + i + 8 kb
+    const int key0 = kap16(0, 4 * grp);  // this lane's keys of the tile: key0 + i + 8 kb
     // online softmax of one tile (fa_tc_v1a.cu:101-220) and O += P V, the lazy base as
     // qmha_fa_f16_v3_kernel; diag: the diagonal tile
     auto tile = [&](const char* L, int gi, S4 s, bool diag) {
@@ -528,13 +516,11 @@ __global__ __launch_bounds__(kCausalWaves * 64, D > 64 ? 2 : 4) void qmha_fa_f16
 // ---------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------
-bool causal_supported(bool int8, int D) { return int8 ? (D == 32 || D == 64 || D == 128) : (D == 64 || D == 128); }
-
 template <int D>
 static hipError_t fa_int8_causal_launch(const Int8Workspace& w, const float* Qf, float* O, int B, int N, int H, int d_model,
                                         hipStream_t stream) {
     const int G = N / QMHA_GROUP, nqb = (G + kCausalWaves - 1) / kCausalWaves;
-    const float c_log2 = (1.0f / sqrtf((float)D)) * kLog2eC;  // inv_sqrt_d: fa_tc_int8_b.cu:587
+    const float c_log2 = softmax_scale_log2(D);
     hipLaunchKernelGGL((qmha_fa_int8_causal_kernel<D>), dim3(B * H * causal_pairs(nqb)), dim3(kCausalWaves * 64), 0, stream, Qf, w.Ki,
                        w.Vh, w.sK, w.sV, O, N, H, d_model, nqb, c_log2);
     return hipGetLastError();
@@ -554,7 +540,7 @@ template <int D>
 static hipError_t fa_f16_causal_launch(const F16Workspace& w, const float* Qf, float* O, int B, int N, int H, int d_model,
                                        hipStream_t stream) {
     const int G = N / QMHA_GROUP, nqb = (G + kCausalWaves - 1) / kCausalWaves;
-    const float c_log2 = (1.0f / sqrtf((float)D)) * kLog2eC;
+    const float c_log2 = softmax_scale_log2(D);
     hipLaunchKernelGGL((qmha_fa_f16_causal_kernel<D>), dim3(B * H * nqb), dim3(kCausalWaves * 64), 0, stream, Qf, w.Kh,
                        w.Vt, O, N, H, d_model, nqb, c_log2);
     return hipGetLastError();

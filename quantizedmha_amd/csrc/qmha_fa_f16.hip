@@ -18,7 +18,6 @@
 
 namespace qmha {
 
-static constexpr float kLog2eH = 1.4426950408889634f;
 // the lazy base's cap: a row's base moves only when the p of one of its key halves sum above 2^12 on a
 // tile, so every p stays <= 4096, far from the f16 maximum (65504)
 static constexpr float kLazySumCap = 4096.0f;
@@ -271,11 +270,6 @@ __global__ __launch_bounds__(WAVES * 64, (FL & F16_LB4) ? 4 : ((FL & F16_LB1) ? 
 // i = 0..3), and B operand element j of the P@V MFMA is V^T slot 8 g + j, i.e. kv_of_slot_f16(8 g + j)
 // = kap(j >> 2, 4 g + (j & 3)).  Per lane: two queries (r, 16 + r) with eight keys each per tile.
 // ---------------------------------------------------------------------------------------
-__host__ __device__ constexpr int kap16(int kb, int m) { return 16 * (m >> 3) + 4 * ((m >> 2) & 1) + (m & 3) + 8 * kb; }
-static_assert(kap16(0, 0) == kv_of_slot_f16(0) && kap16(1, 3) == kv_of_slot_f16(7) && kap16(0, 4) == kv_of_slot_f16(8) &&
-                  kap16(1, 7) == kv_of_slot_f16(15) && kap16(0, 8) == kv_of_slot_f16(16) && kap16(1, 15) == kv_of_slot_f16(31),
-              "lane group g's PV slots 8 g + j hold keys kap16(j >> 2, 4 g + (j & 3))");
-
 template <int D, int WAVES, int SG>
 __global__ __launch_bounds__(WAVES * 64, D > 64 ? 2 : 4) void qmha_fa_f16_v3_kernel(
     const float* __restrict__ Qf, const _Float16* __restrict__ Kh, const _Float16* __restrict__ Vt,
@@ -479,25 +473,12 @@ __global__ __launch_bounds__(WAVES * 64, D > 64 ? 2 : 4) void qmha_fa_f16_v3_ker
     }
 }
 
-// Kh, Vt (Q is converted in the main kernel)
-size_t f16_workspace_bytes(int B, int N, int H, int D) { return 2 * align_up((size_t)B * H * N * D * 2, 256); }
-
-F16Workspace f16_carve(void* ws, int B, int N, int H, int D) {
-    const size_t e = align_up((size_t)B * H * N * D * 2, 256);
-    char* p = static_cast<char*>(ws);
-    F16Workspace w;
-    w.Qh = nullptr;
-    w.Kh = reinterpret_cast<_Float16*>(p);
-    w.Vt = reinterpret_cast<_Float16*>(p + e);
-    return w;
-}
-
 template <int D, int WAVES, int SG, int FL>
 static hipError_t fa_f16_v2_launch(const F16Workspace& w, const float* Qf, float* O, int B, int N, int H, int d_model,
                                    hipStream_t stream) {
     const int G = N / QMHA_GROUP;
     const int nqb = (G + WAVES - 1) / WAVES;
-    const float c_log2 = (1.0f / sqrtf((float)D)) * kLog2eH;
+    const float c_log2 = softmax_scale_log2(D);
     hipLaunchKernelGGL((qmha_fa_f16_v2_kernel<D, WAVES, SG, FL>), dim3(B * H * nqb), dim3(WAVES * 64), 0, stream, Qf,
                        w.Kh, w.Vt, O, N, H, d_model, nqb, c_log2);
     return hipGetLastError();
@@ -547,7 +528,7 @@ static hipError_t fa_f16_d(const F16Workspace& w, const float* Qf, float* O, int
     if constexpr (D == 64 || D == 128) {
         constexpr int W = D <= 64 ? QMHA_F16_WAVES : 4;
         const int G = N / QMHA_GROUP, nqb = (G + W - 1) / W;
-        const float c_log2 = (1.0f / sqrtf((float)D)) * kLog2eH;
+        const float c_log2 = softmax_scale_log2(D);
         hipLaunchKernelGGL((qmha_fa_f16_v3_kernel<D, W, 2>), dim3(B * H * nqb), dim3(W * 64), 0, stream, Qf, w.Kh, w.Vt, O,
                            N, H, d_model, nqb, c_log2);
         return hipGetLastError();

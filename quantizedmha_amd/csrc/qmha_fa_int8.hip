@@ -41,20 +41,10 @@
 
 namespace qmha {
 
-// log2(e): the softmax runs in base 2 (v_exp_f32), scores pre-multiplied by log2(e).
-static constexpr float kLog2e = 1.4426950408889634f;
 // The per-tensor mode's lazy softmax base: a row's base moves only when the p of one of its
 // key halves sum above 2047/127 on a tile, so every p <= 2047/127 and Pi = rint(127 p) <= 2047 stays below
 // 2048, where the magic-number Pi bits are still the f16 encoding of Pi * 2^-24.
 static constexpr float kPtSumCap = 2047.0f / 127.0f;
-
-// A NaN in the caller's Q becomes 0 before the quantiser sees it, explicitly (integer test on the
-// bits): the reference's fmaxf drops a NaN from the group absmax and __float2int_rn maps it to 0
-// (the oracle's fp32_to_int8sram restatement).  This translation unit is built with
-// -fno-honor-nans, so a float self-compare would be folded away (round-3 ADVICE).
-__device__ __forceinline__ float nan_to_zero(float x) {
-    return (__float_as_uint(x) & 0x7fffffffu) > 0x7f800000u ? 0.0f : x;
-}
 
 // In-kernel Q quantisation (fa_tc_int8_b.cu:33-152, the pre-pass arithmetic) straight into
 // the Q^T MFMA operand: lane (col, half) loads the D/2 values of query row `col` it feeds to
@@ -1008,35 +998,12 @@ __global__ __launch_bounds__(64) void qmha_debug_qk_int32_kernel(const int8_t* _
 // ---------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------
-// Production layout: Ki [B*H][N][D], Vh (f16 V^T operand blocks, 2 bytes per element), sK, sV
-// [B*H][N/32] (the main kernel quantises Q in registers).  with_q adds Qi and sQ at the end for the
-// int32 Q@K^T test hook, whose pre-pass quantises Q too.
-size_t int8_workspace_bytes(int B, int N, int H, int D, bool with_q) {
-    const size_t e = align_up((size_t)B * H * N * D, 256);
-    const size_t s = align_up((size_t)B * H * (N / QMHA_GROUP) * sizeof(float), 256);
-    return e + 2 * e + 2 * s + (with_q ? e + s : 0);
-}
-
-Int8Workspace int8_carve(void* ws, int B, int N, int H, int D, bool with_q) {
-    Int8Workspace w{};
-    const size_t e = align_up((size_t)B * H * N * D, 256);
-    const size_t s = align_up((size_t)B * H * (N / QMHA_GROUP) * sizeof(float), 256);
-    char* p = static_cast<char*>(ws);
-    w.Ki = reinterpret_cast<int8_t*>(p);
-    w.Vh = reinterpret_cast<_Float16*>(p + e);
-    w.sK = reinterpret_cast<float*>(p + 3 * e);
-    w.sV = reinterpret_cast<float*>(p + 3 * e + s);
-    w.Qi = with_q ? reinterpret_cast<int8_t*>(p + 3 * e + 2 * s) : nullptr;
-    w.sQ = with_q ? reinterpret_cast<float*>(p + 4 * e + 2 * s) : nullptr;
-    return w;
-}
-
 template <int D, int FL>
 static hipError_t fa_int8_launch(const Int8Workspace& w, const float* Qf, float* O, int B, int N, int H, int d_model,
                                  hipStream_t stream, QkDump dbg = QkDump{}) {
     const int G = N / QMHA_GROUP;
     const int nqb = (G + 3) / 4;
-    const float c_log2 = (1.0f / sqrtf((float)D)) * kLog2e;  // inv_sqrt_d: fa_tc_int8_b.cu:587
+    const float c_log2 = softmax_scale_log2(D);
     hipLaunchKernelGGL((qmha_fa_int8_kernel<D, FL>), dim3(B * H * nqb), dim3(256), 0, stream, Qf, w.Ki, w.Vh, w.sK, w.sV,
                        O, N, H, d_model, nqb, c_log2, dbg);
     return hipGetLastError();
@@ -1076,7 +1043,7 @@ static hipError_t fa_int8_pipe_launch(const Int8Workspace& w, const float* Qf, f
     const int G = N / QMHA_GROUP;
     if (G < 2) return fa_int8_launch<D, 0>(w, Qf, O, B, N, H, d_model, stream);  // no pipeline to fill
     const int nqb = (G + WAVES - 1) / WAVES;
-    const float c_log2 = (1.0f / sqrtf((float)D)) * kLog2e;
+    const float c_log2 = softmax_scale_log2(D);
     const int rounds = pipe_rounds<D, WAVES, FL>((long long)B * H * nqb);
     const int fair = rounds > 0 && rounds <= kFairMaxRounds;
     hipLaunchKernelGGL((qmha_fa_int8_pipe_kernel<D, WAVES, FL>), dim3(B * H * nqb), dim3(WAVES * 64), 0, stream, Qf,
@@ -1092,7 +1059,6 @@ static hipError_t fa_int8_pipe_launch(const Int8Workspace& w, const float* Qf, f
 // triggered by a lane's key quarter.  Same K rows in the kap16 key order as the fp16 v3 kernel, the V^T
 // slot order unchanged.  No software pipeline: four waves per SIMD interleave instead.
 // ---------------------------------------------------------------------------------------
-__host__ __device__ constexpr int kap16_i8(int kb, int m) { return 16 * (m >> 3) + 4 * ((m >> 2) & 1) + (m & 3) + 8 * kb; }
 
 template <int D, int WAVES, int SG, bool DUMP>
 __global__ __launch_bounds__(WAVES * 64, D > 64 ? 2 : 4) void qmha_fa_int8_pt_v3_kernel(
@@ -1207,13 +1173,13 @@ __global__ __launch_bounds__(WAVES * 64, D > 64 ? 2 : 4) void qmha_fa_int8_pt_v3
         }
     };
     struct S4 {
-        v4i v[2][2];  // [kb][qb]: magic-biased int32 S^T, rows kap16_i8(kb, 4 grp + i), query 16 qb + r16
+        v4i v[2][2];  // [kb][qb]: magic-biased int32 S^T, rows kap16(kb, 4 grp + i), query 16 qb + r16
     };
     auto qk = [&](const char* L, int gi) {
         S4 s;
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
-            const int krow = gi * 32 + kap16_i8(kb, r16);
+            const int krow = gi * 32 + kap16(kb, r16);
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 const v4i kop = *reinterpret_cast<const v4i*>(L + krow * RB + 16 * ((4 * ks + grp) ^ kswz16<RB>(krow)));
@@ -1239,7 +1205,7 @@ __global__ __launch_bounds__(WAVES * 64, D > 64 ? 2 : 4) void qmha_fa_int8_pt_v3
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) sd[kap16_i8(kb, 4 * grp + i)] = s.v[kb][qb][i] - 0x4B400000;
+                    for (int i = 0; i < 4; ++i) sd[kap16(kb, 4 * grp + i)] = s.v[kb][qb][i] - 0x4B400000;
             }
         }
         v8h vop[DB];  // V^T rows 16 m + r16, slots 8 grp .. +7
@@ -1343,34 +1309,12 @@ __global__ __launch_bounds__(WAVES * 64, D > 64 ? 2 : 4) void qmha_fa_int8_pt_v3
 }
 
 // ---- per-tensor mode (fa_tc_int8_pt) -----------------------------------------------------
-size_t int8_pt_workspace_bytes(int B, int N, int H, int D) {
-    const size_t e = align_up((size_t)B * H * N * D, 256);
-    const size_t g = align_up((size_t)6 * B * H * sizeof(uint32_t), 256);  // slice_sync [2][3][B*H]
-    const size_t s = align_up((size_t)B * H * sizeof(float), 256);
-    return e + 2 * e + g + 3 * s;
-}
-
-Int8Workspace int8_pt_carve(void* ws, int B, int N, int H, int D) {
-    const size_t e = align_up((size_t)B * H * N * D, 256);
-    const size_t g = align_up((size_t)6 * B * H * sizeof(uint32_t), 256);  // slice_sync [2][3][B*H]
-    const size_t s = align_up((size_t)B * H * sizeof(float), 256);
-    char* p = static_cast<char*>(ws);
-    Int8Workspace w{};
-    w.Ki = reinterpret_cast<int8_t*>(p);
-    w.Vh = reinterpret_cast<_Float16*>(p + e);
-    w.slice_sync = reinterpret_cast<uint32_t*>(p + 3 * e);
-    w.sQ = reinterpret_cast<float*>(p + 3 * e + g);
-    w.sK = reinterpret_cast<float*>(p + 3 * e + g + s);
-    w.sV = reinterpret_cast<float*>(p + 3 * e + g + 2 * s);
-    return w;
-}
-
 template <int D, int FL, int WAVES = 4>
 static hipError_t fa_int8_pt_launch(const Int8Workspace& w, const float* Qf, float* O, int B, int N, int H, int d_model,
                                     hipStream_t stream, QkDump dbg = QkDump{}) {
     const int G = N / QMHA_GROUP;
     const int nqb = (G + WAVES - 1) / WAVES;
-    const float c_log2 = (1.0f / sqrtf((float)D)) * kLog2e;
+    const float c_log2 = softmax_scale_log2(D);
     const int rounds = pipe_rounds<D, WAVES, FL | FL_PT>((long long)B * H * nqb);
     const int fair = rounds > 0 && rounds <= kFairMaxRounds;
     hipLaunchKernelGGL((qmha_fa_int8_pipe_kernel<D, WAVES, FL | FL_PT>), dim3(B * H * nqb), dim3(WAVES * 64), 0, stream,
@@ -1415,7 +1359,7 @@ static hipError_t fa_int8_pt_v3_launch(const Int8Workspace& w, const float* Qf, 
                                        hipStream_t stream, QkDump dbg = QkDump{}) {
     const int G = N / QMHA_GROUP;
     const int nqb = (G + WAVES - 1) / WAVES;
-    const float c_log2 = (1.0f / sqrtf((float)D)) * kLog2e;
+    const float c_log2 = softmax_scale_log2(D);
     hipLaunchKernelGGL((qmha_fa_int8_pt_v3_kernel<D, WAVES, 2, DUMP>), dim3(B * H * nqb), dim3(WAVES * 64), 0, stream, Qf,
                        w.Ki, w.Vh, w.sQ, w.sK, w.sV, O, N, H, d_model, nqb, c_log2, dbg);
     return hipGetLastError();

@@ -3,12 +3,31 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
 namespace qmha {
 
 inline constexpr size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// log2(e): the fused kernels' softmax runs in base 2 (v_exp_f32), scores pre-multiplied by log2(e).
+inline constexpr float kLog2e = 1.4426950408889634f;
+// the launchers' c_log2 = 1/sqrt(d) * log2(e) (inv_sqrt_d: fa_tc_int8_b.cu:587)
+inline float softmax_scale_log2(int D) { return (1.0f / sqrtf((float)D)) * kLog2e; }
+
+// A workspace layout is stated once, as the order in which its carve takes the arrays: with a null base
+// the same walk only adds up the size, so *_workspace_bytes and *_carve cannot disagree.
+struct Carver {
+    char* base;
+    size_t used = 0;
+    template <class T>
+    T* take(size_t bytes) {  // `bytes` already a multiple of 256
+        T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;
+        used += bytes;
+        return p;
+    }
+};
 
 // Tuning knob for benchmarking kernel geometries: env var "<waves>x<stages>" (e.g. "8x2")
 // read once per variable; returns waves*10+stages, or 0 (= built-in default).
@@ -23,9 +42,30 @@ struct Int8Workspace {
     float* sK;
     float* sV;
     uint32_t* slice_sync;  // per-tensor mode only: [2][3][B*H] slice absmax bits and part arrivals (qmha_pt_quant_kernel)
+    size_t bytes;          // of the whole layout (set by the carves)
 };
-size_t int8_workspace_bytes(int B, int N, int H, int D, bool with_q = false);
-Int8Workspace int8_carve(void* ws, int B, int N, int H, int D, bool with_q = false);
+// Production layout: Ki [B*H][N][D], Vh (f16 V^T operand blocks, 2 bytes per element), sK, sV
+// [B*H][N/32] (the main kernel quantises Q in registers).  with_q adds Qi and sQ at the end for the
+// int32 Q@K^T test hook, whose pre-pass quantises Q too.
+inline Int8Workspace int8_carve(void* ws, int B, int N, int H, int D, bool with_q = false) {
+    const size_t e = align_up((size_t)B * H * N * D, 256);
+    const size_t s = align_up((size_t)B * H * (N / 32) * sizeof(float), 256);  // 32-row quantisation groups
+    Carver c{static_cast<char*>(ws)};
+    Int8Workspace w{};
+    w.Ki = c.take<int8_t>(e);
+    w.Vh = c.take<_Float16>(2 * e);
+    w.sK = c.take<float>(s);
+    w.sV = c.take<float>(s);
+    if (with_q) {
+        w.Qi = c.take<int8_t>(e);
+        w.sQ = c.take<float>(s);
+    }
+    w.bytes = c.used;
+    return w;
+}
+inline size_t int8_workspace_bytes(int B, int N, int H, int D, bool with_q = false) {
+    return int8_carve(nullptr, B, N, H, D, with_q).bytes;
+}
 // v_mode 0: V to `vout` as int8 in the i8 operand order; 1: as f16 integers (main path)
 // first_tensor = 1 skips Q (the main kernels quantise Q themselves); 0 quantises Q, K, V;
 // num_tensors (default: all from first_tensor on) limits the roles launched (the standalone op)
@@ -34,8 +74,22 @@ hipError_t launch_quant_int8(const float* Q, const float* K, const float* V, con
                              int first_tensor = 0, int num_tensors = -1);
 // ---- INT8 per-tensor mode (fa_tc_int8_pt) ----------------------------------------------
 // layout: Ki, Vh as fa_tc_int8_b, then slice_sync [2][3][B*H] uint32, then sQ, sK, sV [B*H] each
-size_t int8_pt_workspace_bytes(int B, int N, int H, int D);
-Int8Workspace int8_pt_carve(void* ws, int B, int N, int H, int D);
+inline size_t pt_slice_sync_bytes(int B, int H) { return align_up((size_t)6 * B * H * sizeof(uint32_t), 256); }
+inline Int8Workspace int8_pt_carve(void* ws, int B, int N, int H, int D) {
+    const size_t e = align_up((size_t)B * H * N * D, 256);
+    const size_t s = align_up((size_t)B * H * sizeof(float), 256);
+    Carver c{static_cast<char*>(ws)};
+    Int8Workspace w{};
+    w.Ki = c.take<int8_t>(e);
+    w.Vh = c.take<_Float16>(2 * e);
+    w.slice_sync = c.take<uint32_t>(pt_slice_sync_bytes(B, H));
+    w.sQ = c.take<float>(s);
+    w.sK = c.take<float>(s);
+    w.sV = c.take<float>(s);
+    w.bytes = c.used;
+    return w;
+}
+inline size_t int8_pt_workspace_bytes(int B, int N, int H, int D) { return int8_pt_carve(nullptr, B, N, H, D).bytes; }
 // one pass: K / V quantised with their head-slice scales from registers, sQ (qmha_pt_quant_kernel)
 // the per-tensor pre-pass's bounded wait in 100 MHz ticks (default 200000 = 2 ms; 0 forces the
 // fallback); returns the previous value
@@ -64,13 +118,21 @@ hipError_t launch_fa_int8_pt_dump(const Int8Workspace& w, const float* Qf, float
                                   int d_model, QkDump dbg, hipStream_t stream);
 
 // ---- FP16 (fa_tc_v1a) ------------------------------------------------------------------
-struct F16Workspace {
-    _Float16* Qh;  // unused (nullptr): the main kernel converts Q in registers
+struct F16Workspace {  // no Q: the main kernel converts Q in registers
     _Float16* Kh;  // [B*H][N][D]
     _Float16* Vt;  // [B*H][N/32][D][32]  (f16 operand slot order)
+    size_t bytes;  // of the whole layout (set by the carve)
 };
-size_t f16_workspace_bytes(int B, int N, int H, int D);
-F16Workspace f16_carve(void* ws, int B, int N, int H, int D);
+inline F16Workspace f16_carve(void* ws, int B, int N, int H, int D) {
+    const size_t e = align_up((size_t)B * H * N * D * 2, 256);
+    Carver c{static_cast<char*>(ws)};
+    F16Workspace w{};
+    w.Kh = c.take<_Float16>(e);
+    w.Vt = c.take<_Float16>(e);
+    w.bytes = c.used;
+    return w;
+}
+inline size_t f16_workspace_bytes(int B, int N, int H, int D) { return f16_carve(nullptr, B, N, H, D).bytes; }
 hipError_t launch_convert_f16(const float* Q, const float* K, const float* V, const F16Workspace& w, int B, int N,
                               int H, int D, int d_model, hipStream_t stream);
 hipError_t launch_fa_f16_main(const F16Workspace& w, const float* Qf, float* O, int B, int N, int H, int D, int d_model,
@@ -78,8 +140,8 @@ hipError_t launch_fa_f16_main(const F16Workspace& w, const float* Qf, float* O, 
 
 // ---- causal main kernels (qmha_fa_causal.hip) ---------------------------------
 // the same workspaces as the non-causal paths (the pre-pass is unchanged); query row r attends keys
-// j <= r.  int8: d in {32, 64, 128}; fp16: d in {64, 128} (causal_supported); other d: hipErrorInvalidValue
-bool causal_supported(bool int8, int D);
+// j <= r.  int8: d in {32, 64, 128}; fp16: d in {64, 128} (qmha_api.cpp's variant table); other d:
+// hipErrorInvalidValue
 hipError_t launch_fa_int8_causal_main(const Int8Workspace& w, const float* Qf, float* O, int B, int N, int H, int D,
                                       int d_model, hipStream_t stream);
 hipError_t launch_fa_f16_causal_main(const F16Workspace& w, const float* Qf, float* O, int B, int N, int H, int D,

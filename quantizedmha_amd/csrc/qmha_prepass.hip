@@ -595,7 +595,7 @@ static hipError_t convert_f16_d(const float* Q, const float* K, const float* V, 
                                 int H, int d_model, hipStream_t stream) {
     const int total = B * H * (N / QMHA_GROUP);
     // K and V only: the main kernel converts Q itself (blockIdx.y = tensor - 1)
-    hipLaunchKernelGGL((qmha_convert_f16_kernel<D>), dim3((total + 3) / 4, 2), dim3(256), 0, stream, Q, K, V, w.Qh,
+    hipLaunchKernelGGL((qmha_convert_f16_kernel<D>), dim3((total + 3) / 4, 2), dim3(256), 0, stream, Q, K, V, (_Float16*)nullptr,
                        w.Kh, w.Vt, N, H, d_model, total, 1);
     return hipGetLastError();
 }
@@ -607,7 +607,7 @@ hipError_t launch_convert_f16(const float* Q, const float* K, const float* V, co
         case 64: return convert_f16_d<64>(Q, K, V, w, B, N, H, d_model, stream);
         case 128: return convert_f16_d<128>(Q, K, V, w, B, N, H, d_model, stream);
 #define QMHA_CASE(d) \
-    case d: return prepass_any_d<d, 1, false>(Q, K, V, w.Qh, w.Kh, w.Vt, nullptr, nullptr, nullptr, B, N, H, d_model, 1, -1, stream);
+    case d: return prepass_any_d<d, 1, false>(Q, K, V, (_Float16*)nullptr, w.Kh, w.Vt, nullptr, nullptr, nullptr, B, N, H, d_model, 1, -1, stream);
         QMHA_CASE(96) QMHA_CASE(160) QMHA_CASE(192) QMHA_CASE(224) QMHA_CASE(256)
 #undef QMHA_CASE
         default: return hipErrorInvalidValue;

@@ -74,6 +74,23 @@ def test_host_side_queries(built):
     assert lib.qmha_status_string(1).decode() == "invalid argument"
 
 
+# qmha_workspace_size of variants 0..5 as the library computed it before the layouts were stated once
+# (qmha_kernels.hpp, *_carve): the sizes and therefore every array offset are unchanged
+WORKSPACE_SIZES = {
+    (1, 32, 32, 1): [0, 4096, 3584, 4096, 0, 4096],
+    (2, 96, 128, 2): [0, 98304, 74240, 147456, 0, 74752],
+    (3, 1024, 256, 4): [0, 3145728, 2362368, 50331648, 0, 2360576],
+    (16, 4096, 1024, 16): [0, 268435456, 201588736, 2147483648, 0, 201335808],
+}
+
+
+@pytest.mark.parametrize("shape", sorted(WORKSPACE_SIZES))
+def test_workspace_sizes_unchanged(built, shape):
+    from quantizedmha_amd import _lib
+    lib = _lib.load()
+    assert [lib.qmha_workspace_size(*shape, v) for v in range(len(VARIANTS))] == WORKSPACE_SIZES[shape]
+
+
 @pytest.mark.parametrize("args,err", [
     ((1, 100, 128, 2, 2), "N must be a multiple of 32"),
     ((1, 128, 130, 2, 2), "head size"),

@@ -150,3 +150,206 @@ def test_scratch_contents_never_matter(dev, variant, B, N, d):
     for i in (2, 0, 1, 2):
         assert torch.equal(call(i, ws), refs[i]), f"back-to-back, set {i}"
     assert not torch.equal(refs[0], refs[1])
+
+
+# ---- one leased slot per (device, stream): every solve entry, the overlap side stream, release ----------
+H2, D2 = 2, 64
+CAUSAL_VARIANTS = ("fa_tc_int8_b", "fa_tc_v1a")  # the chunked variants; fa_tc_int8_pt is the unchunked branch
+
+
+def _hip_stream_per_thread():
+    """The hipStreamPerThread handle as the installed ROCm's hip_runtime_api.h defines it."""
+    import re
+    header = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include", "hip", "hip_runtime_api.h")
+    m = re.search(r"#define\s+hipStreamPerThread\s+\(\(hipStream_t\)\s*(\w+)\)", open(header).read())
+    assert m, header
+    return int(m.group(1), 0)
+
+
+def _make_calls(dev, plan):
+    """plan: {key: (entry, variant, B, N)} -> {key: (entry, variant, B, N, Q, K, V, O)}, O filled with NaN."""
+    calls = {}
+    for i, (key, (entry, variant, B, N)) in enumerate(sorted(plan.items())):
+        g = torch.Generator(device=dev).manual_seed(7000 + i)
+        Q, K, V = (torch.randn(B, N, H2 * D2, device=dev, generator=g) * (0.4 + 0.03 * i) for _ in range(3))
+        calls[key] = (entry, variant, B, N, Q, K, V, torch.full_like(Q, float("nan")))
+    return calls
+
+
+def _enqueue(lib, call, O, stream, ws=None):
+    """One call through its entry point: "ex" qmha_solve_ex, "ws" qmha_solve_ws on the caller workspace `ws`,
+    "causal" qmha_solve_opts with QMHA_FLAG_CAUSAL and a null workspace."""
+    from quantizedmha_amd import _lib
+    entry, variant, B, N, Q, K, V, _ = call
+    args = (Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), B, N, H2 * D2, H2, _lib.variant_id(variant))
+    if entry == "ex":
+        st = lib.qmha_solve_ex(*args, stream)
+    elif entry == "ws":
+        st = lib.qmha_solve_ws(*args, ws.data_ptr(), ws.numel(), stream)
+    else:
+        st = lib.qmha_solve_opts(*args, _lib.QMHA_FLAG_CAUSAL, None, 0, stream)
+    _lib.check(st, f"{entry} {variant} B{B} N{N}")
+
+
+def _ws_bytes(lib, call):
+    from quantizedmha_amd import _lib
+    _, variant, B, N = call[:4]
+    return lib.qmha_workspace_size(B, N, H2 * D2, H2, _lib.variant_id(variant))
+
+
+def _references(dev, lib, calls, stream_of):
+    """The same calls made one at a time with overlap chunks = 1."""
+    ws = torch.empty(max(max(_ws_bytes(lib, c) for c in calls.values()), 256), dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)  # the inputs were made on the default stream
+    prev = lib.qmha_set_overlap_chunks(1)
+    try:
+        refs = {}
+        for key, call in calls.items():
+            refs[key] = torch.full_like(call[4], float("nan"))
+            _enqueue(lib, call, refs[key], stream_of(key), ws)
+            torch.cuda.synchronize(dev)
+    finally:
+        lib.qmha_set_overlap_chunks(prev)
+    return refs
+
+
+def _run_threads(dev, workers):
+    """Start every worker(errors) at once, join with a timeout; returns the errors the workers reported."""
+    errors = []
+    start = threading.Barrier(len(workers))
+
+    def body(i, fn):
+        try:
+            torch.cuda.set_device(dev)
+            start.wait()
+            fn()
+        except Exception as e:  # reported below; the other threads go on
+            errors.append(f"thread {i}: {e!r}")
+
+    threads = [threading.Thread(target=body, args=(i, fn)) for i, fn in enumerate(workers)]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join(timeout=60)
+    assert not any(th.is_alive() for th in threads), "a thread hung"
+    return errors
+
+
+def _assert_bit_identical(calls, refs):
+    bad = []
+    for key, (entry, variant, B, N, Q, K, V, O) in calls.items():
+        assert torch.isfinite(refs[key]).all(), key
+        if not torch.equal(O, refs[key]):
+            d = (O - refs[key]).abs().nan_to_num(1e30).max().item()
+            bad.append(f"{key} {entry} {variant} B{B} N{N}: max|diff| {d:.3g}")
+    assert not bad, f"{len(bad)} of {len(calls)} calls differ from their single-threaded result: " + "; ".join(bad[:8])
+
+
+def test_concurrent_callers_with_overlap_chunks(dev):
+    """4 threads x 9 calls on one shared stream with overlap chunks = 2 (the slot's side stream in use), through
+    qmha_solve_ex, qmha_solve_ws (one caller workspace per thread: it leases the slot too) and causal
+    qmha_solve_opts; B = 3 is the uneven 1 + 2 chunk split, N = 96 ends on a partial stage."""
+    from quantizedmha_amd import _lib
+    lib = _lib.load()
+    nthreads, ncalls = 4, 9
+    plan = {}
+    for t in range(nthreads):
+        for j in range(ncalls):
+            entry = ("ex", "ws", "causal")[(j + t) % 3]  # each entry once per block of three calls ...
+            pool = CAUSAL_VARIANTS if entry == "causal" else VARIANTS
+            variant = pool[(j // 3 + t) % len(pool)]  # ... with another variant in every block
+            plan[t, j] = (entry, variant, 2 + (j + j // 3) % 2, (96, 128, 256)[(j + t + j // 3) % 3])
+    seen = set(plan.values())
+    assert {(e, v) for e, v, _, _ in seen} == {(e, v) for e in ("ex", "ws") for v in VARIANTS} | \
+        {("causal", v) for v in CAUSAL_VARIANTS}
+    assert {b for _, _, b, _ in seen} == {2, 3} and {n for _, _, _, n in seen} == {96, 128, 256}
+    calls = _make_calls(dev, plan)
+    shared = torch.cuda.Stream(dev)
+    sptr = shared.cuda_stream
+    refs = _references(dev, lib, calls, lambda key: sptr)
+    wss = [torch.empty(max(_ws_bytes(lib, c) for (t2, _), c in calls.items() if t2 == t and c[0] == "ws"),
+                       dtype=torch.uint8, device=dev) for t in range(nthreads)]
+    torch.cuda.synchronize(dev)  # inputs, references and workspaces exist before the threads start
+
+    def worker(t):
+        def fn():
+            for j in range(ncalls):
+                _enqueue(lib, calls[t, j], calls[t, j][7], sptr, wss[t])
+        return fn
+
+    prev = lib.qmha_set_overlap_chunks(2)
+    try:
+        errors = _run_threads(dev, [worker(t) for t in range(nthreads)])
+        shared.synchronize()
+        torch.cuda.synchronize(dev)
+    finally:
+        lib.qmha_set_overlap_chunks(prev)
+    assert not errors, errors
+    _assert_bit_identical(calls, refs)
+
+
+def test_release_beside_callers_with_overlap_chunks(dev):
+    """qmha_release_workspaces is safe beside running callers, overlap chunks > 1 included
+    (the side stream and its events live in the leased slot).  3 threads x 10 qmha_solve_ex calls, two on a
+    shared stream and one on its own, while a fourth thread releases five times about 20 ms apart: no call
+    fails and every output is bit-identical to its single-threaded, chunks = 1 result."""
+    import time
+    from quantizedmha_amd import _lib
+    lib = _lib.load()
+    ncallers, ncalls = 3, 10
+    plan = {(t, j): ("ex", CAUSAL_VARIANTS[(j + t) % 2], 2, (96, 256)[(j // 2 + t) % 2])
+            for t in range(ncallers) for j in range(ncalls)}
+    calls = _make_calls(dev, plan)
+    streams = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]
+    sptr = lambda key: streams[key[0] // 2].cuda_stream  # noqa: E731  threads 0, 1 share; thread 2 has its own
+    refs = _references(dev, lib, calls, sptr)
+    torch.cuda.synchronize(dev)
+
+    def caller(t):
+        def fn():
+            for j in range(ncalls):
+                _enqueue(lib, calls[t, j], calls[t, j][7], sptr((t, j)))
+        return fn
+
+    def releaser():
+        for _ in range(5):
+            lib.qmha_release_workspaces()
+            time.sleep(0.02)
+
+    prev = lib.qmha_set_overlap_chunks(2)
+    try:
+        errors = _run_threads(dev, [caller(t) for t in range(ncallers)] + [releaser])
+        torch.cuda.synchronize(dev)
+    finally:
+        lib.qmha_set_overlap_chunks(prev)
+    assert not errors, errors
+    _assert_bit_identical(calls, refs)
+
+
+def test_stream_per_thread_slots(dev):
+    """hipStreamPerThread names another stream in every thread, so every thread has a slot of its own (scratch
+    and side stream): 3 threads x 6 qmha_solve_ex calls on that handle with sizes growing 96 -> 256 -> 512
+    within each thread (each slot grows), overlap chunks = 2."""
+    from quantizedmha_amd import _lib
+    lib = _lib.load()
+    per_thread = _hip_stream_per_thread()
+    nthreads, ncalls = 3, 6
+    plan = {(t, j): ("ex", VARIANTS[(j + t) % 3], 2, (96, 256, 512)[j // 2]) for t in range(nthreads) for j in range(ncalls)}
+    calls = _make_calls(dev, plan)
+    refs = _references(dev, lib, calls, lambda key: per_thread)
+    torch.cuda.synchronize(dev)
+
+    def worker(t):
+        def fn():
+            for j in range(ncalls):
+                _enqueue(lib, calls[t, j], calls[t, j][7], per_thread)
+        return fn
+
+    prev = lib.qmha_set_overlap_chunks(2)
+    try:
+        errors = _run_threads(dev, [worker(t) for t in range(nthreads)])
+        torch.cuda.synchronize(dev)  # device-wide: the per-thread streams are not reachable from here
+    finally:
+        lib.qmha_set_overlap_chunks(prev)
+    assert not errors, errors
+    _assert_bit_identical(calls, refs)

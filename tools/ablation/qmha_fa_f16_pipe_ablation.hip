@@ -326,7 +326,7 @@ __global__ __launch_bounds__(WAVES * 64, QMHA_F16_PIPE_LB) void qmha_fa_f16_pipe
         if (G >= 2) {
             constexpr int WV = QMHA_F16_PIPE;  // waves per workgroup
             const int nqb = (G + WV - 1) / WV;
-            const float c_log2 = (1.0f / sqrtf((float)D)) * kLog2eH;
+            const float c_log2 = (1.0f / sqrtf((float)D)) * kLog2e;
             hipLaunchKernelGGL((qmha_fa_f16_pipe_kernel<D, WV>), dim3(B * H * nqb), dim3(WV * 64), 0, stream, Qf, w.Kh,
                                w.Vt, O, N, H, d_model, nqb, c_log2);
             return hipGetLastError();

@@ -85,6 +85,7 @@ def main():
             mains = [x["main_ms"] for x in rr]
             calls = [x["call_ms"] for x in rr]
             summ[n] = {"main_ms_rounds": [round(x, 4) for x in mains], "call_ms_rounds": [round(x, 4) for x in calls],
+                       "pre_ms_rounds": [round(x["pre_ms"], 4) for x in rr],
                        "main_ms_mean": round(sum(mains) / len(mains), 4), "call_ms_mean": round(sum(calls) / len(calls), 4),
                        "pre_ms_mean": round(sum(x["pre_ms"] for x in rr) / len(rr), 4),
                        "tflops_main": round(flops / (sum(mains) / len(mains) * 1e-3) / 1e12, 1)}

@@ -85,7 +85,8 @@ int qmha_solve_ws(const float *Q, const float *K, const float *V, float *O, int 
 
 /* Option flags of qmha_solve_opts. */
 enum {
-    QMHA_FLAG_CAUSAL = 1 /* query row r attends keys j <= r of its own sequence (Nq = Nk = N) */
+    QMHA_FLAG_CAUSAL = 1 /* query row r attends keys j <= r of its own sequence (Nq = Nk = N);
+                            Nq != Nk: qmha_solve_rect, bottom-right aligned, j <= r + (Nk - Nq) */
 };
 
 /*
@@ -100,6 +101,24 @@ enum {
  */
 int qmha_solve_opts(const float *Q, const float *K, const float *V, float *O, int B, int N, int d_model, int h,
                     int variant, unsigned flags, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * qmha_solve_rect -- qmha_solve_opts with separate query and key lengths: cross-attention and chunked
+ * prefill.  Q and O are [B, Nq, d_model], K and V are [B, Nk, d_model] (fp32, contiguous, batch outermost).
+ * Stream, status, leased-slot and caller-workspace rules are qmha_solve_opts': workspace == NULL uses the
+ * library's slot; otherwise the caller supplies >= qmha_workspace_size(B, Nk, d_model, h, variant) bytes (the
+ * scratch depends on the key length only) and the call makes no allocation and no synchronisation.
+ * flags == 0: every query row attends all Nk keys (any Nq, Nk, also Nq > Nk).  QMHA_FLAG_CAUSAL: bottom-right
+ * aligned, query row r attends keys j <= r + (Nk - Nq) -- the Nq queries are the last Nq positions of a
+ * sequence of Nk; needs Nk >= Nq (QMHA_ERR_INVALID otherwise).  Nq % 32 == 0 and Nk % 32 == 0; the other
+ * preconditions are qmha_solve_ex's, per tensor.  Unknown flag bits: QMHA_ERR_INVALID.
+ * Nq == Nk enqueues exactly what qmha_solve_opts enqueues, for every variant.  Nq != Nk is built for
+ * fa_tc_int8_b at d = 32, 64, 128 and fa_tc_v1a at d = 64, 128, with or without QMHA_FLAG_CAUSAL; every other
+ * variant or head size returns QMHA_ERR_NOSYS (qmha_last_error names the variant and d) before anything is
+ * launched, leaving O untouched.  Every call runs the K/V pre-pass over all Nk rows.
+ */
+int qmha_solve_rect(const float *Q, const float *K, const float *V, float *O, int B, int Nq, int Nk, int d_model,
+                    int h, int variant, unsigned flags, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Blocking convenience used by the per-variant `solve` shims and the JAX raw-pointer
  * binding (extensions/jax/jax_ext.cpp:12-28): batch 1, synchronises the device stream. */

@@ -23,6 +23,7 @@ SIGNATURES = {
     "solve": (None, [_vp, _vp, _vp, _vp, _i, _i, _i]),
     "qmha_solve_ex": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "qmha_solve_opts": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_uint, _vp, _sz, _vp]),
+    "qmha_solve_rect": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, ctypes.c_uint, _vp, _sz, _vp]),
     "qmha_workspace_size": (_sz, [_i, _i, _i, _i, _i]),
     "qmha_solve_ws": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "qmha_solve_variant": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i]),

@@ -51,15 +51,16 @@ struct VariantRow {
     const char* name;
     size_t (*ws_bytes)(int B, int N, int H, int D);  // nullptr: no scratch
     unsigned plain, causal;                          // built head sizes without / with QMHA_FLAG_CAUSAL
+    unsigned rect;                                   // built head sizes of qmha_solve_rect with Nq != Nk
 };
 constexpr VariantRow kVariants[] = {
-    {QMHA_FA, "fa", nullptr, kEveryD, 0},
-    {QMHA_FA_TC_V1A, "fa_tc_v1a", qmha::f16_workspace_bytes, kEveryD, d_mask(64, 128)},
+    {QMHA_FA, "fa", nullptr, kEveryD, 0, 0},
+    {QMHA_FA_TC_V1A, "fa_tc_v1a", qmha::f16_workspace_bytes, kEveryD, d_mask(64, 128), d_mask(64, 128)},
     {QMHA_FA_TC_INT8_B, "fa_tc_int8_b", [](int B, int N, int H, int D) { return qmha::int8_workspace_bytes(B, N, H, D); },
-     kEveryD, kTunedD},
-    {QMHA_UNFUSED, "unfused", qmha::unfused_workspace_bytes, kEveryD, 0},
-    {QMHA_FA_MFMA, "fa_mfma", nullptr, kEveryD, 0},
-    {QMHA_FA_TC_INT8_PT, "fa_tc_int8_pt", qmha::int8_pt_workspace_bytes, kTunedD, 0},  // no reference counterpart
+     kEveryD, kTunedD, kTunedD},
+    {QMHA_UNFUSED, "unfused", qmha::unfused_workspace_bytes, kEveryD, 0, 0},
+    {QMHA_FA_MFMA, "fa_mfma", nullptr, kEveryD, 0, 0},
+    {QMHA_FA_TC_INT8_PT, "fa_tc_int8_pt", qmha::int8_pt_workspace_bytes, kTunedD, 0, 0},  // no reference counterpart
 };
 
 const VariantRow* find_variant(int id) {
@@ -82,13 +83,15 @@ size_t workspace_bytes(int B, int N, int H, int D, int variant) {
     return v && v->ws_bytes ? v->ws_bytes(B, N, H, D) : 0;
 }
 
+// n_name: what the caller's row count is called in the messages (qmha_solve_rect checks Nq and Nk in turn)
 int check_shape(const void* Q, const void* K, const void* V, const void* O, int B, int N, int d_model, int h,
-                int variant, int* D_out) {
+                int variant, int* D_out, const char* n_name = "N") {
     if (!Q || !K || !V || !O) return fail(QMHA_ERR_INVALID, "null tensor pointer");
-    if (B < 1 || N < 1 || d_model < 1 || h < 1) return fail(QMHA_ERR_INVALID, "B, N, d_model and h must be positive");
+    if (B < 1 || N < 1 || d_model < 1 || h < 1)
+        return fail(QMHA_ERR_INVALID, std::string("B, ") + n_name + ", d_model and h must be positive");
     if (d_model % h != 0) return fail(QMHA_ERR_INVALID, "d_model must be divisible by h");  // config.h:27
     // fa_tc_int8_b.cu:422-423 (N % Br), Br = Bc = 32
-    if (N % 32 != 0) return fail(QMHA_ERR_INVALID, "N must be a multiple of 32");
+    if (N % 32 != 0) return fail(QMHA_ERR_INVALID, std::string(n_name) + " must be a multiple of 32");
     const int D = d_model / h;
     const VariantRow* v = find_variant(variant);
     if (!v) return fail(QMHA_ERR_INVALID, "unknown variant");
@@ -105,9 +108,12 @@ int check_shape(const void* Q, const void* K, const void* V, const void* O, int 
 
 // qmha_solve_opts' flags, checked before any launch: unknown bits are invalid; QMHA_FLAG_CAUSAL is built
 // for the variants and head sizes of the table's `causal` column
-int check_flags(int variant, int D, unsigned flags) {
+int check_flag_bits(unsigned flags) {
     const unsigned unknown = flags & ~(unsigned)QMHA_FLAG_CAUSAL;
-    if (unknown) return fail(QMHA_ERR_INVALID, "unknown flag bits " + std::to_string(unknown));
+    return unknown ? fail(QMHA_ERR_INVALID, "unknown flag bits " + std::to_string(unknown)) : QMHA_OK;
+}
+int check_flags(int variant, int D, unsigned flags) {
+    if (int st = check_flag_bits(flags)) return st;
     if ((flags & QMHA_FLAG_CAUSAL) && !built(find_variant(variant)->causal, D)) {
         std::string have;
         for (const VariantRow& r : kVariants)
@@ -346,10 +352,14 @@ qmha::F16Workspace f16_slice(qmha::F16Workspace w, size_t b0, int N, int H, int 
 }
 
 // Enqueue one checked call on `stream`; `ws` holds workspace_bytes(...) bytes and `slot` is leased by the caller.
-int run(const float* Q, const float* K, const float* V, float* O, int B, int N, int d_model, int h, int variant,
+// Q and O have Nq rows, K and V have N; the pre-passes and the workspaces see K and V only, so they follow N.
+// Nq != N (qmha_solve_rect, checked against the table's `rect` column: int8 / fp16 only) takes the rectangular
+// main kernels; Nq == N enqueues the square paths.
+int run(const float* Q, const float* K, const float* V, float* O, int B, int Nq, int N, int d_model, int h, int variant,
         unsigned flags, void* ws, WsSlot& slot, hipStream_t stream) {
     const int D = d_model / h;
     const bool causal = flags & QMHA_FLAG_CAUSAL;  // check_flags passed: int8 / fp16 at a built head size
+    const bool rect = Nq != N;
     bool prof;
     {
         std::lock_guard<std::mutex> lk(g_prof_mu);
@@ -357,7 +367,7 @@ int run(const float* Q, const float* K, const float* V, float* O, int B, int N, 
     }
     ProfRec rec;
     Marks *pre_m = prof ? &rec.pre : nullptr, *main_m = prof ? &rec.main : nullptr;
-    const size_t slab = (size_t)N * d_model;  // floats per sequence
+    const size_t slab = (size_t)N * d_model, qslab = (size_t)Nq * d_model;  // floats per sequence: K and V, Q and O
     int st;
     switch (variant) {
         case QMHA_FA_TC_INT8_B: {
@@ -367,13 +377,16 @@ int run(const float* Q, const float* K, const float* V, float* O, int B, int N, 
                 B, stream, slot, pre_m, main_m, "quant_int8 launch",
                 [&](Chunk c, hipStream_t s) {
                     const qmha::Int8Workspace w = int8_slice(w8, c.b0, N, h, D);
-                    return qmha::launch_quant_int8(Q + c.b0 * slab, K + c.b0 * slab, V + c.b0 * slab, w, w.Vh, /*v_mode=*/1,
+                    return qmha::launch_quant_int8(Q + c.b0 * qslab, K + c.b0 * slab, V + c.b0 * slab, w, w.Vh, /*v_mode=*/1,
                                                    c.nb, N, h, D, d_model, s, /*first_tensor=*/1);
                 },
-                causal ? "fa_int8 causal launch" : "fa_int8 launch",
+                rect ? "fa_int8 rect launch" : causal ? "fa_int8 causal launch" : "fa_int8 launch",
                 [&](Chunk c) {
-                    return launch_main(int8_slice(w8, c.b0, N, h, D), Q + c.b0 * slab, O + c.b0 * slab, c.nb, N, h, D, d_model,
-                                       stream);
+                    const qmha::Int8Workspace w = int8_slice(w8, c.b0, N, h, D);
+                    const float* q = Q + c.b0 * qslab;
+                    float* o = O + c.b0 * qslab;
+                    return rect ? qmha::launch_fa_int8_rect_main(w, q, o, c.nb, Nq, N, h, D, d_model, causal, stream)
+                                : launch_main(w, q, o, c.nb, N, h, D, d_model, stream);
                 });
             break;
         }
@@ -383,13 +396,16 @@ int run(const float* Q, const float* K, const float* V, float* O, int B, int N, 
             st = run_chunked(
                 B, stream, slot, pre_m, main_m, "convert_f16 launch",
                 [&](Chunk c, hipStream_t s) {
-                    return qmha::launch_convert_f16(Q + c.b0 * slab, K + c.b0 * slab, V + c.b0 * slab,
+                    return qmha::launch_convert_f16(Q + c.b0 * qslab, K + c.b0 * slab, V + c.b0 * slab,
                                                     f16_slice(w16, c.b0, N, h, D), c.nb, N, h, D, d_model, s);
                 },
-                causal ? "fa_f16 causal launch" : "fa_f16 launch",
+                rect ? "fa_f16 rect launch" : causal ? "fa_f16 causal launch" : "fa_f16 launch",
                 [&](Chunk c) {
-                    return launch_main(f16_slice(w16, c.b0, N, h, D), Q + c.b0 * slab, O + c.b0 * slab, c.nb, N, h, D, d_model,
-                                       stream);
+                    const qmha::F16Workspace w = f16_slice(w16, c.b0, N, h, D);
+                    const float* q = Q + c.b0 * qslab;
+                    float* o = O + c.b0 * qslab;
+                    return rect ? qmha::launch_fa_f16_rect_main(w, q, o, c.nb, Nq, N, h, D, d_model, causal, stream)
+                                : launch_main(w, q, o, c.nb, N, h, D, d_model, stream);
                 });
             break;
         }
@@ -439,7 +455,37 @@ int solve_on(const float* Q, const float* K, const float* V, float* O, int B, in
     WsLease lease;
     st = lease_workspace(caller_owned ? 0 : need, stream, &lease);
     if (st != QMHA_OK) return st;
-    return run(Q, K, V, O, B, N, d_model, h, variant, flags, caller_owned ? caller_ws : lease.ptr, *lease.slot, stream);
+    return run(Q, K, V, O, B, N, N, d_model, h, variant, flags, caller_owned ? caller_ws : lease.ptr, *lease.slot, stream);
+}
+
+// qmha_solve_rect: Q / O of Nq rows, K / V of Nk.  Every check runs before any HIP call.  Nq == Nk is solve_on
+// itself (the square paths, every variant); Nq != Nk is built for the table's `rect` column.  The scratch is
+// that of the keys: workspace_bytes(B, Nk, ...).
+int solve_rect_on(const float* Q, const float* K, const float* V, float* O, int B, int Nq, int Nk, int d_model, int h,
+                  int variant, unsigned flags, bool caller_owned, void* caller_ws, size_t caller_bytes, hipStream_t stream) {
+    int D = 0;
+    int st = check_shape(Q, K, V, O, B, Nq, d_model, h, variant, &D, "Nq");  // Q and O
+    if (st == QMHA_OK) st = check_shape(Q, K, V, O, B, Nk, d_model, h, variant, &D, "Nk");  // K and V
+    if (st == QMHA_OK) st = check_flag_bits(flags);
+    if (st != QMHA_OK) return st;
+    if ((flags & QMHA_FLAG_CAUSAL) && Nq > Nk)
+        return fail(QMHA_ERR_INVALID, "causal attention is bottom-right aligned and needs Nk >= Nq (Nq = " + std::to_string(Nq) +
+                                          ", Nk = " + std::to_string(Nk) + ")");
+    if (Nq == Nk)
+        return solve_on(Q, K, V, O, B, Nk, d_model, h, variant, flags, caller_owned, caller_ws, caller_bytes, stream);
+    if (!built(find_variant(variant)->rect, D)) {
+        std::string have;
+        for (const VariantRow& r : kVariants)
+            if (r.rect) have += (have.empty() ? "" : "; ") + std::string(r.name) + ": d = " + d_list(r.rect);
+        return fail(QMHA_ERR_NOSYS, std::string("rectangular attention (Nq != Nk) is not built for variant ") +
+                                        qmha_variant_name(variant) + " at d = " + std::to_string(D) + " (" + have + ")");
+    }
+    const size_t need = workspace_bytes(B, Nk, h, D, variant);
+    if (caller_owned && caller_bytes < need) return fail(QMHA_ERR_INVALID, "workspace too small");
+    WsLease lease;
+    st = lease_workspace(caller_owned ? 0 : need, stream, &lease);
+    if (st != QMHA_OK) return st;
+    return run(Q, K, V, O, B, Nq, Nk, d_model, h, variant, flags, caller_owned ? caller_ws : lease.ptr, *lease.slot, stream);
 }
 
 // The debug hooks' skeleton: `need` bytes of the null stream's slot, body(ws) enqueues the pre-pass and the
@@ -495,6 +541,12 @@ int qmha_solve_opts(const float* Q, const float* K, const float* V, float* O, in
                     int variant, unsigned flags, void* workspace, size_t workspace_bytes_, void* stream) {
     return solve_on(Q, K, V, O, B, N, d_model, h, variant, flags, workspace != nullptr, workspace, workspace_bytes_,
                     (hipStream_t)stream);
+}
+
+int qmha_solve_rect(const float* Q, const float* K, const float* V, float* O, int B, int Nq, int Nk, int d_model, int h,
+                    int variant, unsigned flags, void* workspace, size_t workspace_bytes_, void* stream) {
+    return solve_rect_on(Q, K, V, O, B, Nq, Nk, d_model, h, variant, flags, workspace != nullptr, workspace, workspace_bytes_,
+                         (hipStream_t)stream);
 }
 
 size_t qmha_workspace_size(int B, int N, int d_model, int h, int variant) {

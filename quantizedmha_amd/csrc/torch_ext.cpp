@@ -11,6 +11,8 @@
 //   * the work is enqueued on PyTorch's current HIP stream (ordered with the caller's other
 //     ops) instead of private streams plus a blocking device synchronisation;
 //   * `causal` (trailing, default false): causal attention through qmha_solve_opts;
+//   * `flash_solve_rect` (a second function, same arguments): K and V of one shape, Q with its own row count,
+//     through qmha_solve_rect; `flash_solve` itself still wants one shape;
 //   * a rejected shape raises (TORCH_CHECK on the C-ABI status) instead of a device assert.
 #include <torch/extension.h>
 // ROCm PyTorch reports HIP devices as device type "cuda": the guard / current-stream
@@ -59,7 +61,58 @@ static Tensor flash_solve(const Tensor& Q, const Tensor& K, const Tensor& V, int
     return out;
 }
 
+// flash_solve with a query length of its own (qmha_solve_rect): K and V share one shape, Q has its own row
+// count and the same batch count; the result is shaped like Q.  causal: bottom-right aligned.
+static Tensor flash_solve_rect(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t d_model, int64_t num_heads,
+                               const std::string& kernel = "fa_tc_int8_b", bool causal = false) {
+    TORCH_CHECK(Q.is_cuda() && K.is_cuda() && V.is_cuda(), "Inputs must be CUDA tensors");
+    TORCH_CHECK(Q.dtype() == torch::kFloat32, "Q must be float32");
+    TORCH_CHECK(K.dtype() == torch::kFloat32, "K must be float32");
+    TORCH_CHECK(V.dtype() == torch::kFloat32, "V must be float32");
+    auto Qc = Q.contiguous();
+    auto Kc = K.contiguous();
+    auto Vc = V.contiguous();
+    TORCH_CHECK(d_model > 0 && Qc.numel() % d_model == 0, "Q.numel() must be divisible by d_model");
+    TORCH_CHECK(Kc.sizes() == Vc.sizes(), "K and V must have the same shape");
+    TORCH_CHECK(Kc.numel() % d_model == 0, "K.numel() must be divisible by d_model");
+    const auto rows = [d_model](const Tensor& t, int64_t* B) {  // flash_solve's shape rule
+        const bool batched = t.dim() == 3 && t.size(2) == d_model;
+        *B = batched ? t.size(0) : 1;
+        return batched ? t.size(1) : t.numel() / d_model;
+    };
+    int64_t B = 1, Bk = 1;
+    const int64_t Nq = rows(Qc, &B), Nk = rows(Kc, &Bk);
+    TORCH_CHECK(B == Bk, "Q and K must have the same batch count");
+    int variant = qmha_variant_from_name(kernel.c_str());
+    if (variant < 0) {
+        TORCH_WARN("Kernel selection supports fa, fa_tc_v1a, fa_tc_int8_b, unfused, fa_mfma, fa_tc_int8_pt; '", kernel,
+                   "' routing to default 'fa_tc_int8_b'");
+        variant = QMHA_FA_TC_INT8_B;
+    }
+    auto out = torch::empty_like(Qc);
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(Qc.device());
+    const hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(Qc.device().index()).stream();
+    const int st = qmha_solve_rect(Qc.data_ptr<float>(), Kc.data_ptr<float>(), Vc.data_ptr<float>(),
+                                   out.data_ptr<float>(), static_cast<int>(B), static_cast<int>(Nq), static_cast<int>(Nk),
+                                   static_cast<int>(d_model), static_cast<int>(num_heads), variant,
+                                   causal ? QMHA_FLAG_CAUSAL : 0u, nullptr, 0, stream);
+    TORCH_CHECK(st == QMHA_OK, "flash_solve_rect(", kernel, "): ", qmha_status_string(st), ": ", qmha_last_error());
+    return out;
+}
+
 PYBIND11_MODULE(torch_ext, m) {
+    m.def("flash_solve_rect", &flash_solve_rect,
+          "FlashAttention solve with separate query and key lengths (HIP, MI355X)\n\n"
+          "Args:\n"
+          "  Q: Query tensor [Nq, d_model] (or [B, Nq, d_model])\n"
+          "  K: Key tensor [Nk, d_model] (or [B, Nk, d_model])\n"
+          "  V: Value tensor, shaped like K\n"
+          "  d_model: Model dimension\n"
+          "  num_heads: Number of attention heads\n"
+          "  kernel: Kernel variant (default: 'fa_tc_int8_b')\n"
+          "  causal: bottom-right aligned, query row r attends keys j <= r + (Nk - Nq) (default: False)",
+          pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("d_model"),
+          pybind11::arg("num_heads"), pybind11::arg("kernel") = "fa_tc_int8_b", pybind11::arg("causal") = false);
     m.def("flash_solve", &flash_solve,
           "FlashAttention solve (HIP, MI355X)\n\n"
           "Args:\n"

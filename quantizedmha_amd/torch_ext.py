@@ -13,6 +13,8 @@ reference has no batch; any other shape is one sequence of numel/d_model rows, a
 must have Q's shape; work is enqueued on torch's current stream instead of private
 streams + a blocking sync (torch orders it with surrounding ops on that stream).
 ROCm tensors report device type 'cuda', exactly as the reference's is_cuda() check expects.
+flash_solve_rect (additive, no reference counterpart) is flash_solve with a query length of its own: K and V
+share one shape, Q has its own row count (cross-attention, chunked prefill; qmha_solve_rect).
 """
 from __future__ import annotations
 
@@ -72,6 +74,48 @@ def flash_solve(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, d_model: int,
             st = lib.qmha_solve_ex(Qc.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), out.data_ptr(), B, N, d_model,
                                    num_heads, _lib.variant_id(kernel), stream)
     _lib.check(st, f"flash_solve({kernel})")
+    return out
+
+
+def flash_solve_rect(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, d_model: int, num_heads: int,
+                     kernel: str = _lib.DEFAULT_KERNEL, out: Optional[torch.Tensor] = None,
+                     causal: bool = False) -> torch.Tensor:
+    """flash_solve with a query length of its own (qmha_solve_rect): Q is [Nq, d_model] or [B, Nq, d_model],
+    K and V share one shape [Nk, d_model] or [B, Nk, d_model] with Q's batch count; returns a tensor shaped
+    like Q.  causal: bottom-right aligned, query row r attends keys j <= r + (Nk - Nq) (the Nq queries are the
+    last Nq positions of a sequence of Nk; Nk >= Nq).  Nq != Nk: fa_tc_int8_b at d = 32 / 64 / 128 and
+    fa_tc_v1a at d = 64 / 128; anything else raises.  Arguments and error behaviour as flash_solve."""
+    if not (Q.is_cuda and K.is_cuda and V.is_cuda):
+        raise RuntimeError("Inputs must be CUDA tensors")
+    for name, t in (("Q", Q), ("K", K), ("V", V)):
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{name} must be float32")
+    Qc, Kc, Vc = Q.contiguous(), K.contiguous(), V.contiguous()
+    d_model, num_heads = int(d_model), int(num_heads)
+    B, Nq = _shape(Qc, d_model)
+    if Kc.shape != Vc.shape:
+        raise RuntimeError("K and V must have the same shape")
+    if Kc.numel() % d_model != 0:
+        raise RuntimeError("K.numel() must be divisible by d_model")
+    Bk, Nk = _shape(Kc, d_model)
+    if Bk != B:
+        raise RuntimeError("Q and K must have the same batch count")
+    if kernel not in _lib.VARIANTS:
+        warnings.warn(f"Kernel selection supports {sorted(_lib.VARIANTS)}; '{kernel}' routing to default "
+                      f"'{_lib.DEFAULT_KERNEL}'")
+        kernel = _lib.DEFAULT_KERNEL
+    if out is None:
+        out = torch.empty_like(Qc)
+    elif (out.shape != Qc.shape or out.dtype != torch.float32 or out.device != Qc.device
+          or not out.is_contiguous()):
+        raise RuntimeError("out must be a contiguous float32 tensor of Q's shape on Q's device")
+    lib = _lib.load()
+    with torch.cuda.device(Qc.device):
+        stream = torch.cuda.current_stream(Qc.device).cuda_stream
+        st = lib.qmha_solve_rect(Qc.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), out.data_ptr(), B, Nq, Nk, d_model,
+                                 num_heads, _lib.variant_id(kernel), _lib.QMHA_FLAG_CAUSAL if causal else 0, None, 0,
+                                 stream)
+    _lib.check(st, f"flash_solve_rect({kernel})")
     return out
 
 

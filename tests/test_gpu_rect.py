@@ -1,0 +1,292 @@
+"""GPU tests (MI355X) of rectangular attention: qmha_solve_rect and its bindings.
+
+References (tests/rect_ref.py: the square restatements of tests/causal_ref.py on Q padded into the last rows, held
+to float64 rectangular attention by tests/test_rect_cpu.py) and bounds, the project's own:
+  * fa_tc_int8_b: EVERY element within 2 u_r + 5e-5 of the restatement in the kernels' base-2 score arithmetic
+    (u_r: the row's one-flip unit, tests/causal_ref.py).
+  * fa_tc_v1a: within fp16_lazy_tol(Nk) of its own contract (fa_fp16_lazy) and within max(1e-3, 1e-3 |ref|) of
+    float64 rectangular attention.
+  * shifted superdiagonal (every row's strongest key is its first masked one): int8 2 one-flip units, fp16
+    2^-10 max|V|; tests/test_rect_cpu.py shows two wrong masks hundreds of times outside these.
+Every call writes O into a buffer with a sentinel-filled guard behind it, which must come back untouched.
+The observed maxima are printed in pytest's terminal summary (tests/parity_log.py).
+"""
+import ctypes
+import functools
+import importlib.util
+import os
+import sysconfig
+
+import numpy as np
+import pytest
+
+from tests import causal_ref as cr
+from tests import parity_log
+from tests import rect_ref as rr
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+INT8, F16 = "fa_tc_int8_b", "fa_tc_v1a"
+CAUSAL = 1
+GUARD = 7.25
+_ids = lambda v: rr.case_id(v) if isinstance(v, tuple) and len(v) == 6 else str(v)  # noqa: E731
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from quantizedmha_amd import _lib
+    _lib.load()  # raises if the HIP library is missing: no silent fallback
+    return torch.device("cuda:0")
+
+
+def to_dev(dev, *xs):
+    return [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in xs]
+
+
+def solve_rect(variant, t, d_model, h, flags, ws=None, ws_bytes=None, stream=None, expect=0):
+    """qmha_solve_rect on device tensors t = [Q [B, Nq, d_model], K, V [B, Nk, d_model]]; returns O (numpy) after a
+    sync.  O is the head of a buffer whose tail (32 rows) holds a sentinel that must survive the call."""
+    from quantizedmha_amd import _lib
+    lib = _lib.load()
+    Q, K, V = t
+    B, Nq, Nk = Q.shape[0], Q.shape[1], K.shape[1]
+    buf = torch.full((Q.numel() + 32 * d_model,), GUARD, dtype=torch.float32, device=Q.device)
+    torch.cuda.synchronize()  # the fill is done before a call on another stream may write O
+    st = lib.qmha_solve_rect(Q.data_ptr(), K.data_ptr(), V.data_ptr(), buf.data_ptr(), B, Nq, Nk, d_model, h,
+                             _lib.VARIANTS[variant], flags, ws.data_ptr() if ws is not None else None,
+                             (ws.numel() if ws_bytes is None else ws_bytes) if ws is not None else 0, stream)
+    torch.cuda.synchronize()
+    assert st == expect, (st, lib.qmha_last_error().decode())
+    got = buf.cpu().numpy()
+    assert (got[Q.numel():] == GUARD).all(), "O written past its last row"
+    return got[:Q.numel()].reshape(Q.shape)
+
+
+def solve_opts(variant, t, d_model, h, flags):
+    from quantizedmha_amd import _lib
+    lib = _lib.load()
+    out = torch.empty_like(t[0])
+    st = lib.qmha_solve_opts(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), out.data_ptr(), t[0].shape[0],
+                             t[0].shape[1], d_model, h, _lib.VARIANTS[variant], flags, None, 0, None)
+    torch.cuda.synchronize()
+    assert st == 0, (st, lib.qmha_last_error().decode())
+    return out.cpu().numpy()
+
+
+def assert_int8(label, got, ref, unit):
+    assert np.isfinite(got).all()
+    err = np.abs(got.astype(np.float64) - ref)
+    units = cr.flip_units(err, unit)
+    parity_log.record(f"{label} [max error beyond 5e-5, in one-flip units]", INT8 + "+r", units,
+                      float((err > 5e-5).mean()), 2.0)
+    print(f"{label}: max|gpu - ref| = {err.max():.3e}, worst (err - 5e-5) / u_r = {units:.3f} (bound 2)")
+    assert (err <= 2.0 * unit + 5e-5).all(), (label, float(err.max()), units)
+
+
+def assert_f16(label, got, contract, tol, exact=None):
+    """Within tol of the kernel's contract; with `exact`, also within max(1e-3, 1e-3 |ref|) of float64."""
+    from oracle import oracle
+    assert np.isfinite(got).all()
+    err = float(np.abs(got.astype(np.float64) - contract).max())
+    parity_log.record(f"{label} (vs lazy contract)", F16 + "+r", err, float((np.abs(got - contract) > 5e-5).mean()), tol)
+    print(f"{label}: max|gpu - lazy contract| = {err:.3e} (bound {tol:.2e})")
+    assert err <= tol, (label, err, tol)
+    if exact is not None:
+        far = float(np.abs(got - exact).max())
+        parity_log.record(f"{label} (vs float64)", F16 + "+r", far, float((np.abs(got - exact) > 5e-5).mean()), 1e-3)
+        print(f"{label}: max|gpu - float64| = {far:.3e} (bound max(1e-3, 1e-3 |ref|))")
+        assert oracle.verify_results(got, exact.astype(np.float32), 1e-3, 1e-3) == -1, (label, far)
+
+
+# ---- parity ------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def int8_reference(case, dist):
+    """(Q, K, V, O_ref in the kernels' base-2 arithmetic, per-element one-flip unit), computed once and shared."""
+    from oracle import oracle
+    Nq, Nk, d_model, h, B, causal = case
+    Q, K, V = rr.inputs(Nq, Nk, d_model, B, dist, rr.seed_of(case, dist))
+    ref, unit = rr.fa_int8(oracle, Q, K, V, d_model, h, causal=causal, base2=True)
+    return Q, K, V, ref, cr.per_element(unit, d_model // h)
+
+
+@functools.lru_cache(maxsize=None)
+def f16_reference(case, dist):
+    Nq, Nk, d_model, h, B, causal = case
+    Q, K, V = rr.inputs(Nq, Nk, d_model, B, dist, rr.seed_of(case, dist))
+    return (Q, K, V, rr.fa_fp16_lazy(None, Q, K, V, d_model, h, causal=causal),
+            rr.attention_f64(Q, K, V, d_model, h, causal))
+
+
+@pytest.mark.parametrize("dist", rr.DISTS)
+@pytest.mark.parametrize("case", rr.INT8_CASES, ids=_ids)
+def test_int8_rect_vs_base2_restatement(dev, case, dist):
+    Nq, Nk, d_model, h, B, causal = case
+    Q, K, V, ref, unit = int8_reference(case, dist)
+    got = solve_rect(INT8, to_dev(dev, Q, K, V), d_model, h, CAUSAL if causal else 0)
+    assert_int8(f"{rr.case_id(case)} {dist}", got, ref, unit)
+
+
+@pytest.mark.parametrize("dist", rr.DISTS)
+@pytest.mark.parametrize("case", rr.F16_CASES, ids=_ids)
+def test_fp16_rect_vs_lazy_contract_and_float64(dev, case, dist):
+    Nq, Nk, d_model, h, B, causal = case
+    Q, K, V, contract, exact = f16_reference(case, dist)
+    got = solve_rect(F16, to_dev(dev, Q, K, V), d_model, h, CAUSAL if causal else 0)
+    assert_f16(f"{rr.case_id(case)} {dist}", got, contract, cr.fp16_lazy_tol(Nk), exact)
+
+
+# ---- the mask: every row's strongest key is its first masked one ----------------------------------------------
+@pytest.mark.parametrize("shape", rr.SUPERDIAG, ids=str)
+def test_int8_shifted_superdiagonal(dev, shape):
+    from oracle import oracle
+    Nq, Nk, d_model, h, B = shape
+    Q, K, V = rr.superdiag_inputs(Nq, Nk, d_model, B)
+    ref, unit = rr.fa_int8(oracle, Q, K, V, d_model, h, causal=True, base2=True)
+    got = solve_rect(INT8, to_dev(dev, Q, K, V), d_model, h, CAUSAL)
+    assert_int8(f"superdiag {shape}", got, ref, cr.per_element(unit, d_model // h))
+
+
+@pytest.mark.parametrize("shape", [s for s in rr.SUPERDIAG if s[2] // s[3] in (64, 128)], ids=str)
+def test_fp16_shifted_superdiagonal(dev, shape):
+    """Against the contract only: with p up to 2^12 rounded to half the contract itself is ~1e-2 from float64 on
+    these inputs (a property of fp16 p)."""
+    Nq, Nk, d_model, h, B = shape
+    Q, K, V = rr.superdiag_inputs(Nq, Nk, d_model, B)
+    ref = rr.fa_fp16_lazy(None, Q, K, V, d_model, h, causal=True)
+    got = solve_rect(F16, to_dev(dev, Q, K, V), d_model, h, CAUSAL)
+    assert_f16(f"superdiag {shape}", got, ref, 2.0 ** -10 * float(np.abs(V).max()))
+
+
+# ---- chunked prefill -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("variant,d", [(INT8, 32), (INT8, 64), (F16, 64)])
+def test_chunked_prefill_reproduces_full_prefill(dev, variant, d):
+    """N = 256 in chunks of 64 rows: chunk c is qmha_solve_rect(Q[64c : 64c + 64], K[: 64(c + 1)], V[: 64(c + 1)], causal).
+    The concatenation is held to the square causal reference at N = 256 and to the GPU's own
+    qmha_solve_opts(CAUSAL) result, both at the variant's bound."""
+    from oracle import oracle
+    N, C, h, B = 256, 64, 2, 2
+    d_model = h * d
+    Q, K, V = cr.inputs(N, d_model, B, "normal", 500 + d)
+    t = to_dev(dev, Q, K, V)
+    parts = []
+    for c in range(N // C):
+        n = C * (c + 1)
+        tc = [t[0][:, n - C:n].contiguous(), t[1][:, :n].contiguous(), t[2][:, :n].contiguous()]
+        parts.append(solve_rect(variant, tc, d_model, h, CAUSAL))
+    got = np.concatenate(parts, axis=1)
+    square = solve_opts(variant, t, d_model, h, CAUSAL)
+    same = np.array_equal(got, square)
+    print(f"{variant} d{d}: chunked prefill {'is' if same else 'is NOT'} bit-identical to the square causal call"
+          f" (max difference {np.abs(got - square).max():.3e})")
+    if variant == INT8:
+        ref, unit, _ = cr.fa_int8(oracle, Q, K, V, d_model, h, causal=True, base2=True)
+        pe = cr.per_element(unit, d)
+        assert_int8(f"chunked prefill d{d}", got, ref, pe)
+        assert_int8(f"chunked prefill d{d} (vs the square GPU call)", got, square.astype(np.float64), pe)
+    else:
+        ref = cr.fa_fp16_lazy(None, Q, K, V, d_model, h, causal=True)[0]
+        assert_f16(f"chunked prefill d{d}", got, ref, cr.fp16_lazy_tol(N), cr.attention_f64(Q, K, V, d_model, h, causal=True))
+        assert_f16(f"chunked prefill d{d} (vs the square GPU call)", got, square, cr.fp16_lazy_tol(N))
+
+
+# ---- routing -----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("variant,flags", [("fa", 0), (F16, 0), (INT8, 0), ("unfused", 0), ("fa_mfma", 0),
+                                           ("fa_tc_int8_pt", 0), (INT8, CAUSAL), (F16, CAUSAL)])
+def test_square_calls_are_qmha_solve_opts(dev, variant, flags):
+    N, d_model, h = 96, 128, 2
+    t = to_dev(dev, *cr.inputs(N, d_model, 2, "normal", 510))
+    assert np.array_equal(solve_rect(variant, t, d_model, h, flags), solve_opts(variant, t, d_model, h, flags))
+
+
+@pytest.mark.parametrize("variant", [INT8, F16])
+@pytest.mark.parametrize("case", [rr.CASES[2], rr.CASES[5]], ids=_ids)
+def test_repeatable_and_batch_independent(dev, variant, case):
+    """The same call twice is bit-identical; each sequence of a B = 2 call equals its own B = 1 call."""
+    Nq, Nk, d_model, h, B, causal = case
+    flags = CAUSAL if causal else 0
+    t = to_dev(dev, *rr.inputs(Nq, Nk, d_model, B, "normal", 520))
+    a = solve_rect(variant, t, d_model, h, flags)
+    assert np.array_equal(a, solve_rect(variant, t, d_model, h, flags))
+    for b in range(B):
+        one = solve_rect(variant, [x[b:b + 1].contiguous() for x in t], d_model, h, flags)
+        assert np.array_equal(one[0], a[b])
+
+
+@pytest.mark.parametrize("variant", [INT8, F16])
+def test_caller_workspace_on_a_side_stream_and_profile_marks(dev, variant):
+    """Caller-owned scratch of exactly qmha_workspace_size(B, Nk, ...) bytes on a non-default stream equals the
+    leased-slot result; one byte less is refused; with profiling on, every call is recorded with a main-kernel and
+    a pre-pass time."""
+    from quantizedmha_amd import _lib
+    lib = _lib.load()
+    Nq, Nk, d_model, h, B, _ = rr.CASES[2]
+    t = to_dev(dev, *rr.inputs(Nq, Nk, d_model, B, "uniform", 530))
+    want = solve_rect(variant, t, d_model, h, CAUSAL)
+    need = lib.qmha_workspace_size(B, Nk, d_model, h, _lib.VARIANTS[variant])
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    s = torch.cuda.Stream(device=dev)
+    s.wait_stream(torch.cuda.current_stream(dev))
+    assert np.array_equal(solve_rect(variant, t, d_model, h, CAUSAL, ws=ws, stream=s.cuda_stream), want)
+    solve_rect(variant, t, d_model, h, CAUSAL, ws=ws, ws_bytes=need - 1, stream=s.cuda_stream, expect=1)
+    lib.qmha_profile_collect(None, None, None)
+    lib.qmha_profile_enable(1)
+    try:
+        for _ in range(3):
+            assert np.array_equal(solve_rect(variant, t, d_model, h, CAUSAL), want)
+        main_ms, pre_ms, calls = ctypes.c_double(), ctypes.c_double(), ctypes.c_longlong()
+        assert lib.qmha_profile_collect(ctypes.byref(main_ms), ctypes.byref(calls), ctypes.byref(pre_ms)) == 0
+    finally:
+        lib.qmha_profile_enable(0)
+    assert calls.value == 3 and main_ms.value > 0.0 and pre_ms.value > 0.0, (calls.value, main_ms.value, pre_ms.value)
+
+
+@pytest.mark.parametrize("variant,d_model,h", [("fa", 128, 2), ("unfused", 128, 2), ("fa_mfma", 128, 2),
+                                               ("fa_tc_int8_pt", 128, 2), (INT8, 192, 2), (F16, 64, 2)])
+@pytest.mark.parametrize("flags", [0, CAUSAL])
+def test_unsupported_rect_touches_nothing(dev, variant, d_model, h, flags):
+    from quantizedmha_amd import _lib
+    Q, K, V = rr.inputs(64, 128, d_model, 1, "normal", 540)
+    got = solve_rect(variant, to_dev(dev, Q, K, V), d_model, h, flags, expect=4)
+    assert (got == GUARD).all()
+    msg = _lib.load().qmha_last_error().decode()
+    assert variant in msg and f"d = {d_model // h}" in msg
+
+
+# ---- bindings ------------------------------------------------------------------------------------------
+def test_bindings_route_to_qmha_solve_rect(dev):
+    """torch_ext.flash_solve_rect (the Python mirror, with out=, and the compiled module) gives the C-ABI's result
+    bit for bit; mismatched K / V and batch counts raise; flash_solve still wants one shape."""
+    from quantizedmha_amd import _lib, torch_ext
+    Nq, Nk, d_model, h, B = 96, 160, 128, 2, 2
+    t = to_dev(dev, *rr.inputs(Nq, Nk, d_model, B, "normal", 550))
+    spec = importlib.util.spec_from_file_location(
+        "torch_ext", os.path.join(_lib.LIB_DIR, "torch_ext" + sysconfig.get_config_var("EXT_SUFFIX")))
+    compiled = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(compiled)
+    for variant in (INT8, F16):
+        for causal in (False, True):
+            want = solve_rect(variant, t, d_model, h, CAUSAL if causal else 0)
+            out = torch.empty_like(t[0])
+            got = torch_ext.flash_solve_rect(t[0], t[1], t[2], d_model, h, variant, out=out, causal=causal)
+            torch.cuda.synchronize()
+            assert got is out and np.array_equal(out.cpu().numpy(), want)
+            got = compiled.flash_solve_rect(t[0], t[1], t[2], d_model, h, variant, causal=causal)
+            torch.cuda.synchronize()
+            assert got.shape == t[0].shape and np.array_equal(got.cpu().numpy(), want)
+    one = torch_ext.flash_solve_rect(t[0][0], t[1][0], t[2][0], d_model, h)  # [Nq, d_model] against [Nk, d_model]
+    torch.cuda.synchronize()
+    assert np.array_equal(one.cpu().numpy(), solve_rect(INT8, [x[:1].contiguous() for x in t], d_model, h, 0)[0])
+    for mod in (torch_ext, compiled):
+        with pytest.raises(RuntimeError, match="K and V must have the same shape"):
+            mod.flash_solve_rect(t[0], t[1], t[2][:, :128].contiguous(), d_model, h)
+        with pytest.raises(RuntimeError, match="same batch count"):
+            mod.flash_solve_rect(t[0][:1].contiguous(), t[1], t[2], d_model, h)
+        with pytest.raises(RuntimeError, match="same shape"):
+            mod.flash_solve(t[0], t[1], t[2], d_model, h)
+    with pytest.raises(RuntimeError, match="not supported"):
+        torch_ext.flash_solve_rect(t[0], t[1], t[2], d_model, h, "fa")
+    with pytest.raises(RuntimeError, match="Nk >= Nq"):
+        torch_ext.flash_solve_rect(t[1], t[0], t[0], d_model, h, causal=True)

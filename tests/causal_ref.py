@@ -20,8 +20,8 @@ Also here: fa_int8's base2 switch (the causal kernel's own score arithmetic) and
 inputs take the kernel's re-anchor branch?); fa_fp16_lazy, the fp16 kernel's contract (oracle fa_fp16_lazy_item)
 restated with the same mask, which counts the rows that rebase; and HARD_CASES, inputs that take those two
 branches on and off the diagonal tile and put every row's strongest key just behind the mask.  Both
-restatements take a private _mutant= (two wrong masks) so the CPU tests can show that the hard cases would
-catch one.
+restatements take a private _mutant= (two wrong masks, two missing rescales) so the CPU tests can show that the
+hard cases would catch one.
 """
 import collections
 
@@ -68,6 +68,12 @@ def softmax_scale_log2(d):
     return f((f(1.0) / np.sqrt(f(d))) * f(1.4426950408889634))
 
 
+MASK_MUTANTS = ("mask_after_max", "leak_next")
+# a re-anchoring group (int8) or a rebasing row (fp16) whose l / whose O keeps the scale it had before the branch
+RESCALE_MUTANTS = ("stale_l", "stale_o")
+_MUTANTS = (None,) + MASK_MUTANTS + RESCALE_MUTANTS
+
+
 def _future(mutant):
     """[r][j] mask of the diagonal tile: j > r; the "leak_next" mutant lets key r + 1 through."""
     return _IDX[None, :] > _IDX[:, None] + (1 if mutant == "leak_next" else 0)
@@ -83,8 +89,11 @@ def fa_int8(oracle, Q, K, V, d_model, h, causal=False, base2=False, _mutant=None
     Rise.log2[b, r, k] is the largest rise of row r's running max over one tile in log2 units (the kernel
     re-anchors when m_new - anchor > 48, and anchor <= the previous m), Rise.diag whether that tile was the
     diagonal one.  _mutant (tests only) selects a wrong mask: "mask_after_max" forms the row max over the
-    unmasked scores, "leak_next" masks j > r + 1."""
-    assert _mutant in (None, "mask_after_max", "leak_next")
+    unmasked scores, "leak_next" masks j > r + 1; or a wrong re-anchor: on a tile where the group re-anchors,
+    "stale_l" is the kernel without `l_run *= f` and "stale_o" the kernel without `o *= f` -- the kernel holds
+    l 2^(m - anchor) and O 2^(m - anchor), so the state that is not rescaled reaches the new anchor as
+    2^(m_prev - old anchor) >= 1 times its value where the correct factor is alpha = 2^(m_prev - m_new)."""
+    assert _mutant in _MUTANTS
     f = np.float32
     Q, K, V = (np.ascontiguousarray(x, dtype=f) for x in (Q, K, V))
     squeeze = Q.ndim == 2
@@ -140,14 +149,18 @@ def fa_int8(oracle, Q, K, V, d_model, h, causal=False, base2=False, _mutant=None
                     up = (m_new - m_prev) * to_log2
                     on_diag = np.where(up > rise, diag, on_diag)
                     rise = np.maximum(rise, up).astype(f)
+                    alpha = ex((m_prev - m_new).astype(f)).astype(f)
+                    alpha_l = alpha_o = alpha
                     if ((m_new - anchor) * to_log2 > f(REANCHOR)).any():  # wave-uniform (a ballot) in the kernel
+                        if _mutant in RESCALE_MUTANTS:
+                            stale = ex((m_prev - anchor).astype(f)).astype(f)
+                            alpha_l, alpha_o = (stale, alpha) if _mutant == "stale_l" else (alpha, stale)
                         anchor = m_new
                         n_anchor += 1
                         anchor_diag |= bool(diag)
                     sum_new = _xor_tree_sum32(p)
-                    alpha = ex((m_prev - m_new).astype(f)).astype(f)
-                    l = _fma32(alpha, l, sum_new)
-                    O = (O * alpha[:, None]).astype(f)
+                    l = _fma32(alpha_l, l, sum_new)
+                    O = (O * alpha_o[:, None]).astype(f)
                     m_prev = m_new
                     Pi, sP = _quantize_tile(p)
                     T = (Pi @ Vt).astype(f)  # exact: |T| <= 32 * 127 * 128 < 2^24
@@ -249,7 +262,7 @@ def fp16_lazy_tol(N):
     return 1e-4 if N <= 256 else 4e-5
 
 
-def fa_fp16_lazy(oracle, Q, K, V, d_model, h, causal=False, _mutant=None):
+def fa_fp16_lazy(oracle, Q, K, V, d_model, h, causal=False, _mutant=None, per_row=False):
     """float32 numpy restatement of oracle/qmha_oracle.c:fa_fp16_lazy_item, quarters form (d = 64, 128), with the
     causal contract of DESIGN.md 10.1; returns (O like Q, rebased (row, tile) pairs, those on a diagonal tile).
 
@@ -260,8 +273,10 @@ def fa_fp16_lazy(oracle, Q, K, V, d_model, h, causal=False, _mutant=None):
     quarter; the guard is l > 1e-10.  causal: group g visits tiles 0..g and on the diagonal tile j > r is -inf
     before anything uses the score, so a masked key takes no part in a quarter sum or in the rebase's row
     max.  All groups advance together, tile by tile (`oracle` is unused: the signature mirrors fa_int8).
-    _mutant as in fa_int8."""
-    assert _mutant in (None, "mask_after_max", "leak_next")
+    _mutant as in fa_int8; here "stale_l" / "stale_o" leave l / O of a rebasing row unscaled (the kernel without
+    `l_run[qb] *= alpha` / `o[m][qb] *= alpha`).  per_row=True returns the two counts per row, [B, N, h], instead
+    of their totals."""
+    assert _mutant in _MUTANTS
     f = np.float32
     Q, K, V = (np.ascontiguousarray(x, dtype=f) for x in (Q, K, V))
     squeeze = Q.ndim == 2
@@ -273,7 +288,8 @@ def fa_fp16_lazy(oracle, Q, K, V, d_model, h, causal=False, _mutant=None):
     c = softmax_scale_log2(d)
     future = _future(_mutant)
     out = np.zeros_like(Q)
-    rebased = rebased_diag = 0
+    rebased = np.zeros((B, N, h), np.int64)
+    rebased_diag = np.zeros((B, N, h), np.int64)
     with np.errstate(over="ignore"):  # p overflows to inf before a rebase, as in the kernel
         for b in range(B):
             for k in range(h):
@@ -300,14 +316,16 @@ def fa_fp16_lazy(oracle, Q, K, V, d_model, h, causal=False, _mutant=None):
                         rows = r0 + np.nonzero(over)[0]
                         xm = (mx[over] * c).astype(f)
                         alpha = np.exp2((m[rows] - xm).astype(f)).astype(f)
-                        l[rows] *= alpha[:, None]
-                        O[rows] *= alpha[:, None]
+                        if _mutant != "stale_l":
+                            l[rows] *= alpha[:, None]
+                        if _mutant != "stale_o":
+                            O[rows] *= alpha[:, None]
                         m[rows] = xm
                         p[over] = np.exp2(_fma32(s[over], np.broadcast_to(c, s[over].shape), -xm[:, None])).astype(f)
                         ts[over] = _quarter_sums(p[over])
-                        rebased += int(over.sum())
+                        rebased[b, rows, k] += 1
                         if causal:
-                            rebased_diag += int(over[:GROUP].sum())
+                            rebased_diag[b, rows[rows < r0 + GROUP], k] += 1
                     ph = _half(p)
                     l[r0:] += ts
                     vt = v[t * GROUP:(t + 1) * GROUP]
@@ -318,7 +336,9 @@ def fa_fp16_lazy(oracle, Q, K, V, d_model, h, causal=False, _mutant=None):
                 lr = (l[:, 0] + l[:, 1]) + (l[:, 2] + l[:, 3])
                 ok = lr > f(1e-10)
                 out[b, :, k * d:(k + 1) * d] = np.where(ok[:, None], O / np.where(ok, lr, f(1.0))[:, None], f(0.0))
-    return (out[0] if squeeze else out), rebased, rebased_diag
+    if not per_row:
+        return (out[0] if squeeze else out), int(rebased.sum()), int(rebased_diag.sum())
+    return (out[0], rebased[0], rebased_diag[0]) if squeeze else (out, rebased, rebased_diag)
 
 
 # ---- hard inputs: the re-anchor (int8) and rebase (fp16) branches, the mask before the max ----------------

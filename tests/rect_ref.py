@@ -1,15 +1,23 @@
 """References for rectangular attention (Nq != Nk), built from tests/causal_ref.py.
 
-Helper of tests/test_rect_cpu.py and tests/test_gpu_rect.py (not a test).  No arithmetic is restated here:
-query groups are independent of each other and the K / V scales are per 32-row group, so a rectangular
-result is a slice of a square one.
+Helper of tests/test_rect_cpu.py, tests/test_rect_hard_cpu.py and tests/test_gpu_rect.py (not a test).  No
+arithmetic is restated here: query groups are independent of each other and the K / V scales are per 32-row
+group, so a rectangular result is a slice of a square one.
   * causal (bottom-right aligned, row r attends keys j <= r + Nk - Nq): Q goes into the LAST Nq rows of a zero
     [B, Nk, d_model] array, the square causal restatement runs at N = Nk, and the last Nq rows of its output
     (and of its one-flip units) are the answer.  Nk - Nq is a multiple of 32, so the zero rows fill whole
     query groups of their own and touch no scale of a real group.
   * non-causal: Q is fed in pieces of at most Nk rows, padded likewise, with causal=False.
-The _mutant argument of causal_ref passes straight through.
+The _mutant argument of causal_ref passes straight through.  With stats=True both restatements also return
+causal_ref's branch statistics (did a query group re-anchor, did a row rebase?), sliced to the real query rows
+like the output; the zero pad rows score 0 against every key, stay at m0 = 0 and take neither branch (asserted).
+
+hard_inputs() cuts causal_ref's hard cases to a rectangle: the case is built at N = max(Nq, Nk) and Q keeps its
+LAST Nq rows, K and V their first Nk, so a causal rectangular call is the last chunk of the square hard problem
+at N = Nk.  HARD_INT8 / HARD_F16 list the shapes of DESIGN.md 11.3.
 """
+import collections
+
 import numpy as np
 
 from tests import causal_ref as cr
@@ -64,6 +72,54 @@ def superdiag_inputs(Nq, Nk, d_model, B):
     return Q, K, rng.standard_normal((B, Nk, d_model)).astype(np.float32)
 
 
+def hard_inputs(name, d, Nq, Nk, **kw):
+    """(Q [B, Nq, h d], K, V [B, Nk, h d]) of causal_ref.HARD[name] built at N = max(Nq, Nk), as copies."""
+    c = cr.HARD[name]
+    N = max(Nq, Nk)
+    Q, K, V = c.build(d, c.h, N, c.B, **kw)
+    return Q[:, N - Nq:].copy(), K[:, :Nk].copy(), V[:, :Nk].copy()
+
+
+def zero_v_hard_inputs(d, Nq, Nk):
+    """causal_ref.zero_v_inputs (V = 0) cut to a rectangle the same way, with `underflow`'s h and B."""
+    c = cr.HARD["underflow"]
+    N = max(Nq, Nk)
+    Q, K, V = cr.zero_v_inputs(d, c.h, N, c.B)
+    return Q[:, N - Nq:].copy(), K[:, :Nk].copy(), V[:, :Nk].copy()
+
+
+# (name, Nq, Nk, causal) with the head sizes each variant runs it at; h and B are those of causal_ref.HARD[name]
+HardShape = collections.namedtuple("HardShape", "name Nq Nk causal int8_d f16_d")
+_ALL8, _ALL16 = (32, 64, 128), (64, 128)
+HARD_SHAPES = [
+    HardShape("const", 288, 352, True, _ALL8, _ALL16),       # nqb = 3, offset 2: every wave re-anchors on tile 0
+    HardShape("spike_tile", 160, 256, True, _ALL8, _ALL16),  # nqb = 2, offset 3: pass 0 re-anchors, pass 1 restarts
+    HardShape("ramp", 64, 512, True, _ALL8, _ALL16),         # 16 tiles: re-anchors on accumulated distance only
+    HardShape("staircase", 64, 512, True, (), _ALL16),       # a rebase on every second tile of the loop
+    HardShape("spike_tile", 64, 256, False, _ALL8, _ALL16),  # both branches without the mask, after four plain tiles
+    HardShape("spike_tile", 288, 224, False, _ALL8, _ALL16),  # Nq > Nk, nqb = 3, Gk = 7: partial last stage
+    HardShape("const", 160, 96, False, _ALL8, _ALL16),       # Nq > Nk, a second workgroup with one active wave
+    HardShape("ramp", 32, 512, False, _ALL8, _ALL16),        # one active wave, accumulated re-anchor
+    HardShape("staircase", 160, 224, False, (), _ALL16),
+    HardShape("staircase", 32, 512, False, (), _ALL16),
+    HardShape("underflow", 32, 96, True, (64,), (64,)),      # the guards: l under 1e-20 / 1e-10 gives exactly 0
+    HardShape("underflow", 32, 96, False, (64,), (64,)),
+    HardShape("underflow", 160, 96, False, (64,), (64,)),
+    HardShape("zero_q", 64, 96, True, (32,), (128,)),        # B = 2; Q = 0: prefix mean / mean of V
+    HardShape("zero_q", 64, 96, False, (32,), (128,)),
+    HardShape("nan_int8", 32, 96, True, (64,), ()),          # one NaN in the Q slice (row 4), two each in K and V
+    HardShape("nan_int8", 32, 96, False, (64,), ()),
+]
+HARD_INT8 = [(s, d) for s in HARD_SHAPES for d in s.int8_d]
+HARD_F16 = [(s, d) for s in HARD_SHAPES for d in s.f16_d]
+
+
+def hard_id(v):
+    if isinstance(v, HardShape):
+        return f"{v.name}-Nq{v.Nq}-Nk{v.Nk}-{'causal' if v.causal else 'full'}"
+    return str(v)
+
+
 def _batched(Q, K, V):
     Q, K, V = (np.ascontiguousarray(x, dtype=np.float32) for x in (Q, K, V))
     if Q.ndim == 2:
@@ -86,27 +142,42 @@ def _padded(Q, r0, r1, Nk):
     return P
 
 
-def fa_int8(oracle, Q, K, V, d_model, h, causal=False, base2=False, _mutant=None):
-    """causal_ref.fa_int8 for Q [B, Nq, d_model] against K, V [B, Nk, d_model]: (O like Q, u [B, Nq, h])."""
+def fa_int8(oracle, Q, K, V, d_model, h, causal=False, base2=False, _mutant=None, stats=False):
+    """causal_ref.fa_int8 for Q [B, Nq, d_model] against K, V [B, Nk, d_model]: (O like Q, u [B, Nq, h]); with
+    stats=True also causal_ref's Rise, each field [B, Nq, h] (a group's re-anchor counts stand on its 32 rows)."""
     Q, K, V, squeeze = _batched(Q, K, V)
     Nq, Nk = Q.shape[1], K.shape[1]
     out = np.zeros_like(Q)
     unit = np.zeros((Q.shape[0], Nq, h), np.float32)
+    rise = cr.Rise(*(np.zeros((Q.shape[0], Nq, h), t) for t in (np.float32, bool, np.int64, bool)))
     for r0, r1 in _pieces(Nq, Nk, causal):
-        o, u, _ = cr.fa_int8(oracle, _padded(Q, r0, r1, Nk), K, V, d_model, h, causal=causal, base2=base2, _mutant=_mutant)
-        out[:, r0:r1], unit[:, r0:r1] = o[:, Nk - (r1 - r0):], u[:, Nk - (r1 - r0):]
-    return (out[0], unit[0]) if squeeze else (out, unit)
+        pad = Nk - (r1 - r0)
+        o, u, ri = cr.fa_int8(oracle, _padded(Q, r0, r1, Nk), K, V, d_model, h, causal=causal, base2=base2, _mutant=_mutant)
+        out[:, r0:r1], unit[:, r0:r1] = o[:, pad:], u[:, pad:]
+        for mine, theirs in zip(rise, ri):
+            assert not theirs[:, :pad].any(), "a zero pad row rose or re-anchored"
+            mine[:, r0:r1] = theirs[:, pad:]
+    if squeeze:
+        out, unit, rise = out[0], unit[0], cr.Rise(*(x[0] for x in rise))
+    return (out, unit, rise) if stats else (out, unit)
 
 
-def fa_fp16_lazy(oracle, Q, K, V, d_model, h, causal=False, _mutant=None):
-    """causal_ref.fa_fp16_lazy for Q [B, Nq, d_model] against K, V [B, Nk, d_model]: O like Q."""
+def fa_fp16_lazy(oracle, Q, K, V, d_model, h, causal=False, _mutant=None, stats=False):
+    """causal_ref.fa_fp16_lazy for Q [B, Nq, d_model] against K, V [B, Nk, d_model]: O like Q; with stats=True
+    (O, rebased (row, tile) pairs, those on a diagonal tile), counted over the real query rows of every piece."""
     Q, K, V, squeeze = _batched(Q, K, V)
     Nq, Nk = Q.shape[1], K.shape[1]
     out = np.zeros_like(Q)
+    rebased = on_diag = 0
     for r0, r1 in _pieces(Nq, Nk, causal):
-        o = cr.fa_fp16_lazy(oracle, _padded(Q, r0, r1, Nk), K, V, d_model, h, causal=causal, _mutant=_mutant)[0]
-        out[:, r0:r1] = o[:, Nk - (r1 - r0):]
-    return out[0] if squeeze else out
+        pad = Nk - (r1 - r0)
+        o, n, nd = cr.fa_fp16_lazy(oracle, _padded(Q, r0, r1, Nk), K, V, d_model, h, causal=causal, _mutant=_mutant,
+                                   per_row=True)
+        assert not n[:, :pad].any() and not nd[:, :pad].any(), "a zero pad row rebased"
+        out[:, r0:r1] = o[:, pad:]
+        rebased, on_diag = rebased + int(n.sum()), on_diag + int(nd.sum())
+    out = out[0] if squeeze else out
+    return (out, rebased, on_diag) if stats else out
 
 
 def attention_f64(Q, K, V, d_model, h, causal=False):

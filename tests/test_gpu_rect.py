@@ -8,6 +8,10 @@ to float64 rectangular attention by tests/test_rect_cpu.py) and bounds, the proj
     float64 rectangular attention.
   * shifted superdiagonal (every row's strongest key is its first masked one): int8 2 one-flip units, fp16
     2^-10 max|V|; tests/test_rect_cpu.py shows two wrong masks hundreds of times outside these.
+  * HARD SHAPES (rect_ref.HARD_SHAPES: causal_ref's hard cases cut to rectangles): inputs that take the rectangular
+    kernels' own int8 re-anchor, fp16 rebase and guards, with and without the mask, at the same two bounds;
+    tests/test_rect_hard_cpu.py shows a re-anchor or rebase without its rescale hundreds of times outside them.
+    Batch-chunked calls (qmha_set_overlap_chunks) with Nq != Nk are held bit for bit to the unchunked call.
 Every call writes O into a buffer with a sentinel-filled guard behind it, which must come back untouched.
 The observed maxima are printed in pytest's terminal summary (tests/parity_log.py).
 """
@@ -290,3 +294,134 @@ def test_bindings_route_to_qmha_solve_rect(dev):
         torch_ext.flash_solve_rect(t[0], t[1], t[2], d_model, h, "fa")
     with pytest.raises(RuntimeError, match="Nk >= Nq"):
         torch_ext.flash_solve_rect(t[1], t[0], t[0], d_model, h, causal=True)
+
+
+# ---- hard numerics: the rectangular kernels' own re-anchor (int8), rebase (fp16) and guards ---------------------
+# rect_ref.HARD_SHAPES; tests/test_rect_hard_cpu.py shows which branch each shape takes and that a
+# re-anchor / rebase without its rescale of l or of O is hundreds of times outside the bounds used here.
+@functools.lru_cache(maxsize=None)
+def hard_int8_reference(shape, d):
+    """(Q, K, V, O_ref in the kernels' base-2 arithmetic, per-element one-flip unit), computed once and shared."""
+    from oracle import oracle
+    c = cr.HARD[shape.name]
+    Q, K, V = rr.hard_inputs(shape.name, d, shape.Nq, shape.Nk)
+    ref, unit = rr.fa_int8(oracle, Q, K, V, c.h * d, c.h, causal=shape.causal, base2=True)
+    return Q, K, V, ref, cr.per_element(unit, d)
+
+
+@functools.lru_cache(maxsize=None)
+def hard_f16_reference(shape, d):
+    c = cr.HARD[shape.name]
+    Q, K, V = rr.hard_inputs(shape.name, d, shape.Nq, shape.Nk)
+    return Q, K, V, rr.fa_fp16_lazy(None, Q, K, V, c.h * d, c.h, causal=shape.causal)
+
+
+def hard_flip_tol(V):
+    """2^-10 max|V|: one flipped half(p) of a dominant key, the fp16 bound of the hard cases."""
+    return 2.0 ** -10 * float(np.abs(V).max())
+
+
+@pytest.mark.parametrize("shape,d", rr.HARD_INT8, ids=rr.hard_id)
+def test_int8_hard_shapes_vs_base2_restatement(dev, shape, d):
+    """Every element finite and within 2 u_r + 5e-5 of rect_ref.fa_int8(base2=True); `underflow` and V = 0 give exactly
+    0 from the reference and from the GPU; `nan_int8` (a NaN in the Q slice, two each in K and V) gives the
+    restatement's finite output."""
+    c = cr.HARD[shape.name]
+    flags = CAUSAL if shape.causal else 0
+    Q, K, V, ref, unit = hard_int8_reference(shape, d)
+    got = solve_rect(INT8, to_dev(dev, Q, K, V), c.h * d, c.h, flags)
+    assert_int8(f"hard {rr.hard_id(shape)} d{d}", got, ref, unit)
+    if shape.name == "underflow":
+        assert not ref.any() and not got.any()
+        assert not solve_rect(INT8, to_dev(dev, *rr.zero_v_hard_inputs(d, shape.Nq, shape.Nk)), c.h * d, c.h, flags).any()
+
+
+@pytest.mark.parametrize("shape,d", rr.HARD_F16, ids=rr.hard_id)
+def test_fp16_hard_shapes_vs_lazy_contract(dev, shape, d):
+    """Finite and within 2^-10 max|V| of rect_ref.fa_fp16_lazy; `underflow` and V = 0 give exactly 0.  The distance to
+    float64 is recorded only, for the reason given at tests/test_gpu_causal.py test_fp16_hard_cases_vs_lazy_contract."""
+    c = cr.HARD[shape.name]
+    flags = CAUSAL if shape.causal else 0
+    Q, K, V, ref = hard_f16_reference(shape, d)
+    got = solve_rect(F16, to_dev(dev, Q, K, V), c.h * d, c.h, flags)
+    label = f"hard {rr.hard_id(shape)} d{d}"
+    assert_f16(label, got, ref, hard_flip_tol(V))
+    if shape.name == "underflow":  # float64 has no m0 = 0 guard
+        assert not ref.any() and not got.any()
+        assert not solve_rect(F16, to_dev(dev, *rr.zero_v_hard_inputs(d, shape.Nq, shape.Nk)), c.h * d, c.h, flags).any()
+    else:
+        far = float(np.abs(got - rr.attention_f64(Q, K, V, c.h * d, c.h, shape.causal)).max())
+        parity_log.record(f"{label} (vs float64, recorded only)", F16 + "+r", far, 0.0, float("inf"))
+        print(f"{label}: max|gpu - float64| = {far:.2e} (recorded only)")
+
+
+@pytest.mark.parametrize("variant,shape,d", [(INT8,) + sd for sd in rr.HARD_INT8 if sd[0].causal]
+                         + [(F16,) + sd for sd in rr.HARD_F16 if sd[0].causal], ids=rr.hard_id)
+def test_hard_last_chunk_equals_the_square_causal_call(dev, variant, shape, d):
+    """A causal hard shape is the last chunk of the square hard problem at N = Nk: the rectangular call is held to the
+    last Nq rows of the GPU's own qmha_solve_opts(CAUSAL) at the variant's bound (whether they are bit-identical is
+    printed)."""
+    c = cr.HARD[shape.name]
+    sq = c.build(d, c.h, shape.Nk, c.B)
+    Q, K, V = rr.hard_inputs(shape.name, d, shape.Nq, shape.Nk)
+    assert np.array_equal(Q, sq[0][:, -shape.Nq:], equal_nan=True) and np.array_equal(K, sq[1], equal_nan=True)
+    got = solve_rect(variant, to_dev(dev, Q, K, V), c.h * d, c.h, CAUSAL)
+    square = solve_opts(variant, to_dev(dev, *sq), c.h * d, c.h, CAUSAL)[:, -shape.Nq:]
+    label = f"hard {rr.hard_id(shape)} d{d} (vs the square GPU call)"
+    print(f"{variant} {label}: {'is' if np.array_equal(got, square) else 'is NOT'} bit-identical"
+          f" (max difference {np.abs(got - square).max():.3e})")
+    assert np.isfinite(square).all()
+    if variant == INT8:
+        assert_int8(label, got, square.astype(np.float64), hard_int8_reference(shape, d)[4])
+    else:
+        assert_f16(label, got, square, hard_flip_tol(V))
+
+
+@pytest.mark.parametrize("variant,d", [(INT8, 32), (INT8, 64), (INT8, 128), (F16, 64), (F16, 128)])
+def test_rows_before_the_spike_tile_are_bit_identical(dev, variant, d):
+    """`spike_tile` (160, 256) causal: the query rows are rows 96..255 of the square problem and keys 160..191 one key
+    tile, so rows 0..63 (waves 0 and 1 of the first workgroup, which skip that tile's body) equal the run without
+    the spike bit for bit; every row from 64 on changes."""
+    c = cr.HARD["spike_tile"]
+    spike = solve_rect(variant, to_dev(dev, *rr.hard_inputs("spike_tile", d, 160, 256)), c.h * d, c.h, CAUSAL)
+    plain = solve_rect(variant, to_dev(dev, *rr.hard_inputs("spike_tile", d, 160, 256, spike=False)), c.h * d, c.h, CAUSAL)
+    assert np.array_equal(spike[:, :64], plain[:, :64])
+    assert (spike[:, 64:] != plain[:, 64:]).any(axis=-1).all()
+
+
+@pytest.mark.parametrize("variant,shape,d", [(INT8,) + sd for sd in rr.HARD_INT8] + [(F16,) + sd for sd in rr.HARD_F16],
+                         ids=rr.hard_id)
+def test_hard_shapes_repeat_and_split_by_batch(dev, variant, shape, d):
+    """A hard shape run twice is bit-identical (nqb >= 2: the second pass of an int8 q-block pair restarts from
+    anchor = 0, m = 0, l = 0 after the first re-anchored); each sequence of the B = 2 case equals its own B = 1 call."""
+    c = cr.HARD[shape.name]
+    flags = CAUSAL if shape.causal else 0
+    t = to_dev(dev, *rr.hard_inputs(shape.name, d, shape.Nq, shape.Nk))
+    a = solve_rect(variant, t, c.h * d, c.h, flags)
+    assert np.isfinite(a).all() and np.array_equal(a, solve_rect(variant, t, c.h * d, c.h, flags))
+    for b in range(c.B if c.B > 1 else 0):
+        one = solve_rect(variant, [x[b:b + 1].contiguous() for x in t], c.h * d, c.h, flags)
+        assert np.array_equal(one[0], a[b])
+
+
+@pytest.mark.parametrize("variant", [INT8, F16])
+@pytest.mark.parametrize("Nq,Nk,causal", [(96, 160, True), (160, 96, False)])
+def test_overlap_chunks_with_rectangular_slabs_are_bit_identical(dev, variant, Nq, Nk, causal):
+    """qmha_set_overlap_chunks(2 and 3) with B = 3 and Nq != Nk: every chunk boundary has b0 > 0, chunk c reads Q and
+    writes O at b0 Nq d_model and reads K, V and its workspace slice at b0 Nk ..., and the two slabs differ in both
+    directions over the two shapes.  Each run equals the unchunked call bit for bit, with the guard behind O intact."""
+    from quantizedmha_amd import _lib
+    lib = _lib.load()
+    B, d_model, h = 3, 128, 2
+    flags = CAUSAL if causal else 0
+    t = to_dev(dev, *rr.inputs(Nq, Nk, d_model, B, "normal", 560 + Nq))
+    prev = lib.qmha_set_overlap_chunks(1)
+    try:
+        want = solve_rect(variant, t, d_model, h, flags)
+        assert len({want[b].tobytes() for b in range(B)}) == B  # three different sequences: a mixed-up slab shows
+        for chunks in (2, 3):
+            lib.qmha_set_overlap_chunks(chunks)
+            for _ in range(2):
+                assert np.array_equal(solve_rect(variant, t, d_model, h, flags), want), (variant, chunks)
+    finally:
+        lib.qmha_set_overlap_chunks(prev)

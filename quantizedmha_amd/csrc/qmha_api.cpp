@@ -360,6 +360,7 @@ int run(const float* Q, const float* K, const float* V, float* O, int B, int Nq,
     const int D = d_model / h;
     const bool causal = flags & QMHA_FLAG_CAUSAL;  // check_flags passed: int8 / fp16 at a built head size
     const bool rect = Nq != N;
+    const bool masked = causal || rect;  // qmha_fa_masked.hip; plain square calls keep the non-causal main kernels
     bool prof;
     {
         std::lock_guard<std::mutex> lk(g_prof_mu);
@@ -372,7 +373,6 @@ int run(const float* Q, const float* K, const float* V, float* O, int B, int Nq,
     switch (variant) {
         case QMHA_FA_TC_INT8_B: {
             const qmha::Int8Workspace w8 = qmha::int8_carve(ws, B, N, h, D);
-            const auto launch_main = causal ? qmha::launch_fa_int8_causal_main : qmha::launch_fa_int8_main;
             st = run_chunked(
                 B, stream, slot, pre_m, main_m, "quant_int8 launch",
                 [&](Chunk c, hipStream_t s) {
@@ -385,14 +385,13 @@ int run(const float* Q, const float* K, const float* V, float* O, int B, int Nq,
                     const qmha::Int8Workspace w = int8_slice(w8, c.b0, N, h, D);
                     const float* q = Q + c.b0 * qslab;
                     float* o = O + c.b0 * qslab;
-                    return rect ? qmha::launch_fa_int8_rect_main(w, q, o, c.nb, Nq, N, h, D, d_model, causal, stream)
-                                : launch_main(w, q, o, c.nb, N, h, D, d_model, stream);
+                    return masked ? qmha::launch_fa_int8_masked_main(w, q, o, c.nb, Nq, N, h, D, d_model, causal, stream)
+                                  : qmha::launch_fa_int8_main(w, q, o, c.nb, N, h, D, d_model, stream);
                 });
             break;
         }
         case QMHA_FA_TC_V1A: {
             const qmha::F16Workspace w16 = qmha::f16_carve(ws, B, N, h, D);
-            const auto launch_main = causal ? qmha::launch_fa_f16_causal_main : qmha::launch_fa_f16_main;
             st = run_chunked(
                 B, stream, slot, pre_m, main_m, "convert_f16 launch",
                 [&](Chunk c, hipStream_t s) {
@@ -404,8 +403,8 @@ int run(const float* Q, const float* K, const float* V, float* O, int B, int Nq,
                     const qmha::F16Workspace w = f16_slice(w16, c.b0, N, h, D);
                     const float* q = Q + c.b0 * qslab;
                     float* o = O + c.b0 * qslab;
-                    return rect ? qmha::launch_fa_f16_rect_main(w, q, o, c.nb, Nq, N, h, D, d_model, causal, stream)
-                                : launch_main(w, q, o, c.nb, N, h, D, d_model, stream);
+                    return masked ? qmha::launch_fa_f16_masked_main(w, q, o, c.nb, Nq, N, h, D, d_model, causal, stream)
+                                  : qmha::launch_fa_f16_main(w, q, o, c.nb, N, h, D, d_model, stream);
                 });
             break;
         }

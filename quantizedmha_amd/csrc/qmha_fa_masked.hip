@@ -1,28 +1,52 @@
-// qmha_fa_rect.hip -- rectangular (Nq != Nk) main kernels of the int8 and fp16 fused attention paths for
-// gfx950 (MI355X): cross-attention and chunked prefill.  DESIGN.md section 11 is the contract.
+// qmha_fa_masked.hip -- the main kernels of the int8 and fp16 fused attention paths that visit a masked or
+// partial set of key tiles, for gfx950 (MI355X): square causal (is_causal=True) and
+// rectangular (Nq != Nk: cross-attention and chunked prefill).  One int8 and one fp16
+// kernel template; a compile-time geometry type (SquareCausal, Rect: below) supplies what differs.
 //
-// Q and O are [B, Nq, d_model], K and V [B, Nk, d_model]; Gq = Nq / 32 query groups, Gk = Nk / 32 key tiles.
-// The pre-pass touches K and V only and runs unchanged with N = Nk, so the kernels read the Ki / Vh / sK / sV
-// and Kh / Vt workspaces of the square paths.  Geometry and tile arithmetic are those of the causal kernels
-// (qmha_fa_causal.hip): one wave = one 32-row query group, a workgroup of 4 groups shares the LDS-DMA K/V
-// staging (stages of 2 key tiles, double-buffered), the tile bodies are repeated here statement for statement.
-//   Query rows, O rows and `active` follow Gq; the K/V bases, the buffer extents, the sK / sV index and the
-//   loop bounds follow Gk.
-//   diag_off (a kernel argument, wave-uniform, SGPR) is the one switch between the two modes, so each kernel
-//   has one instance per head size:
+// Square causal: query row r attends keys j <= r of its own sequence (Nq = Nk = N).  Both kernels keep the
+// geometry of the non-causal main kernels, so they consume the unchanged pre-pass outputs (qmha_prepass.hip):
+//   one wave = one 32-row query group g, a workgroup of 4 groups shares the LDS-DMA K/V staging
+//   (buffer_load ... lds, stages of 2 key tiles, double-buffered), tiles are 32 keys wide.
+//   group g visits key tiles t = 0..g; on the diagonal tile t == g a score with j > r is -inf BEFORE the
+//   row maximum is formed: no part in the row max, p = 0 exactly, nothing in the row sum, (int8) Pi = 0 and
+//   nothing in the P-tile absmax.
+//   The workgroup's KV loop ends at the stage that holds its last wave's diagonal tile; later stages are
+//   neither staged nor computed.  A wave whose diagonal lies earlier keeps taking part in every barrier
+//   and every DMA issue and skips the tile body under a wave-uniform branch (it adds exactly zero).
+//   The mask is one select per score under a wave-uniform branch taken on the diagonal tile only, so
+//   off-diagonal tiles execute no mask instructions.  (A separate compile-time instantiation of the whole
+//   tile body for the diagonal doubled the unrolled loop body and spilled -- fp16 d = 64: 221 VGPRs to
+//   scratch at the 4-waves-per-SIMD budget -- so the tile body exists once.)
+//   Workgroup cost grows with the q-block index.  fp16: the launch index maps the largest q-blocks of every
+//   (b, h) first.  int8: a workgroup runs a PAIR of q-blocks one after the other,
+//   nqb - 1 - i and its mirror i: every workgroup of a head then costs the same nqb + 1 units, whatever
+//   compute unit it lands on (with heaviest-first single q-blocks, a grid that is resident all at once --
+//   B1 H32 N8192 d32 -- ended 1.5x later than its mean: DESIGN.md 10).  The pairs with the largest
+//   q-blocks start first; xcd_remap keeps the pairs of one (b, h) in one XCD's L2.
+// Rectangular: Q and O are [B, Nq, d_model], K and V [B, Nk, d_model]; Gq = Nq / 32 query groups, Gk = Nk / 32
+// key tiles.  The pre-pass touches K and V only and runs unchanged with N = Nk.  Query rows, O rows and `active`
+// follow Gq; the K/V bases, the buffer extents, the sK / sV index and the loop bounds follow Gk.
+//   diag_off (run-time, wave-uniform, SGPR) is the one switch between the two modes, so each kernel has one
+//   rectangular instance per head size:
 //     causal, bottom-right aligned (row r attends keys j <= r + Nk - Nq, Nk >= Nq): diag_off = Gk - Gq.  The
 //       32-row K/V groups are aligned to the tile grid and Nk - Nq is a multiple of 32, so group g's diagonal
-//       tile is exactly key tile g + diag_off and the in-tile mask is the causal kernels' (j > r inside the
-//       tile, -inf BEFORE the row maximum is formed); tiles past the diagonal are not visited.
+//       tile is exactly key tile g + diag_off and the in-tile mask is the square one (j > r inside the tile);
+//       tiles past the diagonal are not visited.
 //     non-causal: diag_off = Gk, a diagonal no tile reaches (t <= Gk - 1 < g + Gk): every wave runs all Gk
 //       tiles and never takes the mask branch.
 //   A wave's last tile is min(g + diag_off, Gk - 1); the workgroup's KV loop ends at the stage holding the last
-//   tile of its last active wave, and the partial last stage brings in that many tiles only.
-//   Balance as in the causal kernels: int8 runs mirrored q-block pairs (with an offset every workgroup of a
-//   head still costs the same; without the mask both passes cost Gk tiles), fp16 single q-blocks, heaviest first.
+//   tile of its last active wave, and the partial last stage brings in that many tiles only.  With an offset
+//   every int8 workgroup of a head still costs the same; without the mask both passes cost Gk tiles.
 // Out of range by construction: K/V reads go through buffer descriptors of exactly the (b, h) slice
 // (Nk * D, Nk * 2D bytes) and a stage issues whole tiles t <= Gk - 1 only; sK / sV are read at t <= Gk - 1
 // of slice bh * Gk; Q and O rows are touched by active waves (g < Gq) only.
+//
+// int8 (fa_tc_int8_b contract): the tile of qmha_fa_int8_kernel -- i8 MFMA for Q@K^T, exact-integer f16
+//   MFMA for P@V, one sP per 32x32 tile, the anchored O / l state -- on the Ki / Vh / sK / sV workspace.
+// fp16 (fa_tc_v1a contract): the tile of qmha_fa_f16_v3_kernel -- v_mfma_f32_16x16x32_f16 for both
+//   products, the lazy base of DESIGN.md 3 -- on the Kh / Vt workspace.
+// Both are unpipelined (one tile at a time, co-resident waves interleave); N = 32 is the same kernel
+// (one stage, one diagonal tile).
 #include "qmha_common.hpp"
 #include "qmha_kernels.hpp"
 
@@ -30,27 +54,55 @@
 
 namespace qmha {
 
-static constexpr float kRectLazySumCapC = 4096.0f;  // the fp16 lazy base's cap
-constexpr int kRectWaves = 4, kRectSG = 2;
+static constexpr float kLazySumCapC = 4096.0f;  // the fp16 lazy base's cap
+constexpr int kWaves = 4, kSG = 2;
 
-// launch index -> (bh, q-block) as the causal kernels map it: fp16 one q-block per workgroup, the largest
-// first; int8 the pair nqb - 1 - pi and its mirror pi
-__host__ __device__ constexpr int rect_pairs(int nqb) { return (nqb + 1) / 2; }
-__device__ __forceinline__ void rect_wg_single(int nqb, int& bh, int& qb) {
+// The geometry of a launch, a kernel argument: the rows of Q / O and of K / V, and which key tiles query
+// group g visits -- tiles t <= last(g), masked on tile diag(g).
+// Square causal: the diagonal of group g is tile g, which is also its last; nothing beyond N is passed or
+// computed, so these instances carry no offset and no clamp.
+struct SquareCausal {
+    int N;
+    __device__ int nq() const { return N; }
+    __device__ int nk() const { return N; }
+    __device__ int gk() const { return N / QMHA_GROUP; }
+    __device__ int diag(int g) const { return g; }
+    __device__ int last(int g) const { return g; }
+};
+// Rectangular.  causal: bottom-right aligned, diag_off = Gk - Gq (Nk >= Nq, checked by the launchers);
+// else diag_off = Gk, a diagonal no tile reaches
+struct Rect {
+    int Nq, Nk, diag_off;
+    Rect(int nq, int nk, bool causal) : Nq(nq), Nk(nk), diag_off(nk / QMHA_GROUP - (causal ? nq / QMHA_GROUP : 0)) {}
+    __device__ int nq() const { return Nq; }
+    __device__ int nk() const { return Nk; }
+    __device__ int gk() const { return Nk / QMHA_GROUP; }
+    __device__ int diag(int g) const { return g + diag_off; }  // >= Gk: none
+    __device__ int last(int g) const { return min(g + diag_off, gk() - 1); }
+};
+
+// Launch index -> (bh, q-block pair): a workgroup runs q-block nqb - 1 - pi and then its mirror pi, so every
+// workgroup of a head costs the same nqb + 1 q-block units (the middle q-block of an odd nqb runs alone);
+// consecutive indices of an XCD share (b, h), and the pairs holding the largest q-blocks start first.
+// (int8 kernel.  The fp16 kernel keeps one q-block per workgroup, heaviest first -- masked_wg_single: with the
+// pair loop around it its d = 64 instance no longer fits the 128 VGPRs of four waves per SIMD, 4 spilled, and
+// it has no grid that is resident all at once among the measured shapes.)
+__host__ __device__ constexpr int masked_pairs(int nqb) { return (nqb + 1) / 2; }
+__device__ __forceinline__ void masked_wg_single(int nqb, int& bh, int& qb) {
     const int wg = xcd_remap(blockIdx.x, gridDim.x);
     bh = wg / nqb;
     qb = nqb - 1 - wg % nqb;
 }
-__device__ __forceinline__ void rect_wg(int nqb, int& bh, int& pi) {
+__device__ __forceinline__ void masked_wg(int nqb, int& bh, int& pi) {
     const int wg = xcd_remap(blockIdx.x, gridDim.x);
-    bh = wg / rect_pairs(nqb);
-    pi = wg % rect_pairs(nqb);
+    bh = wg / masked_pairs(nqb);
+    pi = wg % masked_pairs(nqb);
 }
 
 // K/V staging of both kernels: fixed per-lane source offsets (the LDS image's swizzle applied to the
 // source address by the kernel that fills koff / voff), the stage offset in soffset.
 template <int WAVES, int KCH, int VCH, int KBYTES, int VBYTES, int SG>
-struct RectStager {
+struct MaskedStager {
     static constexpr int KJ = (KCH / 64 + WAVES - 1) / WAVES, VJ = (VCH / 64 + WAVES - 1) / WAVES;
     int koff[KJ], voff[VJ];
     // ngr: tiles of the stage to bring in (1..SG, wave-uniform)
@@ -73,26 +125,27 @@ struct RectStager {
 
 // ---------------------------------------------------------------------------------------
 // int8: 32x32 accumulator map.  Lane (col, half) holds S^T[acc_row(r, half)][col], r = 0..15: query
-// row `col` of the group against key acc_row(r, half) of the tile; on the diagonal tile the score of
-// register r is masked when acc_row(r, half) > col.
+// row `col` of the group against key acc_row(r, half) of the tile, so on the diagonal tile (the groups of
+// queries and keys aligned) the score of register r is masked when acc_row(r, half) > col.
 // ---------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(kRectWaves * 64, D > 64 ? 2 : 4) void qmha_fa_int8_rect_kernel(
+template <int D, class Geo>
+__global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_int8_masked_kernel(
     const float* __restrict__ Qf, const int8_t* __restrict__ Ki, const _Float16* __restrict__ Vh,
-    const float* __restrict__ sK, const float* __restrict__ sV, float* __restrict__ O, int Nq, int Nk, int H,
-    int d_model, int nqb, int diag_off, float c_log2) {
-    constexpr int WAVES = kRectWaves, SG = kRectSG;
+    const float* __restrict__ sK, const float* __restrict__ sV, float* __restrict__ O, Geo geo, int H, int d_model,
+    int nqb, float c_log2) {
+    constexpr int WAVES = kWaves, SG = kSG;
     constexpr int KS = D / 32;               // i8 MFMA k-steps (QK) and d-blocks (PV)
     constexpr int KBYTES = SG * 32 * D;      // K int8 per stage
     constexpr int VBYTES = SG * 32 * D * 2;  // V f16 per stage
     constexpr int KCH = KBYTES / 16, VCH = VBYTES / 16;
-    static_assert(D == 32 || D == 64 || D == 128, "rect int8: d in {32, 64, 128}");
+    static_assert(D == 32 || D == 64 || D == 128, "masked int8: d in {32, 64, 128}");
     static_assert(KCH % 64 == 0 && VCH % 64 == 0 && (KCH / SG) % 64 == 0, "whole KiB LDS-DMA pieces");
     __shared__ __attribute__((aligned(16))) char lds[2][KBYTES + VBYTES];
 
-    const int Gq = Nq / QMHA_GROUP, Gk = Nk / QMHA_GROUP;
+    const int Nq = geo.nq(), Nk = geo.nk();
+    const int Gq = Nq / QMHA_GROUP, Gk = geo.gk();
     int bh, pi;
-    rect_wg(nqb, bh, pi);
+    masked_wg(nqb, bh, pi);
     const int b = bh / H, k = bh % H;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -104,10 +157,10 @@ __global__ __launch_bounds__(kRectWaves * 64, D > 64 ? 2 : 4) void qmha_fa_int8_
     const int qg = qb * WAVES + wave;
     const bool active = qg < Gq;  // wave-uniform; an inactive wave still stages and syncs
     // the workgroup's last tile: that of its last active wave
-    const int wg_last = min(min(qb * WAVES + WAVES - 1, Gq - 1) + diag_off, Gk - 1);
+    const int wg_last = geo.last(min(qb * WAVES + WAVES - 1, Gq - 1));
     const int nst = wg_last / SG + 1;
-    const int my_diag = qg + diag_off;                       // this wave's diagonal tile (>= Gk: none)
-    const int my_last = active ? min(my_diag, Gk - 1) : -1;  // this wave computes tiles t <= my_last
+    const int my_diag = geo.diag(qg);              // this wave's diagonal tile
+    const int my_last = active ? geo.last(qg) : -1;  // this wave computes tiles t <= my_last
 
     // in-register Q quantisation (fa_tc_int8_b.cu:33-152) into the Q^T operand: lane (col, half) holds
     // bytes [32 s + 16 half, +16) of query row col for every k-step s
@@ -156,7 +209,7 @@ __global__ __launch_bounds__(kRectWaves * 64, D > 64 ? 2 : 4) void qmha_fa_int8_
     const float* skb = sK + (size_t)bh * Gk;
     const float* svb = sV + (size_t)bh * Gk;
 
-    RectStager<WAVES, KCH, VCH, KBYTES, VBYTES, SG> stg;
+    MaskedStager<WAVES, KCH, VCH, KBYTES, VBYTES, SG> stg;
 #pragma unroll
     for (int jj = 0; jj < stg.KJ; ++jj) {
         const int idx = (wave + jj * WAVES) * 64 + lane;
@@ -211,8 +264,10 @@ __global__ __launch_bounds__(kRectWaves * 64, D > 64 ? 2 : 4) void qmha_fa_int8_
         float p[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) p[r] = __builtin_amdgcn_exp2f(fmaf(sf[r], c, -m_new));  // masked: exp2(-inf) = 0
-        // Pi = rint(p/sP) (0..127) carried as the f16 subnormal Pi * 2^-24 (qmha_fa_causal.hip): P@V then
-        // yields T * 2^-24 exactly and the O scale carries the 2^24 back
+        // Pi = rint(p/sP) (0..127), carried as the f16 subnormal Pi * 2^-24 as in qmha_fa_int8_pipe_kernel:
+        // fma(p, 1/sP, 1.5 * 2^23) rounds half-even to an integer whose float bits end in Pi, and those low
+        // 16 bits are the f16 encoding of Pi * 2^-24; one byte permute packs two entries.  P@V then yields
+        // T * 2^-24 exactly (T < 2^20) and the O scale carries the 2^24 back.
         v8h pop[2];
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
@@ -222,10 +277,10 @@ __global__ __launch_bounds__(kRectWaves * 64, D > 64 ? 2 : 4) void qmha_fa_int8_
             pop[r >> 3][(r & 7) + 1] = h2[1];
         }
         // row sum of the unquantised p (:336) over this lane's 16 keys; the two halves of l are joined once,
-        // in the epilogue
+        // in the epilogue (every factor l takes below is the same in both halves of a row)
         const float rs = tree_sum16(p);
-        // anchored running state: o += T*sP*sV*2^(m_t - anchor), l_run += rowsum*2^(m_t - anchor);
-        // re-anchor before the shift is formed
+        // anchored running state, as qmha_fa_int8_kernel: o += T*sP*sV*2^(m_t - anchor),
+        // l_run += rowsum*2^(m_t - anchor); re-anchor before the shift is formed
         if (__builtin_amdgcn_ballot_w64(m_new - anchor > 48.0f)) {
             const float f = __builtin_amdgcn_exp2f(anchor - m_new);
 #pragma unroll
@@ -300,36 +355,37 @@ __global__ __launch_bounds__(kRectWaves * 64, D > 64 ? 2 : 4) void qmha_fa_int8_
 // qb, S^T[kap16(kb, 4 grp + i)][16 qb + r16] (kb = 0, 1, i = 0..3): on the diagonal tile that score
 // is masked when kap16(kb, 4 grp + i) > 16 qb + r16.
 // ---------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(kRectWaves * 64, D > 64 ? 2 : 4) void qmha_fa_f16_rect_kernel(
+template <int D, class Geo>
+__global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_f16_masked_kernel(
     const float* __restrict__ Qf, const _Float16* __restrict__ Kh, const _Float16* __restrict__ Vt,
-    float* __restrict__ O, int Nq, int Nk, int H, int d_model, int nqb, int diag_off, float c_log2) {
+    float* __restrict__ O, Geo geo, int H, int d_model, int nqb, float c_log2) {
     QMHA_ENABLE_AGPR_MFMA();
     asm volatile("" : "+v"(c_log2));  // a VOP3 fma reading an SGPR issues at the slow rate
-    constexpr int WAVES = kRectWaves, SG = kRectSG;
+    constexpr int WAVES = kWaves, SG = kSG;
     constexpr int KS = D / 32;            // QK k-steps (K = 32)
     constexpr int DB = D / 16;            // PV d-blocks of 16 rows
     constexpr int RB = 2 * D;             // K row bytes
     constexpr int KBYTES = SG * 32 * RB;  // K per stage
     constexpr int VBYTES = SG * 32 * D * 2;
     constexpr int KCH = KBYTES / 16, VCH = VBYTES / 16;
-    static_assert(D == 64 || D == 128, "rect fp16: d in {64, 128}");
+    static_assert(D == 64 || D == 128, "masked fp16: d in {64, 128}");
     static_assert(KCH % 64 == 0 && VCH % 64 == 0 && (KCH / SG) % 64 == 0, "whole KiB LDS-DMA pieces");
     __shared__ __attribute__((aligned(16))) char lds[2][KBYTES + VBYTES];
 
-    const int Gq = Nq / QMHA_GROUP, Gk = Nk / QMHA_GROUP;
+    const int Nq = geo.nq(), Nk = geo.nk();
+    const int Gq = Nq / QMHA_GROUP;
     int bh, qb0;
-    rect_wg_single(nqb, bh, qb0);
+    masked_wg_single(nqb, bh, qb0);
     const int b = bh / H, k = bh % H;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int qg = qb0 * WAVES + wave;
     const bool active = qg < Gq;
     const int grp = lane >> 4, r16 = lane & 15;
-    const int wg_last = min(min(qb0 * WAVES + WAVES - 1, Gq - 1) + diag_off, Gk - 1);  // of the last active wave
+    const int wg_last = geo.last(min(qb0 * WAVES + WAVES - 1, Gq - 1));  // of the last active wave
     const int nst = wg_last / SG + 1;
-    const int my_diag = qg + diag_off;  // this wave's diagonal tile (>= Gk: none)
-    const int my_last = active ? min(my_diag, Gk - 1) : -1;
+    const int my_diag = geo.diag(qg);  // this wave's diagonal tile
+    const int my_last = active ? geo.last(qg) : -1;
 
     // Q converted in-kernel (RNE) into the QK B operand: query 16 qb + r16, d = 32 ks + 8 grp .. +7
     v8h qop[2][KS];
@@ -359,7 +415,7 @@ __global__ __launch_bounds__(kRectWaves * 64, D > 64 ? 2 : 4) void qmha_fa_f16_r
     const char* kbase = reinterpret_cast<const char*>(Kh + (size_t)bh * Nk * D);
     const char* vbase = reinterpret_cast<const char*>(Vt + (size_t)bh * Nk * D);
 
-    RectStager<WAVES, KCH, VCH, KBYTES, VBYTES, SG> stg;
+    MaskedStager<WAVES, KCH, VCH, KBYTES, VBYTES, SG> stg;
 #pragma unroll
     for (int jj = 0; jj < stg.KJ; ++jj) {
         const int idx = (wave + jj * WAVES) * 64 + lane;
@@ -427,8 +483,8 @@ __global__ __launch_bounds__(kRectWaves * 64, D > 64 ? 2 : 4) void qmha_fa_f16_r
             }
         };
         softmax_p();
-        const uint64_t over0 = __builtin_amdgcn_ballot_w64(ts[0] > kRectLazySumCapC);
-        const uint64_t over1 = __builtin_amdgcn_ballot_w64(ts[1] > kRectLazySumCapC);
+        const uint64_t over0 = __builtin_amdgcn_ballot_w64(ts[0] > kLazySumCapC);
+        const uint64_t over1 = __builtin_amdgcn_ballot_w64(ts[1] > kLazySumCapC);
         if (over0 | over1) {  // rare (wave-uniform): rebase the queries with a key quarter above the cap
 #pragma unroll
             for (int qb = 0; qb < 2; ++qb) {
@@ -506,55 +562,50 @@ __global__ __launch_bounds__(kRectWaves * 64, D > 64 ? 2 : 4) void qmha_fa_f16_r
 }
 
 // ---------------------------------------------------------------------------------------
-// host launchers.  causal: bottom-right aligned, diag_off = Gk - Gq (Nk >= Nq, checked by the C ABI);
-// else diag_off = Gk, a diagonal no tile reaches
+// host launchers: square causal calls take the SquareCausal instances, everything else the Rect ones
 // ---------------------------------------------------------------------------------------
-static int rect_diag_off(int Nq, int Nk, bool causal) {
-    const int Gq = Nq / QMHA_GROUP, Gk = Nk / QMHA_GROUP;
-    return causal ? Gk - Gq : Gk;
+static bool masked_shape_ok(int Nq, int Nk, bool causal) {
+    return Nq >= QMHA_GROUP && Nk >= QMHA_GROUP && Nq % QMHA_GROUP == 0 && Nk % QMHA_GROUP == 0 && !(causal && Nk < Nq);
 }
+static int masked_nqb(int Nq) { return (Nq / QMHA_GROUP + kWaves - 1) / kWaves; }
 
-template <int D>
-static hipError_t fa_int8_rect_launch(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H,
+hipError_t launch_fa_int8_masked_main(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
                                       int d_model, bool causal, hipStream_t stream) {
-    const int Gq = Nq / QMHA_GROUP, nqb = (Gq + kRectWaves - 1) / kRectWaves;
-    const float c_log2 = softmax_scale_log2(D);
-    hipLaunchKernelGGL((qmha_fa_int8_rect_kernel<D>), dim3(B * H * rect_pairs(nqb)), dim3(kRectWaves * 64), 0, stream, Qf,
-                       w.Ki, w.Vh, w.sK, w.sV, O, Nq, Nk, H, d_model, nqb, rect_diag_off(Nq, Nk, causal), c_log2);
-    return hipGetLastError();
+    if (!masked_shape_ok(Nq, Nk, causal)) return hipErrorInvalidValue;
+    const int nqb = masked_nqb(Nq);
+    auto launch = [&](auto geo, auto d) {
+        hipLaunchKernelGGL((qmha_fa_int8_masked_kernel<decltype(d)::value, decltype(geo)>), dim3(B * H * masked_pairs(nqb)), dim3(kWaves * 64),
+                           0, stream, Qf, w.Ki, w.Vh, w.sK, w.sV, O, geo, H, d_model, nqb, softmax_scale_log2(D));
+        return hipGetLastError();
+    };
+    auto by_d = [&](auto geo) {
+        switch (D) {
+            case 32: return launch(geo, std::integral_constant<int, 32>{});
+            case 64: return launch(geo, std::integral_constant<int, 64>{});
+            case 128: return launch(geo, std::integral_constant<int, 128>{});
+            default: return hipErrorInvalidValue;
+        }
+    };
+    return causal && Nq == Nk ? by_d(SquareCausal{Nq}) : by_d(Rect(Nq, Nk, causal));
 }
 
-hipError_t launch_fa_int8_rect_main(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
-                                    int d_model, bool causal, hipStream_t stream) {
-    if (Nq < QMHA_GROUP || Nk < QMHA_GROUP || Nq % QMHA_GROUP || Nk % QMHA_GROUP || (causal && Nk < Nq))
-        return hipErrorInvalidValue;
-    switch (D) {
-        case 32: return fa_int8_rect_launch<32>(w, Qf, O, B, Nq, Nk, H, d_model, causal, stream);
-        case 64: return fa_int8_rect_launch<64>(w, Qf, O, B, Nq, Nk, H, d_model, causal, stream);
-        case 128: return fa_int8_rect_launch<128>(w, Qf, O, B, Nq, Nk, H, d_model, causal, stream);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-template <int D>
-static hipError_t fa_f16_rect_launch(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H,
+hipError_t launch_fa_f16_masked_main(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
                                      int d_model, bool causal, hipStream_t stream) {
-    const int Gq = Nq / QMHA_GROUP, nqb = (Gq + kRectWaves - 1) / kRectWaves;
-    const float c_log2 = softmax_scale_log2(D);
-    hipLaunchKernelGGL((qmha_fa_f16_rect_kernel<D>), dim3(B * H * nqb), dim3(kRectWaves * 64), 0, stream, Qf, w.Kh, w.Vt,
-                       O, Nq, Nk, H, d_model, nqb, rect_diag_off(Nq, Nk, causal), c_log2);
-    return hipGetLastError();
-}
-
-hipError_t launch_fa_f16_rect_main(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
-                                   int d_model, bool causal, hipStream_t stream) {
-    if (Nq < QMHA_GROUP || Nk < QMHA_GROUP || Nq % QMHA_GROUP || Nk % QMHA_GROUP || (causal && Nk < Nq))
-        return hipErrorInvalidValue;
-    switch (D) {
-        case 64: return fa_f16_rect_launch<64>(w, Qf, O, B, Nq, Nk, H, d_model, causal, stream);
-        case 128: return fa_f16_rect_launch<128>(w, Qf, O, B, Nq, Nk, H, d_model, causal, stream);
-        default: return hipErrorInvalidValue;
-    }
+    if (!masked_shape_ok(Nq, Nk, causal)) return hipErrorInvalidValue;
+    const int nqb = masked_nqb(Nq);
+    auto launch = [&](auto geo, auto d) {
+        hipLaunchKernelGGL((qmha_fa_f16_masked_kernel<decltype(d)::value, decltype(geo)>), dim3(B * H * nqb), dim3(kWaves * 64), 0, stream,
+                           Qf, w.Kh, w.Vt, O, geo, H, d_model, nqb, softmax_scale_log2(D));
+        return hipGetLastError();
+    };
+    auto by_d = [&](auto geo) {
+        switch (D) {
+            case 64: return launch(geo, std::integral_constant<int, 64>{});
+            case 128: return launch(geo, std::integral_constant<int, 128>{});
+            default: return hipErrorInvalidValue;
+        }
+    };
+    return causal && Nq == Nk ? by_d(SquareCausal{Nq}) : by_d(Rect(Nq, Nk, causal));
 }
 
 }  // namespace qmha

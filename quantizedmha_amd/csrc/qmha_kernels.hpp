@@ -138,23 +138,15 @@ hipError_t launch_convert_f16(const float* Q, const float* K, const float* V, co
 hipError_t launch_fa_f16_main(const F16Workspace& w, const float* Qf, float* O, int B, int N, int H, int D, int d_model,
                               hipStream_t stream);
 
-// ---- causal main kernels (qmha_fa_causal.hip) ---------------------------------
-// the same workspaces as the non-causal paths (the pre-pass is unchanged); query row r attends keys
-// j <= r.  int8: d in {32, 64, 128}; fp16: d in {64, 128} (qmha_api.cpp's variant table); other d:
-// hipErrorInvalidValue
-hipError_t launch_fa_int8_causal_main(const Int8Workspace& w, const float* Qf, float* O, int B, int N, int H, int D,
-                                      int d_model, hipStream_t stream);
-hipError_t launch_fa_f16_causal_main(const F16Workspace& w, const float* Qf, float* O, int B, int N, int H, int D,
-                                     int d_model, hipStream_t stream);
-
-// ---- rectangular main kernels (qmha_fa_rect.hip) -------------------------------
-// Q / O of Nq rows against a workspace pre-passed with N = Nk; causal: bottom-right aligned (row r attends
-// keys j <= r + Nk - Nq, Nk >= Nq).  Nq, Nk multiples of 32; head sizes as the causal kernels; anything
-// else: hipErrorInvalidValue
-hipError_t launch_fa_int8_rect_main(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
-                                    int d_model, bool causal, hipStream_t stream);
-hipError_t launch_fa_f16_rect_main(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
-                                   int d_model, bool causal, hipStream_t stream);
+// ---- causal and rectangular main kernels (qmha_fa_masked.hip) ---------------
+// the same workspaces as the non-causal paths (the pre-pass is unchanged, run with N = Nk); Q / O have Nq rows.
+// causal: bottom-right aligned (row r attends keys j <= r + Nk - Nq, Nk >= Nq; Nq == Nk: j <= r, the square
+// causal instances).  Nq, Nk multiples of 32; int8: d in {32, 64, 128}; fp16: d in {64, 128} (qmha_api.cpp's
+// variant table); anything else: hipErrorInvalidValue
+hipError_t launch_fa_int8_masked_main(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H,
+                                      int D, int d_model, bool causal, hipStream_t stream);
+hipError_t launch_fa_f16_masked_main(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
+                                     int d_model, bool causal, hipStream_t stream);
 
 // ---- FP32 (fa: scalar VALU kernel; fa_mfma: the same contract on v_mfma_f32_32x32x2_f32) -----
 hipError_t launch_fa_f32(const float* Q, const float* K, const float* V, float* O, int B, int N, int H, int D,

@@ -83,7 +83,7 @@ def fa_int8(oracle, Q, K, V, d_model, h, causal=False, base2=False, _mutant=None
     """fa_tc_int8_b's intended per-block algorithm; returns (O like Q, u [B, N, h] one-flip units, Rise).
 
     base2=False is the C oracle's score arithmetic in nats, exp((acc sQ sK) / sqrt(d) - m).  base2=True is the
-    causal kernel's (qmha_fa_causal.hip:201-220): c = (sQ c_log2) sK with the host's c_log2, m_new =
+    causal kernel's (qmha_fa_masked.hip:247-266): c = (sQ c_log2) sK with the host's c_log2, m_new =
     max(m, mx c), p = exp2(fma(s, c, -m_new)), alpha = exp2(m - m_new); everything else is unchanged.  At scores
     of 50..200 log2 units the two forms differ by ~1e-5 in the exponent, enough to flip a Pi.
     Rise.log2[b, r, k] is the largest rise of row r's running max over one tile in log2 units (the kernel

@@ -174,8 +174,8 @@ def test_slot_permutations_are_bijective():
 
 def test_production_library_has_one_kernel_per_variant_and_d(built):
     """No tuning/ablation alternates in the shipped libqmha.so (round-1 ADVICE): every kernel
-    template is instantiated at most once per head size, and no QMHA_*_CFG / overlap
-    environment switch exists (those live in QMHA_ABLATION builds only)."""
+    template is instantiated at most once per head size (the masked kernels: once per geometry), and no
+    QMHA_*_CFG / overlap environment switch exists (those live in QMHA_ABLATION builds only)."""
     path = os.path.join(LIB_DIR, "libqmha.so")
     syms = subprocess.run(["nm", path], capture_output=True, text=True, check=True).stdout
     stubs = set(re.findall(r"__device_stub__(\w+?)ILi(\d+)E(\w*)", syms))
@@ -190,6 +190,9 @@ def test_production_library_has_one_kernel_per_variant_and_d(built):
                 continue
             per.setdefault((name, d), set()).add(rest)
             continue
+        if name in ("qmha_fa_int8_masked_kernel", "qmha_fa_f16_masked_kernel"):  # <D, geometry>
+            # the square causal and the rectangular kernel are two kernels of one template: one instance of each
+            name += "[%s]" % re.match(r"NS_\d+([A-Za-z]+?)E", rest).group(1)
         if name == "qmha_fa_int8_pipe_kernel":  # <D, WAVES, FL>
             m, fl = re.match(r"Li(\d+)ELi(\d+)E", rest), 2
         elif name == "qmha_fa_int8_kernel":  # <D, FL> (the one-tile kernel: N = 32, and d outside 32/64/128)

@@ -1,5 +1,6 @@
 """CPU tests of the rectangular hard cases: rect_ref.HARD_SHAPES cut causal_ref's hard inputs to
-rectangles that drive qmha_fa_rect.hip's int8 re-anchor, its fp16 rebase and its guards, with and without the mask.
+rectangles that drive the int8 re-anchor, the fp16 rebase and the guards of qmha_fa_masked.hip's rectangular
+instances, with and without the mask.
 
 Held here, with no kernel launched:
   * every shape reaches the branch it is listed for -- counts asserted exactly where the input's construction

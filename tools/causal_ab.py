@@ -24,8 +24,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 # the shipped query groups per workgroup, read from the kernel source
-with open(os.path.join(ROOT, "quantizedmha_amd", "csrc", "qmha_fa_causal.hip")) as _f:
-    CAUSAL_WAVES = int(re.search(r"constexpr int kCausalWaves = (\d+)", _f.read()).group(1))
+with open(os.path.join(ROOT, "quantizedmha_amd", "csrc", "qmha_fa_masked.hip")) as _f:
+    CAUSAL_WAVES = int(re.search(r"constexpr int kWaves = (\d+)", _f.read()).group(1))
 
 
 def tile_ratio(N, waves=CAUSAL_WAVES):
@@ -92,7 +92,7 @@ def main():
     R = tile_ratio(a.N)
     ratio = med[1][0] / med[0][0]
     ids = bench.isa_ids(a.variant, a.d)
-    ckern = ("qmha_fa_int8_causal_kernelILi%dE" if a.variant == "fa_tc_int8_b" else "qmha_fa_f16_causal_kernelILi%dE") % a.d
+    ckern = "qmha_fa_%s_masked_kernelILi%dENS_12SquareCausalE" % ("int8" if a.variant == "fa_tc_int8_b" else "f16", a.d)
     res = {
         "tool": "causal_ab", "variant": a.variant, "B": a.B, "H": a.H, "N": a.N, "d": a.d,
         "rounds": a.rounds, "calls_per_round": a.calls,

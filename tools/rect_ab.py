@@ -27,8 +27,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 # the shipped query groups per workgroup, read from the kernel source
-with open(os.path.join(ROOT, "quantizedmha_amd", "csrc", "qmha_fa_rect.hip")) as _f:
-    RECT_WAVES = int(re.search(r"constexpr int kRectWaves = (\d+)", _f.read()).group(1))
+with open(os.path.join(ROOT, "quantizedmha_amd", "csrc", "qmha_fa_masked.hip")) as _f:
+    RECT_WAVES = int(re.search(r"constexpr int kWaves = (\d+)", _f.read()).group(1))
 
 
 def tiles(Nq, Nk, causal, waves=RECT_WAVES):
@@ -113,7 +113,7 @@ def main():
     ratio = med[1][0] / med[0][0]
     ids = bench.isa_ids(a.variant, a.d)
     stem = "int8" if a.variant == "fa_tc_int8_b" else "f16"
-    ref_main = isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_causal_kernelILi{a.d}E") if a.causal else \
+    ref_main = isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_masked_kernelILi{a.d}ENS_12SquareCausalE") if a.causal else \
         ids.get("main", {}).get("isa_sha16")
     res = {
         "tool": "rect_ab", "variant": a.variant, "B": a.B, "H": a.H, "Nq": a.Nq, "Nk": a.Nk, "d": a.d, "causal": a.causal,
@@ -127,7 +127,7 @@ def main():
         "rect_waves": RECT_WAVES, "R": round(R, 4), "bound_1p2R": round(1.2 * R, 4), "within_bound": ratio <= 1.2 * R,
         "clock_probe": bench.clock_probe(dev),
         "isa_sha16": {"square_main": ref_main, "prepass": ids.get("prepass", {}).get("isa_sha16"),
-                      "rect_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_rect_kernelILi{a.d}E")},
+                      "rect_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_masked_kernelILi{a.d}ENS_4RectE")},
         "device": torch.cuda.get_device_properties(dev).name,
     }
     print(json.dumps(res))

@@ -161,6 +161,25 @@ int qmha_debug_fa_int8_dump(const float *Q, const float *K, const float *V, floa
 int qmha_debug_fa_int8_pt_dump(const float *Q, const float *K, const float *V, float *O, int B, int N, int d_model,
                                int h, int32_t *S, int8_t *Qi, float *sQ);
 
+/*
+ * Test hook: the P stage of the per-block int8 path (QMHA_FA_TC_INT8_B), tile by tile.  Takes Nq, Nk and flags
+ * as qmha_solve_rect and launches the dumping twin of whichever main kernel that call would launch (the
+ * pipelined kernel, the one-tile kernel -- N = 32 included --, or the causal / rectangular kernel), which
+ * writes O as in production and, for every tile a wave computes (Gq = Nq/32, Gk = Nk/32, key tile t):
+ *   S  [B*h][Nq][Nk]    int32  Qi Ki^T as the MFMAs produced it, before the causal mask
+ *   Qi [B*h][Nq][d]     int8   the in-register Q operand;  sQ [B*h][Gq] its group scales
+ *   m  [B*h][Nq][Gk]    fp32   the row's running max after tile t (log2 units)
+ *   sP [B*h][Gq][Gk]    fp32   the tile's P scale
+ *   Pi [B*h][Nq][Nk]    int8   the quantised P entry, read back from the packed f16 operand of the P@V MFMA
+ *   T  [B*h][Gk][Nq][d] int32  the tile's P@V accumulator (INT32_MIN: the accumulator was not an integer)
+ *   l  [B*h][Nq]        fp32   the row sum the epilogue divides by
+ * Entries of tiles a wave does not visit (past the diagonal of a causal call) are left untouched.
+ * Device pointers; runs on the null stream; blocking.
+ */
+int qmha_debug_fa_int8_pstage(const float *Q, const float *K, const float *V, float *O, int B, int Nq, int Nk,
+                              int d_model, int h, unsigned flags, int32_t *S, int8_t *Qi, float *sQ, float *m,
+                              float *sP, int8_t *Pi, int32_t *T, float *l);
+
 /* Test hook: bound, in ticks of the 100 MHz real-time clock, of the per-tensor pre-pass's wait for the
  * other parts of a head slice (default 200000 = 2 ms; 0 makes every part take its fallback, reducing
  * the whole slice itself; negative makes every call take the two-pass form that slices of more parts

@@ -31,6 +31,7 @@ SIGNATURES = {
     "qmha_debug_qk_int32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "qmha_debug_fa_int8_dump": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "qmha_debug_fa_int8_pt_dump": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "qmha_debug_fa_int8_pstage": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_uint] + [_vp] * 8),
     "qmha_variant_from_name": (_i, [_cp]),
     "qmha_variant_name": (_cp, [_i]),
     "qmha_status_string": (_cp, [_i]),

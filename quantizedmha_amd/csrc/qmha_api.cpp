@@ -635,6 +635,36 @@ int qmha_debug_fa_int8_dump(const float* Q, const float* K, const float* V, floa
     });
 }
 
+int qmha_debug_fa_int8_pstage(const float* Q, const float* K, const float* V, float* O, int B, int Nq, int Nk, int d_model,
+                              int h, unsigned flags, int32_t* S, int8_t* Qi, float* sQ, float* m, float* sP, int8_t* Pi,
+                              int32_t* T, float* l) {
+    // qmha_solve_rect's checks for fa_tc_int8_b, then run()'s choice of main kernel
+    int D = 0;
+    int st = check_shape(Q, K, V, O, B, Nq, d_model, h, QMHA_FA_TC_INT8_B, &D, "Nq");
+    if (st == QMHA_OK) st = check_shape(Q, K, V, O, B, Nk, d_model, h, QMHA_FA_TC_INT8_B, &D, "Nk");
+    if (st == QMHA_OK) st = check_flag_bits(flags);
+    if (st != QMHA_OK) return st;
+    const bool causal = flags & QMHA_FLAG_CAUSAL;
+    if (causal && Nq > Nk) return fail(QMHA_ERR_INVALID, "causal attention is bottom-right aligned and needs Nk >= Nq");
+    const VariantRow* row = find_variant(QMHA_FA_TC_INT8_B);
+    if ((causal && !built(row->causal, D)) || (Nq != Nk && !built(row->rect, D)))
+        return fail(QMHA_ERR_NOSYS, "debug P-stage dump: fa_tc_int8_b has no causal / rectangular kernel at d = " + std::to_string(D));
+    if (!S || !Qi || !sQ || !m || !sP || !Pi || !T || !l) return fail(QMHA_ERR_INVALID, "debug P-stage dump: null buffer");
+    return debug_run(qmha::int8_workspace_bytes(B, Nk, h, D), [&](void* ws) -> int {
+        const qmha::Int8Workspace w = qmha::int8_carve(ws, B, Nk, h, D);
+        QMHA_HIP_TRY(qmha::launch_quant_int8(Q, K, V, w, w.Vh, /*v_mode=*/1, B, Nk, h, D, d_model, nullptr, /*first_tensor=*/1),
+                     "quant_int8 launch");
+        const qmha::QkDump dbg{S, Qi, sQ};
+        const qmha::PDump pd{m, sP, Pi, T, l};
+        if (causal || Nq != Nk)
+            QMHA_HIP_TRY(qmha::launch_fa_int8_masked_pstage_dump(w, Q, O, B, Nq, Nk, h, D, d_model, causal, dbg, pd),
+                         "fa_int8 masked P-stage dump launch");
+        else
+            QMHA_HIP_TRY(qmha::launch_fa_int8_pstage_dump(w, Q, O, B, Nk, h, D, d_model, dbg, pd), "fa_int8 P-stage dump launch");
+        return QMHA_OK;
+    });
+}
+
 int qmha_debug_fa_int8_pt_dump(const float* Q, const float* K, const float* V, float* O, int B, int N, int d_model,
                                int h, int32_t* S, int8_t* Qi, float* sQ) {
     int D = 0;

@@ -241,6 +241,43 @@ __device__ __forceinline__ uint32_t pack4_lowbytes(float a, float b, float c, fl
     return __builtin_amdgcn_perm(t23, t01, 0x05040100u);
 }
 
+// Stores of the dumping kernel instances (PDump, qmha_kernels.hpp), lane (col, half) of the 32x32 accumulator
+// map.  SUBNORMAL: the P operand holds Pi * 2^-24 as f16 subnormals (its bits are Pi) and the accumulator
+// T * 2^-24; else both hold the integers themselves.  What is not the integer it should be is stored as the
+// type's minimum, which no correct value takes (Pi >= 0, |T| < 2^20).
+// prow: the row's Pi entries of this tile; element e of k-step ks pairs with key acc_row(8 ks + e, half)
+template <bool SUBNORMAL>
+__device__ __forceinline__ void dump_p_operand(int8_t* prow, const v8h (&pop)[2], int half) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const _Float16 hv = pop[r >> 3][r & 7];
+        int v;
+        if constexpr (SUBNORMAL) {
+            v = (int)__builtin_bit_cast(unsigned short, hv);
+        } else {
+            const float fv = (float)hv;
+            v = (int)fv;
+            if ((float)v != fv) v = -128;
+        }
+        prow[acc_row(r, half)] = (int8_t)(v >= 0 && v <= 127 ? v : -128);
+    }
+}
+// trow: the row's T entries of d-block m of this tile (32 ints); register r is d = 32 m + acc_row(r, half)
+template <bool SUBNORMAL>
+__device__ __forceinline__ void dump_pv_acc(int32_t* trow, const v16f& acc, int half) {
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4) {
+        v4i w;
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+            const float v = SUBNORMAL ? acc[4 * g4 + jj] * 16777216.0f : acc[4 * g4 + jj];
+            const int i = (int)v;
+            w[jj] = (float)i == v ? i : (int)0x80000000;
+        }
+        *reinterpret_cast<v4i*>(trow + 8 * g4 + 4 * half) = w;
+    }
+}
+
 // Workgroup barrier after LDS-DMA (global_load_lds): every wave first drains its own DMA
 // (vmcnt(0)) so that after the barrier all waves see the whole stage in LDS.  __syncthreads()
 // alone is not enough: the compiler may drop the vmcnt wait before s_barrier when no LDS read

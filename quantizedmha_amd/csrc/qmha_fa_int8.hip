@@ -93,11 +93,17 @@ __device__ __forceinline__ float quant_q_operand(const float* __restrict__ row, 
 //             accumulator: the bias folded into the shift (see the kernel)
 //   FL_DUMP   also store what the kernel itself computed: the int32 S^T of every tile (bias
 //             removed), its in-register Q operand and sQ (qmha_debug_fa_int8_dump: the bit-exact
-//             check of the production Q@K^T path; never the production launch)
+//             check of the production Q@K^T path; never the production launch); per-block mode with
+//             g_pdump set: the P stage of every tile too (PDump)
 //   FL_PT     (pipe kernel) the per-tensor mode fa_tc_int8_pt
 // Measured and not shipped (the sources are in git history up to commit df5dced):
 // the K/V pre-pass inside the sweep (FL_FUSED), P@V on the i8 matrix core per block (FL_I8PV) and per
 // tensor (FL_PT | FL_I8PV), the fold as packed fmas (QMHA_FOLD_PK), 12-wave workgroups (QMHA_INT8_W64).
+// The P-stage buffers of the dumping instances (PDump, qmha_kernels.hpp): set by the dump launchers before the
+// launch, read by FL_DUMP instances of the per-block kernels only; all null outside launch_fa_int8_pstage_dump.
+// (Not a kernel argument: one more argument moves the hidden arguments of the shipped instances.)
+__device__ PDump g_pdump;
+
 enum { FL_MAGIC = 1, FL_LB1 = 2, FL_LB2 = 4, FL_JIT = 8, FL_LB4 = 16, FL_KFOLD = 64, FL_DUMP = 256, FL_PT = 1048576 };
 
 // ---------------------------------------------------------------------------------------
@@ -140,6 +146,10 @@ __global__ __launch_bounds__(256, (FL & FL_LB1) ? 1 : ((FL & FL_LB2) ? 2 : 4)) v
     const int qg = qb * WAVES + wave;
     const bool active = qg < G;  // wave-uniform; an inactive wave still stages and syncs
 
+    PDump pd{};
+    if constexpr (DUMP) pd = g_pdump;
+    size_t drow = 0;  // DUMP: this lane's query row
+    if constexpr (DUMP) drow = (size_t)bh * N + (size_t)qg * QMHA_GROUP + col;
     v4i qop[KS];
     float cq = 0.0f;
     if (active) {
@@ -252,6 +262,13 @@ __global__ __launch_bounds__(256, (FL & FL_LB1) ? 1 : ((FL & FL_LB2) ? 2 : 4)) v
         }
         // row sum of the unquantised p (:336) + the other lane half
         const float rs = half_swap_add(tree_sum16(p));
+        if constexpr (DUMP) {
+            if (active && pd.m) {
+                if (half == 0) pd.m[drow * G + t] = m_new;
+                if (lane == 0) pd.sP[((size_t)bh * G + qg) * G + t] = sp;
+                dump_p_operand<false>(pd.Pi + drow * N + (size_t)t * QMHA_GROUP, pop, half);
+            }
+        }
         // Anchored running state: o = O * 2^(m - anchor), l_run = l * 2^(m - anchor).  The
         // reference's O = alpha*O + T*sP*sV and l = alpha*l + rowsum (:336,:344,:369-371)
         // become o += T*sP*sV*2^(m_t - anchor) and l_run += rowsum*2^(m_t - anchor):
@@ -278,6 +295,10 @@ __global__ __launch_bounds__(256, (FL & FL_LB1) ? 1 : ((FL & FL_LB2) ? 2 : 4)) v
             for (int ks = 0; ks < 2; ++ks) {
                 const v8h vop = *reinterpret_cast<const v8h*>(vr + 16 * swz_pos<64>(d, 2 * ks + half));
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(vop, pop[ks], acc, 0, 0, 0);
+            }
+            if constexpr (DUMP) {
+                if (active && pd.m)
+                    dump_pv_acc<false>(pd.T + (((size_t)bh * G + t) * N + qg * QMHA_GROUP + col) * D + 32 * m, acc, half);
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) o[m][r] = fmaf(acc[r], scale, o[m][r]);
@@ -308,6 +329,9 @@ __global__ __launch_bounds__(256, (FL & FL_LB1) ? 1 : ((FL & FL_LB2) ? 2 : 4)) v
     if (active) {
         const float unanchor = __builtin_amdgcn_exp2f(anchor - m_run);  // 2^(anchor - m)
         const float l = l_run * unanchor;
+        if constexpr (DUMP) {
+            if (pd.m && half == 0) pd.l[drow] = l;
+        }
         const bool ok = l > 1e-20f;
         float* orow = O + ((size_t)b * N + (size_t)qg * QMHA_GROUP + col) * d_model + (size_t)k * D + 4 * half;
 #pragma unroll
@@ -383,6 +407,22 @@ __global__ __launch_bounds__(WAVES * 64, (FL & FL_LB2) ? 2 : ((FL & FL_LB4) ? 4 
     // accumulates straight into O (the MFMA C operand); O is rescaled by alpha when a row's
     // running max moves (ballot-skipped otherwise) -- no P-tile max, no per-tile O fold
     constexpr bool PT = FL & FL_PT;
+    // per-block DUMP instances: the P-stage buffers and this lane's query row.  (Computed nowhere else: even a
+    // dead expression here moved the compiler's choices in the shipped instances.)
+    PDump pd{};
+    size_t drow = 0;
+    if constexpr (DUMP && !PT) {
+        pd = g_pdump;
+        drow = (size_t)bh * N + (size_t)qg * QMHA_GROUP + col;
+    }
+    // DUMP: the P@V accumulators of tile t (folded one iteration later, or in the drain)
+    auto dump_t = [&](int t, const v16f (&acc)[D / 32]) {
+        if (active && pd.m) {
+#pragma unroll
+            for (int m = 0; m < D / 32; ++m)
+                dump_pv_acc<true>(pd.T + (((size_t)bh * G + t) * N + qg * QMHA_GROUP + col) * D + 32 * m, acc[m], half);
+        }
+    };
     if (active) {
         const float* qrow = Qf + ((size_t)b * N + (size_t)qg * QMHA_GROUP + col) * d_model + (size_t)k * D;
         const float sq = quant_q_operand<D>(qrow, half, qop, PT ? sQt[bh] : 0.0f);
@@ -674,6 +714,13 @@ __global__ __launch_bounds__(WAVES * 64, (FL & FL_LB2) ? 2 : ((FL & FL_LB4) ? 4 
             pc[r >> 2][2 * (r & 3)] = h2[0];
             pc[r >> 2][2 * (r & 3) + 1] = h2[1];
         }
+        if constexpr (DUMP) {  // m, sP (without its 2^24) and the P operand as the MFMAs of iteration t+1 read it
+            if (active && pd.m) {
+                if (half == 0) pd.m[drow * G + t] = m_new;
+                if (lane == 0) pd.sP[((size_t)bh * G + qg) * G + t] = sp * (1.0f / 16777216.0f);
+                dump_p_operand<true>(pd.Pi + drow * N + (size_t)t * QMHA_GROUP, pc, half);
+            }
+        }
         QMHA_FENCE();
         mfmas(5);
         QMHA_FENCE();
@@ -686,6 +733,7 @@ __global__ __launch_bounds__(WAVES * 64, (FL & FL_LB2) ? 2 : ((FL & FL_LB4) ? 4 
         const float scale_t = sp * svb[t] * e;
         // ---- H: fold the pending tile's P@V into O (o += T * sP * sV * 2^(m - anchor))
         if constexpr (has_prev) {
+            if constexpr (DUMP) dump_t(t - 1, a);
 #pragma unroll
             for (int m = 0; m < MB; ++m)
 #pragma unroll
@@ -949,6 +997,7 @@ __global__ __launch_bounds__(WAVES * 64, (FL & FL_LB2) ? 2 : ((FL & FL_LB4) ? 4 
 #pragma unroll
                 for (int m = 0; m < MB; ++m)
                     a[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vop_of(t, m, ks), pp[ks], ks == 0 ? v16f{} : a[m], 0, 0, 0);
+            if constexpr (DUMP) dump_t(t, a);
 #pragma unroll
             for (int m = 0; m < MB; ++m) o[m] += a[m] * scale_prev;
         }
@@ -960,6 +1009,9 @@ __global__ __launch_bounds__(WAVES * 64, (FL & FL_LB2) ? 2 : ((FL & FL_LB4) ? 4 
         // rescales it exactly to the oracle's O * (sV / 127)
         const float unanchor = PT ? 16777216.0f * (svb[0] / 127.0f) : __builtin_amdgcn_exp2f(anchor - m_run);
         const float l = PT ? half_swap_add(l_run) : half_swap_add(l_run) * unanchor;
+        if constexpr (DUMP && !PT) {
+            if (pd.m && half == 0) pd.l[drow] = l;
+        }
         const bool ok = l > 1e-20f;
         float* orow = O + ((size_t)b * N + (size_t)qg * QMHA_GROUP + col) * d_model + (size_t)k * D + 4 * half;
 #pragma unroll
@@ -1412,6 +1464,26 @@ hipError_t launch_fa_int8_dump(const Int8Workspace& w, const float* Qf, float* O
 #undef QMHA_CASE
         default: return hipErrorInvalidValue;
     }
+}
+
+// launch_fa_int8_dump with the P-stage buffers set, and at N = 32 of the pipelined head sizes the twin of the
+// kernel fa_int8_pipe_launch falls back to (qmha_fa_int8_kernel<D, 0>)
+hipError_t launch_fa_int8_pstage_dump(const Int8Workspace& w, const float* Qf, float* O, int B, int N, int H, int D,
+                                      int d_model, QkDump dbg, PDump pd) {
+    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(g_pdump), &pd, sizeof(pd));
+    if (e != hipSuccess) return e;
+    if ((D == 32 || D == 64 || D == 128) && N / QMHA_GROUP < 2) {
+        switch (D) {
+            case 32: e = fa_int8_launch<32, FL_DUMP>(w, Qf, O, B, N, H, d_model, nullptr, dbg); break;
+            case 64: e = fa_int8_launch<64, FL_DUMP>(w, Qf, O, B, N, H, d_model, nullptr, dbg); break;
+            default: e = fa_int8_launch<128, FL_DUMP>(w, Qf, O, B, N, H, d_model, nullptr, dbg); break;
+        }
+    } else {
+        e = launch_fa_int8_dump(w, Qf, O, B, N, H, D, d_model, dbg, nullptr);
+    }
+    const PDump none{};  // the blocking copy also waits for the kernel
+    const hipError_t e2 = hipMemcpyToSymbol(HIP_SYMBOL(g_pdump), &none, sizeof(none));
+    return e != hipSuccess ? e : e2;
 }
 
 // The per-tensor mode's production schedule with FL_DUMP (same flags and workgroup size as

@@ -62,6 +62,7 @@ constexpr int kWaves = 4, kSG = 2;
 // Square causal: the diagonal of group g is tile g, which is also its last; nothing beyond N is passed or
 // computed, so these instances carry no offset and no clamp.
 struct SquareCausal {
+    static constexpr bool kDump = false;
     int N;
     __device__ int nq() const { return N; }
     __device__ int nk() const { return N; }
@@ -72,6 +73,7 @@ struct SquareCausal {
 // Rectangular.  causal: bottom-right aligned, diag_off = Gk - Gq (Nk >= Nq, checked by the launchers);
 // else diag_off = Gk, a diagonal no tile reaches
 struct Rect {
+    static constexpr bool kDump = false;
     int Nq, Nk, diag_off;
     Rect(int nq, int nk, bool causal) : Nq(nq), Nk(nk), diag_off(nk / QMHA_GROUP - (causal ? nq / QMHA_GROUP : 0)) {}
     __device__ int nq() const { return Nq; }
@@ -79,6 +81,16 @@ struct Rect {
     __device__ int gk() const { return Nk / QMHA_GROUP; }
     __device__ int diag(int g) const { return g + diag_off; }  // >= Gk: none
     __device__ int last(int g) const { return min(g + diag_off, gk() - 1); }
+};
+
+// A geometry that also carries the buffers of a dumping instance (int8 kernel; QkDump and PDump in
+// qmha_kernels.hpp): the debug hook's twin of a shipped instance, whose own arguments stay as they are.
+template <class Geo>
+struct Dumping : Geo {
+    static constexpr bool kDump = true;
+    QkDump qk;
+    PDump pd;
+    Dumping(Geo g, QkDump q, PDump p) : Geo(g), qk(q), pd(p) {}
 };
 
 // Launch index -> (bh, q-block pair): a workgroup runs q-block nqb - 1 - pi and then its mirror pi, so every
@@ -138,6 +150,7 @@ __global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_int8_mask
     constexpr int KBYTES = SG * 32 * D;      // K int8 per stage
     constexpr int VBYTES = SG * 32 * D * 2;  // V f16 per stage
     constexpr int KCH = KBYTES / 16, VCH = VBYTES / 16;
+    constexpr bool DUMP = Geo::kDump;  // also store what the kernel computed (Dumping<Geo>), per tile a wave runs
     static_assert(D == 32 || D == 64 || D == 128, "masked int8: d in {32, 64, 128}");
     static_assert(KCH % 64 == 0 && VCH % 64 == 0 && (KCH / SG) % 64 == 0, "whole KiB LDS-DMA pieces");
     __shared__ __attribute__((aligned(16))) char lds[2][KBYTES + VBYTES];
@@ -193,10 +206,18 @@ __global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_int8_mask
                 qop[s][c4] = (int)w;
             }
         cq = sq * c_log2;
+        if constexpr (DUMP) {  // the Q operand as held in registers: lane (col, half), k-step s
+            int8_t* qd = geo.qk.Qi + ((size_t)bh * Nq + (size_t)qg * QMHA_GROUP + col) * D + 16 * half;
+#pragma unroll
+            for (int s = 0; s < KS; ++s) *reinterpret_cast<v4i*>(qd + 32 * s) = qop[s];
+            if (lane == 0) geo.qk.sQ[(size_t)bh * Gq + qg] = sq;
+        }
     } else {
 #pragma unroll
         for (int s = 0; s < KS; ++s) qop[s] = v4i{0, 0, 0, 0};
     }
+    size_t drow = 0;  // DUMP: this lane's query row
+    if constexpr (DUMP) drow = (size_t)bh * Nq + (size_t)qg * QMHA_GROUP + col;
     v16f o[KS];
 #pragma unroll
     for (int m = 0; m < KS; ++m) o[m] = v16f{};
@@ -245,6 +266,11 @@ __global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_int8_mask
     auto tile = [&](const char* L, int gi, int t, const v16i& s, bool diag) {
         const float skt = skb[t], svt = svb[t];
         const float c = cq * skt;  // sQ*sK*log2(e)/sqrt(d) > 0
+        if constexpr (DUMP) {  // S^T of tile t before the mask (32x32 accumulator map); only an active wave gets here
+            int32_t* sd = geo.qk.S + drow * Nk + (size_t)t * QMHA_GROUP;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) sd[acc_row(r, half)] = s[r];
+        }
         float sf[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) sf[r] = (float)s[r];
@@ -279,6 +305,11 @@ __global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_int8_mask
         // row sum of the unquantised p (:336) over this lane's 16 keys; the two halves of l are joined once,
         // in the epilogue (every factor l takes below is the same in both halves of a row)
         const float rs = tree_sum16(p);
+        if constexpr (DUMP) {
+            if (half == 0) geo.pd.m[drow * Gk + t] = m_new;
+            if (lane == 0) geo.pd.sP[((size_t)bh * Gq + qg) * Gk + t] = sp;
+            dump_p_operand<true>(geo.pd.Pi + drow * Nk + (size_t)t * QMHA_GROUP, pop, half);
+        }
         // anchored running state, as qmha_fa_int8_kernel: o += T*sP*sV*2^(m_t - anchor),
         // l_run += rowsum*2^(m_t - anchor); re-anchor before the shift is formed
         if (__builtin_amdgcn_ballot_w64(m_new - anchor > 48.0f)) {
@@ -302,6 +333,8 @@ __global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_int8_mask
                 const v8h vop = *reinterpret_cast<const v8h*>(vr + 16 * swz_pos<64>(d, 2 * ks + half));
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(vop, pop[ks], acc, 0, 0, 0);
             }
+            if constexpr (DUMP)
+                dump_pv_acc<true>(geo.pd.T + (((size_t)bh * Gk + t) * Nq + qg * QMHA_GROUP + col) * D + 32 * m, acc, half);
 #pragma unroll
             for (int r = 0; r < 16; ++r) o[m][r] = fmaf(acc[r], scale, o[m][r]);
         }
@@ -335,6 +368,9 @@ __global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_int8_mask
     if (active) {
         const float unanchor = __builtin_amdgcn_exp2f(anchor - m_run);  // 2^(anchor - m)
         const float l = half_swap_add(l_run) * unanchor;
+        if constexpr (DUMP) {
+            if (half == 0) geo.pd.l[drow] = l;
+        }
         const bool ok = l > 1e-20f;
         float* orow = O + ((size_t)b * Nq + (size_t)qg * QMHA_GROUP + col) * d_model + (size_t)k * D + 4 * half;
 #pragma unroll
@@ -569,8 +605,10 @@ static bool masked_shape_ok(int Nq, int Nk, bool causal) {
 }
 static int masked_nqb(int Nq) { return (Nq / QMHA_GROUP + kWaves - 1) / kWaves; }
 
-hipError_t launch_fa_int8_masked_main(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
-                                      int d_model, bool causal, hipStream_t stream) {
+// `wrap` turns the launch's geometry into the kernel's Geo argument: itself, or Dumping<> for the debug twin
+template <class Wrap>
+static hipError_t fa_int8_masked_launch(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
+                                        int d_model, bool causal, hipStream_t stream, Wrap&& wrap) {
     if (!masked_shape_ok(Nq, Nk, causal)) return hipErrorInvalidValue;
     const int nqb = masked_nqb(Nq);
     auto launch = [&](auto geo, auto d) {
@@ -586,7 +624,20 @@ hipError_t launch_fa_int8_masked_main(const Int8Workspace& w, const float* Qf, f
             default: return hipErrorInvalidValue;
         }
     };
-    return causal && Nq == Nk ? by_d(SquareCausal{Nq}) : by_d(Rect(Nq, Nk, causal));
+    return causal && Nq == Nk ? by_d(wrap(SquareCausal{Nq})) : by_d(wrap(Rect(Nq, Nk, causal)));
+}
+
+hipError_t launch_fa_int8_masked_main(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
+                                      int d_model, bool causal, hipStream_t stream) {
+    return fa_int8_masked_launch(w, Qf, O, B, Nq, Nk, H, D, d_model, causal, stream, [](auto geo) { return geo; });
+}
+
+// The dumping twin of the instance launch_fa_int8_masked_main launches for this shape: the same grid and
+// arguments, the geometry wrapped in Dumping<>
+hipError_t launch_fa_int8_masked_pstage_dump(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H,
+                                             int D, int d_model, bool causal, QkDump dbg, PDump pd) {
+    return fa_int8_masked_launch(w, Qf, O, B, Nq, Nk, H, D, d_model, causal, nullptr,
+                                 [&](auto geo) { return Dumping<decltype(geo)>(geo, dbg, pd); });
 }
 
 hipError_t launch_fa_f16_masked_main(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,

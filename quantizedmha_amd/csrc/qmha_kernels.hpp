@@ -112,8 +112,30 @@ struct QkDump {
     int8_t* Qi;
     float* sQ;
 };
+// what a dumping instance of the per-block kernels stores beside QkDump, per tile a wave computes (the P stage;
+// all null: nothing): m [B*H][Nq][Gk] the row's running max after the tile (log2 units); sP [B*H][Gq][Gk] the
+// tile's P scale (without the 2^24 of the f16-subnormal packing); Pi [B*H][Nq][Nk] the quantised P entry read back
+// from the packed f16 MFMA operand; T [B*H][Gk][Nq][D] the tile's P@V accumulator as int32 (INT32_MIN where the
+// accumulator was not an integer); l [B*H][Nq] the joined, un-anchored row sum the epilogue divides by.
+// Gq = Nq / 32, Gk = Nk / 32.  The shipped kernels' arguments are not touched: the non-causal kernels' dumping
+// instances read it from a device variable of their translation unit, the masked kernel's from their geometry.
+struct PDump {
+    float* m;
+    float* sP;
+    int8_t* Pi;
+    int32_t* T;
+    float* l;
+};
 hipError_t launch_fa_int8_dump(const Int8Workspace& w, const float* Qf, float* O, int B, int N, int H, int D,
                                int d_model, QkDump dbg, hipStream_t stream);
+// The dumping twin of the kernel launch_fa_int8_main (Nq == Nk, not causal) or launch_fa_int8_masked_main would
+// launch for this shape, N = 32 included; every buffer of dbg and pd is written.  On the null stream, for the
+// blocking debug hook: the non-causal twins' device variable is set before the launch and cleared after it with
+// blocking copies.
+hipError_t launch_fa_int8_pstage_dump(const Int8Workspace& w, const float* Qf, float* O, int B, int N, int H, int D,
+                                      int d_model, QkDump dbg, PDump pd);
+hipError_t launch_fa_int8_masked_pstage_dump(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk,
+                                             int H, int D, int d_model, bool causal, QkDump dbg, PDump pd);
 hipError_t launch_fa_int8_pt_dump(const Int8Workspace& w, const float* Qf, float* O, int B, int N, int H, int D,
                                   int d_model, QkDump dbg, hipStream_t stream);
 

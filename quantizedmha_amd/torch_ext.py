@@ -180,3 +180,37 @@ def debug_fa_int8_dump(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, d_mode
                 Qi.data_ptr(), sQ.data_ptr())
     _lib.check(st, "debug_fa_int8_dump")
     return O, S, Qi, sQ
+
+
+# What debug_fa_int8_pstage pre-fills its buffers with: values no kernel writes there (|S| < 2^22, |T| < 2^20 or
+# INT32_MIN, Pi in 0..127 or -128, Qi never -128 from a symmetric scale, sQ / sP / l >= 0, m >= m0 = 0).
+PSTAGE_SENTINEL = {"S": 0x7FFFFFF1, "Qi": -128, "sQ": -3.0e38, "m": -3.0e38, "sP": -3.0e38, "Pi": -127, "T": 0x7FFFFFF1,
+                   "l": -3.0e38}
+
+
+def debug_fa_int8_pstage(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, d_model: int, num_heads: int,
+                         causal: bool = False):
+    """The P stage of fa_tc_int8_b, tile by tile (test hook; qmha_debug_fa_int8_pstage in include/launchers.h).
+
+    Q [B, Nq, d_model], K and V [B, Nk, d_model]: runs the dumping twin of the kernel flash_solve / flash_solve_rect
+    would launch and returns (O, dump) with dump a dict of tensors, every one pre-filled with PSTAGE_SENTINEL so
+    that what the kernel did not write can be told: S [B, h, Nq, Nk] int32, Qi [B, h, Nq, d] int8, sQ [B, h, Gq],
+    m [B, h, Nq, Gk], sP [B, h, Gq, Gk], Pi [B, h, Nq, Nk] int8, T [B, h, Gk, Nq, d] int32, l [B, h, Nq]."""
+    if not (Q.is_cuda and K.is_cuda and V.is_cuda):
+        raise RuntimeError("Inputs must be CUDA tensors")
+    Qc, Kc, Vc = Q.contiguous(), K.contiguous(), V.contiguous()
+    B, Nq = _shape(Qc, d_model)
+    _, Nk = _shape(Kc, d_model)
+    h, d, Gq, Gk = num_heads, d_model // num_heads, Nq // 32, Nk // 32
+    O = torch.empty_like(Qc)
+    i32, i8, f32 = torch.int32, torch.int8, torch.float32
+    shapes = {"S": ((B, h, Nq, Nk), i32), "Qi": ((B, h, Nq, d), i8), "sQ": ((B, h, Gq), f32), "m": ((B, h, Nq, Gk), f32),
+              "sP": ((B, h, Gq, Gk), f32), "Pi": ((B, h, Nq, Nk), i8), "T": ((B, h, Gk, Nq, d), i32), "l": ((B, h, Nq), f32)}
+    dump = {k: torch.full(shape, PSTAGE_SENTINEL[k], dtype=dt, device=Q.device) for k, (shape, dt) in shapes.items()}
+    torch.cuda.synchronize(Q.device)
+    with torch.cuda.device(Qc.device):
+        st = _lib.load().qmha_debug_fa_int8_pstage(Qc.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), O.data_ptr(), B, Nq, Nk, d_model,
+                                                   h, _lib.QMHA_FLAG_CAUSAL if causal else 0,
+                                                   *(dump[k].data_ptr() for k in ("S", "Qi", "sQ", "m", "sP", "Pi", "T", "l")))
+    _lib.check(st, "debug_fa_int8_pstage")
+    return O, dump

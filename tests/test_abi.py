@@ -181,6 +181,7 @@ def test_production_library_has_one_kernel_per_variant_and_d(built):
     stubs = set(re.findall(r"__device_stub__(\w+?)ILi(\d+)E(\w*)", syms))
     per = {}
     dumps = []
+    masked_dumps = []
     for name, d, rest in stubs:
         if name.startswith("qmha_gemm"):
             continue
@@ -192,6 +193,11 @@ def test_production_library_has_one_kernel_per_variant_and_d(built):
             continue
         if name in ("qmha_fa_int8_masked_kernel", "qmha_fa_f16_masked_kernel"):  # <D, geometry>
             # the square causal and the rectangular kernel are two kernels of one template: one instance of each
+            twin = re.match(r"NS_\d+DumpingINS_\d+([A-Za-z]+?)EEE", rest)
+            if twin:  # the P-stage test hook's twin of a shipped int8 instance: its geometry wrapped in Dumping<>
+                assert name == "qmha_fa_int8_masked_kernel", name
+                masked_dumps.append((f"{name}[{twin.group(1)}]", d))
+                continue
             name += "[%s]" % re.match(r"NS_\d+([A-Za-z]+?)E", rest).group(1)
         if name == "qmha_fa_int8_pipe_kernel":  # <D, WAVES, FL>
             m, fl = re.match(r"Li(\d+)ELi(\d+)E", rest), 2
@@ -208,9 +214,12 @@ def test_production_library_has_one_kernel_per_variant_and_d(built):
             dumps.append((name, d, twin))
             continue
         per.setdefault((name, d), set()).add(rest)
-    # per-block d = 32 / 64 / 128 (pipelined) and 96 / 160 / 192 / 224 / 256 (one-tile kernel),
-    # per-tensor d = 32 / 64 / 128
-    assert len(dumps) == 11, dumps
+    # per-block d = 32 / 64 / 128 (pipelined, and the one-tile kernel they run at N = 32) and 96 / 160 / 192 /
+    # 224 / 256 (one-tile kernel), per-tensor d = 32 / 64 / 128
+    assert len(dumps) == 14, dumps
+    # one twin of every shipped masked int8 instance (d = 32 / 64 / 128, both geometries), and of nothing else
+    assert sorted(masked_dumps) == sorted(k for k in per if k[0].startswith("qmha_fa_int8_masked_kernel[")), masked_dumps
+    assert len(masked_dumps) == 6, masked_dumps
     for name, d, twin in dumps:  # exactly the production schedule (same WAVES, flags, PAD) plus the stores
         if name == "qmha_fa_int8_pt_v3_kernel":  # the 8-wave production instance (the 4-wave one has no twin)
             assert twin in per[(name, d)], (name, d, twin)

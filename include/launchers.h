@@ -115,10 +115,54 @@ int qmha_solve_opts(const float *Q, const float *K, const float *V, float *O, in
  * Nq == Nk enqueues exactly what qmha_solve_opts enqueues, for every variant.  Nq != Nk is built for
  * fa_tc_int8_b at d = 32, 64, 128 and fa_tc_v1a at d = 64, 128, with or without QMHA_FLAG_CAUSAL; every other
  * variant or head size returns QMHA_ERR_NOSYS (qmha_last_error names the variant and d) before anything is
- * launched, leaving O untouched.  Every call runs the K/V pre-pass over all Nk rows.
+ * launched, leaving O untouched.  Every call runs the K/V pre-pass over all Nk rows (qmha_kv_cache_* below keeps
+ * the pre-passed rows of earlier calls instead).
  */
 int qmha_solve_rect(const float *Q, const float *K, const float *V, float *O, int B, int Nq, int Nk, int d_model,
                     int h, int variant, unsigned flags, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Persistent K/V cache -- chunked prefill and decode without re-running the K/V pre-pass over rows that were
+ * quantised (int8) or converted (fp16) by an earlier call.  A cache is an opaque host object over CALLER-OWNED device
+ * memory: qmha_kv_cache_bytes(B, cap, ...) bytes (exactly qmha_workspace_size at N = cap; the layout is that
+ * workspace's), 256-byte aligned, holding up to `cap` rows of K and V per sequence, of which the first `len` are valid.
+ * The library never allocates, frees or synchronises for a cache; destroy releases the host object only.
+ *
+ *   create    cap % 32 == 0, cap >= 32, the other shape rules of qmha_solve_ex at N = cap; len = 0.  Built for
+ *             fa_tc_int8_b at d = 32, 64, 128 and fa_tc_v1a at d = 64, 128 (qmha_solve_rect's Nq != Nk set); any other
+ *             variant or head size: QMHA_ERR_NOSYS, qmha_last_error names the variant and d.
+ *   append    K, V: [B, n, d_model] fp32 device tensors, contiguous; n % 32 == 0, n >= 32, len + n <= cap (otherwise
+ *             QMHA_ERR_INVALID and len is unchanged).  Enqueues the pre-pass of the n new rows on `stream`, writing
+ *             rows [len, len + n) of the cache with the bytes the pre-pass of a whole call writes for them (32-row
+ *             quantisation groups are independent); len advances by n only when the launch succeeded.
+ *   attend    Q, O: [B, Nq, d_model], Nq % 32 == 0.  QMHA_FLAG_CAUSAL: bottom-right aligned over the valid rows,
+ *             query row r attends cache rows j <= r + (len - Nq); needs Nq <= len.  Rows at and beyond len are never
+ *             read, whatever they hold.  flags == 0: every query row attends all cap rows, which needs len == cap (a
+ *             cross-attention memory built once at its size); len < cap without the mask is QMHA_ERR_INVALID.  Unknown
+ *             flag bits: QMHA_ERR_INVALID.  The result is bit-identical to qmha_solve_rect(Q, K[:, :len], V[:, :len],
+ *             Nq, len, flags) whenever that call takes its rectangular kernel (Nq != len, or no mask).
+ *   truncate  drops rows from the end: len % 32 == 0, 0 <= len <= the current length.  Host only; nothing is enqueued.
+ *   len       the valid rows; 0 after create.
+ *
+ * Every check runs before any HIP call.  append and attend make no allocation and no synchronisation, so they can
+ * be captured in a hipGraph; the capture bakes in the cache's length at the time of the call (a replay appends to,
+ * and attends over, the same rows again).
+ * Threading: each cache has a mutex of its own, held across an enqueue; no leased (device, stream) slot is taken.
+ * Different caches are independent and may be used from different threads and streams at once.  The CALLER orders
+ * the operations on one cache: by issuing them on one stream, or with its own events -- an attend must follow the
+ * appends it reads, and an append into rows freed by truncate must follow the attends that still read them.
+ * With qmha_profile_enable(1), every append records one pre-pass event pair and every attend one main-kernel pair,
+ * each a record of its own (qmha_profile_collect counts one call for each).
+ */
+typedef struct qmha_kv_cache qmha_kv_cache_t;
+size_t qmha_kv_cache_bytes(int B, int cap, int d_model, int h, int variant);
+int qmha_kv_cache_create(qmha_kv_cache_t **out, void *mem, size_t bytes, int B, int cap, int d_model, int h,
+                         int variant);
+void qmha_kv_cache_destroy(qmha_kv_cache_t *c);
+int qmha_kv_cache_len(const qmha_kv_cache_t *c);
+int qmha_kv_cache_truncate(qmha_kv_cache_t *c, int len);
+int qmha_kv_cache_append(qmha_kv_cache_t *c, const float *K, const float *V, int n, void *stream);
+int qmha_attend_cached(qmha_kv_cache_t *c, const float *Q, float *O, int Nq, unsigned flags, void *stream);
 
 /* Blocking convenience used by the per-variant `solve` shims and the JAX raw-pointer
  * binding (extensions/jax/jax_ext.cpp:12-28): batch 1, synchronises the device stream. */

@@ -501,7 +501,37 @@ int debug_run(size_t need, Body&& body) {
     return QMHA_OK;
 }
 
+// "persistent K/V cache is not built for variant X at d = D (...)": the table's `rect` column, whose kernels it runs
+int check_cache_built(int variant, int D) {
+    if (built(find_variant(variant)->rect, D)) return QMHA_OK;
+    std::string have;
+    for (const VariantRow& r : kVariants)
+        if (r.rect) have += (have.empty() ? "" : "; ") + std::string(r.name) + ": d = " + d_list(r.rect);
+    return fail(QMHA_ERR_NOSYS, std::string("the persistent K/V cache is not built for variant ") + qmha_variant_name(variant) +
+                                    " at d = " + std::to_string(D) + " (" + have + ")");
+}
+
+bool profiling_on() {
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    return g_prof_on;
+}
+void keep_record(ProfRec&& rec) {
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    g_prof_recs.push_back(std::move(rec));
+}
+
 }  // namespace
+
+// ---- persistent K/V cache ---------------------------------------------------------
+// A host object over caller-owned device memory laid out as the variant's workspace carve at N = cap.  No HIP
+// allocation, no synchronisation, no leased slot (there is no scratch): `mu` is held across each enqueue, and the
+// caller orders the operations on one cache (one stream, or its own events).
+struct qmha_kv_cache {
+    std::mutex mu;
+    void* mem;
+    int B, cap, d_model, h, D, variant;
+    int len;  // valid rows of every head slice
+};
 
 int qmha::tune_config(const char* env_name) {
     static std::mutex mu;
@@ -551,6 +581,108 @@ int qmha_solve_rect(const float* Q, const float* K, const float* V, float* O, in
 size_t qmha_workspace_size(int B, int N, int d_model, int h, int variant) {
     if (B < 1 || N < 1 || h < 1 || d_model % h) return 0;
     return workspace_bytes(B, N, h, d_model / h, variant);
+}
+
+// ---- persistent K/V cache: every check runs before any HIP call -------------------------------------
+size_t qmha_kv_cache_bytes(int B, int cap, int d_model, int h, int variant) {
+    return qmha_workspace_size(B, cap, d_model, h, variant);  // the variant's carve at N = cap
+}
+
+int qmha_kv_cache_create(qmha_kv_cache_t** out, void* mem, size_t bytes, int B, int cap, int d_model, int h, int variant) {
+    if (!out) return fail(QMHA_ERR_INVALID, "null cache handle pointer");
+    *out = nullptr;
+    if (!mem) return fail(QMHA_ERR_INVALID, "null cache memory");
+    int D = 0;
+    int st = check_shape(mem, mem, mem, mem, B, cap, d_model, h, variant, &D, "cap");  // cap >= 32, cap % 32 == 0
+    if (st == QMHA_OK) st = check_cache_built(variant, D);
+    if (st != QMHA_OK) return st;
+    if (reinterpret_cast<uintptr_t>(mem) % 256 != 0) return fail(QMHA_ERR_INVALID, "cache memory must be 256-byte aligned");
+    const size_t need = workspace_bytes(B, cap, h, D, variant);
+    if (bytes < need)
+        return fail(QMHA_ERR_INVALID, "cache memory too small: " + std::to_string(bytes) + " bytes, qmha_kv_cache_bytes is " +
+                                          std::to_string(need));
+    qmha_kv_cache* c = new qmha_kv_cache;
+    c->mem = mem;
+    c->B = B, c->cap = cap, c->d_model = d_model, c->h = h, c->D = D, c->variant = variant;
+    c->len = 0;
+    *out = c;
+    return QMHA_OK;
+}
+
+void qmha_kv_cache_destroy(qmha_kv_cache_t* c) { delete c; }
+
+int qmha_kv_cache_len(const qmha_kv_cache_t* c) {
+    if (!c) return 0;
+    std::lock_guard<std::mutex> lk(const_cast<qmha_kv_cache_t*>(c)->mu);
+    return c->len;
+}
+
+int qmha_kv_cache_truncate(qmha_kv_cache_t* c, int len) {
+    if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (len < 0 || len % 32 != 0) return fail(QMHA_ERR_INVALID, "truncate: len must be a non-negative multiple of 32");
+    if (len > c->len)
+        return fail(QMHA_ERR_INVALID, "truncate: len = " + std::to_string(len) + " is above the cache's " +
+                                          std::to_string(c->len) + " valid rows");
+    c->len = len;
+    return QMHA_OK;
+}
+
+int qmha_kv_cache_append(qmha_kv_cache_t* c, const float* K, const float* V, int n, void* stream) {
+    if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+    if (!K || !V) return fail(QMHA_ERR_INVALID, "null tensor pointer");
+    std::lock_guard<std::mutex> lk(c->mu);  // held across the enqueue
+    if (n < 32 || n % 32 != 0) return fail(QMHA_ERR_INVALID, "append: n must be a positive multiple of 32");
+    if ((long long)c->len + n > c->cap)
+        return fail(QMHA_ERR_INVALID, "append: " + std::to_string(n) + " rows behind len = " + std::to_string(c->len) +
+                                          " exceed cap = " + std::to_string(c->cap));
+    const hipStream_t s = (hipStream_t)stream;
+    const bool prof = profiling_on();
+    ProfRec rec;
+    bool launched = false;
+    const int st = timed(prof ? &rec.pre : nullptr, s, "kv_cache append launch", [&] {
+        const hipError_t e =
+            c->variant == QMHA_FA_TC_INT8_B
+                ? qmha::launch_kv_append_int8(K, V, qmha::int8_carve(c->mem, c->B, c->cap, c->h, c->D), c->B, n, c->cap, c->len,
+                                              c->h, c->D, c->d_model, s)
+                : qmha::launch_kv_append_f16(K, V, qmha::f16_carve(c->mem, c->B, c->cap, c->h, c->D), c->B, n, c->cap, c->len,
+                                             c->h, c->D, c->d_model, s);
+        launched = e == hipSuccess;
+        return e;
+    });
+    if (launched) c->len += n;  // the rows are on their way whatever became of the closing profile event
+    if (st == QMHA_OK && prof) keep_record(std::move(rec));
+    return st;
+}
+
+int qmha_attend_cached(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, unsigned flags, void* stream) {
+    if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+    int D = 0;
+    int st = check_shape(Q, Q, Q, O, c->B, Nq, c->d_model, c->h, c->variant, &D, "Nq");
+    if (st == QMHA_OK) st = check_flag_bits(flags);
+    if (st != QMHA_OK) return st;
+    const bool causal = flags & QMHA_FLAG_CAUSAL;
+    std::lock_guard<std::mutex> lk(c->mu);  // held across the enqueue
+    const int len = c->len;
+    if (causal && Nq > len)
+        return fail(QMHA_ERR_INVALID, "causal attention is bottom-right aligned and needs len >= Nq (Nq = " + std::to_string(Nq) +
+                                          ", len = " + std::to_string(len) + ")");
+    if (!causal && len != c->cap)
+        return fail(QMHA_ERR_INVALID, "attention without QMHA_FLAG_CAUSAL reads all cap = " + std::to_string(c->cap) +
+                                          " rows and the cache holds len = " + std::to_string(len) +
+                                          ": the kernel has no unmasked mode that stops before cap");
+    const hipStream_t s = (hipStream_t)stream;
+    const bool prof = profiling_on();
+    ProfRec rec;
+    st = timed(prof ? &rec.main : nullptr, s, "kv_cache attend launch", [&] {
+        return c->variant == QMHA_FA_TC_INT8_B
+                   ? qmha::launch_fa_int8_masked_cached(qmha::int8_carve(c->mem, c->B, c->cap, c->h, c->D), Q, O, c->B, Nq, c->cap,
+                                                        len, c->h, c->D, c->d_model, causal, s)
+                   : qmha::launch_fa_f16_masked_cached(qmha::f16_carve(c->mem, c->B, c->cap, c->h, c->D), Q, O, c->B, Nq, c->cap,
+                                                       len, c->h, c->D, c->d_model, causal, s);
+    });
+    if (st == QMHA_OK && prof) keep_record(std::move(rec));
+    return st;
 }
 
 int qmha_solve_variant(const float* Q, const float* K, const float* V, float* O, int N, int d_model, int h,

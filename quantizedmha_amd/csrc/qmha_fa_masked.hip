@@ -76,6 +76,15 @@ struct Rect {
     static constexpr bool kDump = false;
     int Nq, Nk, diag_off;
     Rect(int nq, int nk, bool causal) : Nq(nq), Nk(nk), diag_off(nk / QMHA_GROUP - (causal ? nq / QMHA_GROUP : 0)) {}
+    // Host only: the causal geometry of a K/V cache.  The arrays hold `cap` rows per head slice and the
+    // first `len` are valid: Nk = cap keeps the bases, the extents and the sK / sV index those of the cache, and the
+    // explicit offset (len - nq) / 32 puts the diagonal of the last query group on tile len / 32 - 1, so last(g) <=
+    // len / 32 - 1 for every g < Gq and no tile at or beyond len / 32 is staged or computed.  nq <= len <= cap.
+    static Rect cached(int nq, int cap, int len) {
+        Rect r(nq, cap, false);
+        r.diag_off = (len - nq) / QMHA_GROUP;
+        return r;
+    }
     __device__ int nq() const { return Nq; }
     __device__ int nk() const { return Nk; }
     __device__ int gk() const { return Nk / QMHA_GROUP; }
@@ -605,11 +614,12 @@ static bool masked_shape_ok(int Nq, int Nk, bool causal) {
 }
 static int masked_nqb(int Nq) { return (Nq / QMHA_GROUP + kWaves - 1) / kWaves; }
 
-// `wrap` turns the launch's geometry into the kernel's Geo argument: itself, or Dumping<> for the debug twin
+// `wrap` turns the launch's geometry into the kernel's Geo argument: itself, or Dumping<> for the debug twin.
+// `given`: launch the Rect instance with this geometry (the K/V cache, which has checked it) and not the call's own.
 template <class Wrap>
 static hipError_t fa_int8_masked_launch(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
-                                        int d_model, bool causal, hipStream_t stream, Wrap&& wrap) {
-    if (!masked_shape_ok(Nq, Nk, causal)) return hipErrorInvalidValue;
+                                        int d_model, bool causal, hipStream_t stream, Wrap&& wrap, const Rect* given = nullptr) {
+    if (!given && !masked_shape_ok(Nq, Nk, causal)) return hipErrorInvalidValue;
     const int nqb = masked_nqb(Nq);
     auto launch = [&](auto geo, auto d) {
         hipLaunchKernelGGL((qmha_fa_int8_masked_kernel<decltype(d)::value, decltype(geo)>), dim3(B * H * masked_pairs(nqb)), dim3(kWaves * 64),
@@ -624,7 +634,7 @@ static hipError_t fa_int8_masked_launch(const Int8Workspace& w, const float* Qf,
             default: return hipErrorInvalidValue;
         }
     };
-    return causal && Nq == Nk ? by_d(wrap(SquareCausal{Nq})) : by_d(wrap(Rect(Nq, Nk, causal)));
+    return !given && causal && Nq == Nk ? by_d(wrap(SquareCausal{Nq})) : by_d(wrap(given ? *given : Rect(Nq, Nk, causal)));
 }
 
 hipError_t launch_fa_int8_masked_main(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
@@ -640,9 +650,9 @@ hipError_t launch_fa_int8_masked_pstage_dump(const Int8Workspace& w, const float
                                  [&](auto geo) { return Dumping<decltype(geo)>(geo, dbg, pd); });
 }
 
-hipError_t launch_fa_f16_masked_main(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
-                                     int d_model, bool causal, hipStream_t stream) {
-    if (!masked_shape_ok(Nq, Nk, causal)) return hipErrorInvalidValue;
+static hipError_t fa_f16_masked_launch(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
+                                       int d_model, bool causal, hipStream_t stream, const Rect* given = nullptr) {
+    if (!given && !masked_shape_ok(Nq, Nk, causal)) return hipErrorInvalidValue;
     const int nqb = masked_nqb(Nq);
     auto launch = [&](auto geo, auto d) {
         hipLaunchKernelGGL((qmha_fa_f16_masked_kernel<decltype(d)::value, decltype(geo)>), dim3(B * H * nqb), dim3(kWaves * 64), 0, stream,
@@ -656,7 +666,33 @@ hipError_t launch_fa_f16_masked_main(const F16Workspace& w, const float* Qf, flo
             default: return hipErrorInvalidValue;
         }
     };
-    return causal && Nq == Nk ? by_d(SquareCausal{Nq}) : by_d(Rect(Nq, Nk, causal));
+    return !given && causal && Nq == Nk ? by_d(SquareCausal{Nq}) : by_d(given ? *given : Rect(Nq, Nk, causal));
+}
+
+hipError_t launch_fa_f16_masked_main(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
+                                     int d_model, bool causal, hipStream_t stream) {
+    return fa_f16_masked_launch(w, Qf, O, B, Nq, Nk, H, D, d_model, causal, stream);
+}
+
+// K/V cache: always the Rect instances (also at Nq == len, where a call of its own takes the
+// SquareCausal ones), with Nk = cap.  causal: Rect::cached; else every row attends all cap rows, so len == cap.
+static bool cached_shape_ok(int Nq, int cap, int len, bool causal) {
+    if (!masked_shape_ok(Nq, cap, false) || len % QMHA_GROUP != 0) return false;
+    return causal ? Nq <= len && len <= cap : len == cap;
+}
+
+hipError_t launch_fa_int8_masked_cached(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int cap, int len,
+                                        int H, int D, int d_model, bool causal, hipStream_t stream) {
+    if (!cached_shape_ok(Nq, cap, len, causal)) return hipErrorInvalidValue;
+    const Rect geo = causal ? Rect::cached(Nq, cap, len) : Rect(Nq, cap, false);
+    return fa_int8_masked_launch(w, Qf, O, B, Nq, cap, H, D, d_model, causal, stream, [](auto g) { return g; }, &geo);
+}
+
+hipError_t launch_fa_f16_masked_cached(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int cap, int len,
+                                       int H, int D, int d_model, bool causal, hipStream_t stream) {
+    if (!cached_shape_ok(Nq, cap, len, causal)) return hipErrorInvalidValue;
+    const Rect geo = causal ? Rect::cached(Nq, cap, len) : Rect(Nq, cap, false);
+    return fa_f16_masked_launch(w, Qf, O, B, Nq, cap, H, D, d_model, causal, stream, &geo);
 }
 
 }  // namespace qmha

@@ -170,6 +170,23 @@ hipError_t launch_fa_int8_masked_main(const Int8Workspace& w, const float* Qf, f
 hipError_t launch_fa_f16_masked_main(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
                                      int d_model, bool causal, hipStream_t stream);
 
+// ---- persistent K/V cache (qmha_kv_cache_*) ---------------------------------------
+// w: the variant's carve at N = cap, in caller-owned memory; `len` of its `cap` rows per head slice are valid.
+// Append (qmha_prepass.hip): the pre-pass of the n new rows K, V [B, n, d_model] into rows [len, len + n) of every
+// slice; n, cap, len multiples of 32, len + n <= cap; the bytes are those the pre-pass of a whole call writes there.
+hipError_t launch_kv_append_int8(const float* K, const float* V, const Int8Workspace& w, int B, int n, int cap, int len,
+                                 int H, int D, int d_model, hipStream_t stream);
+hipError_t launch_kv_append_f16(const float* K, const float* V, const F16Workspace& w, int B, int n, int cap, int len,
+                                int H, int D, int d_model, hipStream_t stream);
+// Attend (qmha_fa_masked.hip): the shipped Rect instances with Nk = cap.  causal: bottom-right aligned over the first
+// `len` rows (row r attends cache rows j <= r + len - Nq; Nq <= len <= cap), diag_off = (len - Nq) / 32, so no tile
+// at or beyond len / 32 is staged or computed.  Not causal: every row attends all cap rows, which needs len == cap
+// (the kernel has no unmasked mode that stops before cap / 32).  Anything else: hipErrorInvalidValue.
+hipError_t launch_fa_int8_masked_cached(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int cap, int len,
+                                        int H, int D, int d_model, bool causal, hipStream_t stream);
+hipError_t launch_fa_f16_masked_cached(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int cap, int len,
+                                       int H, int D, int d_model, bool causal, hipStream_t stream);
+
 // ---- FP32 (fa: scalar VALU kernel; fa_mfma: the same contract on v_mfma_f32_32x32x2_f32) -----
 hipError_t launch_fa_f32(const float* Q, const float* K, const float* V, float* O, int B, int N, int H, int D,
                          int d_model, bool mfma, hipStream_t stream);

@@ -15,9 +15,11 @@ streams + a blocking sync (torch orders it with surrounding ops on that stream).
 ROCm tensors report device type 'cuda', exactly as the reference's is_cuda() check expects.
 flash_solve_rect (additive, no reference counterpart) is flash_solve with a query length of its own: K and V
 share one shape, Q has its own row count (cross-attention, chunked prefill; qmha_solve_rect).
+KVCache (additive) keeps the pre-passed K and V of earlier chunks: append new rows, attend with the last Nq.
 """
 from __future__ import annotations
 
+import ctypes
 import warnings
 from typing import Optional
 
@@ -117,6 +119,89 @@ def flash_solve_rect(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, d_model:
                                  stream)
     _lib.check(st, f"flash_solve_rect({kernel})")
     return out
+
+
+class KVCache:
+    """A persistent quantised K/V cache (qmha_kv_cache_*; additive, no reference counterpart): chunked prefill and
+    decode without re-running the K/V pre-pass over rows an earlier call already quantised / converted.
+
+        cache = KVCache(B, cap, d_model, num_heads)          # fa_tc_int8_b (d = 32 / 64 / 128) or fa_tc_v1a (64 / 128)
+        cache.append(K_chunk, V_chunk)                       # [B, n, d_model] (or [n, d_model] for B = 1), n % 32 == 0
+        O = cache.attend(Q_chunk)                            # row r attends cache rows j <= r + (len - Nq)
+
+    The object owns a torch.uint8 tensor of qmha_kv_cache_bytes (`.mem`).  append and attend are enqueued on torch's
+    current stream; the caller keeps the operations on one cache ordered (one stream, or its own events).
+    attend(Q, causal=False) needs a full cache (len == cap): every row attends all cap rows.  truncate(n) drops rows
+    from the end (n % 32 == 0, n <= len); nothing is enqueued."""
+
+    def __init__(self, B: int, cap: int, d_model: int, num_heads: int, kernel: str = _lib.DEFAULT_KERNEL, device="cuda"):
+        self.B, self.cap, self.d_model, self.num_heads, self.kernel = int(B), int(cap), int(d_model), int(num_heads), kernel
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("KVCache needs a CUDA device")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        lib = _lib.load()
+        vid = _lib.variant_id(kernel)
+        self._handle = None
+        nbytes = lib.qmha_kv_cache_bytes(self.B, self.cap, self.d_model, self.num_heads, vid)
+        # zero-filled: rows beyond len are never read, but a read-back of the tensor is then reproducible
+        self.mem = torch.zeros(max(nbytes, 1), dtype=torch.uint8, device=self.device)
+        handle = ctypes.c_void_p()
+        st = lib.qmha_kv_cache_create(ctypes.byref(handle), self.mem.data_ptr(), nbytes, self.B, self.cap, self.d_model,
+                                      self.num_heads, vid)
+        _lib.check(st, f"KVCache({kernel})")
+        self._handle = handle
+
+    def __del__(self):
+        if getattr(self, "_handle", None):
+            _lib.load().qmha_kv_cache_destroy(self._handle)
+            self._handle = None
+
+    @property
+    def len(self) -> int:
+        return _lib.load().qmha_kv_cache_len(self._handle)
+
+    def _rows(self, X: torch.Tensor, name: str) -> torch.Tensor:
+        if not X.is_cuda:
+            raise RuntimeError("Inputs must be CUDA tensors")
+        if X.dtype != torch.float32:
+            raise RuntimeError(f"{name} must be float32")
+        if X.device != self.device:
+            raise RuntimeError(f"{name} must be on the cache's device {self.device}")
+        Xc = X.contiguous()
+        if Xc.dim() == 2 and self.B == 1:
+            Xc = Xc.unsqueeze(0)
+        if Xc.dim() != 3 or Xc.shape[0] != self.B or Xc.shape[2] != self.d_model:
+            raise RuntimeError(f"{name} must be [B = {self.B}, n, d_model = {self.d_model}]"
+                               + (" or [n, d_model]" if self.B == 1 else ""))
+        return Xc
+
+    def append(self, K: torch.Tensor, V: torch.Tensor) -> None:
+        Kc, Vc = self._rows(K, "K"), self._rows(V, "V")
+        if Kc.shape != Vc.shape:
+            raise RuntimeError("K and V must have the same shape")
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            st = _lib.load().qmha_kv_cache_append(self._handle, Kc.data_ptr(), Vc.data_ptr(), Kc.shape[1], stream)
+        _lib.check(st, f"KVCache.append({self.kernel})")
+
+    def attend(self, Q: torch.Tensor, causal: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        Qc = self._rows(Q, "Q")
+        if out is None:
+            out = torch.empty_like(Qc)
+        elif (out.numel() != Qc.numel() or out.dtype != torch.float32 or out.device != Qc.device
+              or not out.is_contiguous()):
+            raise RuntimeError("out must be a contiguous float32 tensor of Q's size on Q's device")
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            st = _lib.load().qmha_attend_cached(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[1],
+                                                _lib.QMHA_FLAG_CAUSAL if causal else 0, stream)
+        _lib.check(st, f"KVCache.attend({self.kernel})")
+        return out.view(Q.shape) if out.numel() == Q.numel() and out.dim() != Q.dim() else out
+
+    def truncate(self, n: int) -> None:
+        _lib.check(_lib.load().qmha_kv_cache_truncate(self._handle, int(n)), "KVCache.truncate")
 
 
 def quantize_int8(X: torch.Tensor, d_model: int, num_heads: int, layout: int = 0):

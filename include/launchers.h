@@ -122,6 +122,24 @@ int qmha_solve_rect(const float *Q, const float *K, const float *V, float *O, in
                     int h, int variant, unsigned flags, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * qmha_solve_gqa -- qmha_solve_rect for grouped-query attention (GQA; h_kv = 1: MQA): the h query heads share
+ * h_kv key/value heads, query head k reading K/V head k / (h / h_kv).  Q and O are [B, Nq, d_model]; K and V are
+ * [B, Nk, h_kv * (d_model / h)] (fp32, contiguous, batch outermost).  1 <= h_kv <= h and h % h_kv == 0, otherwise
+ * QMHA_ERR_INVALID; every other rule is qmha_solve_rect's (Nq % 32 == 0, Nk % 32 == 0, QMHA_FLAG_CAUSAL bottom-right
+ * aligned and Nk >= Nq, unknown flag bits QMHA_ERR_INVALID, every check before any HIP call).
+ * There is no size function of its own: K, V and the scratch are those of a call with h_kv heads, so a caller
+ * workspace holds >= qmha_workspace_size(B, Nk, h_kv * (d_model / h), h_kv, variant) bytes.
+ * h_kv == h enqueues exactly what qmha_solve_rect enqueues, for every variant and shape.  h_kv < h is built for
+ * fa_tc_int8_b at d = 32, 64, 128 and fa_tc_v1a at d = 64, 128 (qmha_solve_rect's Nq != Nk set) and runs the
+ * grouped kernels for every Nq and Nk, square and unmasked calls included; every other variant or head size
+ * returns QMHA_ERR_NOSYS (qmha_last_error names the variant, d and "grouped-query") before anything is launched,
+ * leaving O untouched.  The K/V pre-pass runs once per K/V head, and query head k's result is bit-identical to
+ * qmha_solve_rect on K and V expanded to h heads whenever that call takes its rectangular kernel.
+ */
+int qmha_solve_gqa(const float *Q, const float *K, const float *V, float *O, int B, int Nq, int Nk, int d_model, int h,
+                   int h_kv, int variant, unsigned flags, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Persistent K/V cache -- chunked prefill and decode without re-running the K/V pre-pass over rows that were
  * quantised (int8) or converted (fp16) by an earlier call.  A cache is an opaque host object over CALLER-OWNED device
  * memory: qmha_kv_cache_bytes(B, cap, ...) bytes (exactly qmha_workspace_size at N = cap; the layout is that
@@ -153,11 +171,19 @@ int qmha_solve_rect(const float *Q, const float *K, const float *V, float *O, in
  * appends it reads, and an append into rows freed by truncate must follow the attends that still read them.
  * With qmha_profile_enable(1), every append records one pre-pass event pair and every attend one main-kernel pair,
  * each a record of its own (qmha_profile_collect counts one call for each).
+ *
+ * qmha_kv_cache_create_gqa: a cache of h_kv key/value heads shared by h query heads (the rules of qmha_solve_gqa;
+ * h_kv == h is qmha_kv_cache_create).  The memory is qmha_workspace_size(B, cap, h_kv * (d_model / h), h_kv, variant)
+ * bytes -- qmha_kv_cache_bytes at h_kv heads, 1 / (h / h_kv) of the multi-head cache --, append takes K, V of
+ * [B, n, h_kv * (d_model / h)], attend takes Q, O of [B, Nq, d_model] as before and runs the grouped kernels;
+ * truncate and len are unchanged.  h_kv < h with a variant or head size outside qmha_solve_gqa's set: QMHA_ERR_NOSYS.
  */
 typedef struct qmha_kv_cache qmha_kv_cache_t;
 size_t qmha_kv_cache_bytes(int B, int cap, int d_model, int h, int variant);
 int qmha_kv_cache_create(qmha_kv_cache_t **out, void *mem, size_t bytes, int B, int cap, int d_model, int h,
                          int variant);
+int qmha_kv_cache_create_gqa(qmha_kv_cache_t **out, void *mem, size_t bytes, int B, int cap, int d_model, int h,
+                             int h_kv, int variant);
 void qmha_kv_cache_destroy(qmha_kv_cache_t *c);
 int qmha_kv_cache_len(const qmha_kv_cache_t *c);
 int qmha_kv_cache_truncate(qmha_kv_cache_t *c, int len);

@@ -24,10 +24,12 @@ SIGNATURES = {
     "qmha_solve_ex": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "qmha_solve_opts": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_uint, _vp, _sz, _vp]),
     "qmha_solve_rect": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, ctypes.c_uint, _vp, _sz, _vp]),
+    "qmha_solve_gqa": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, ctypes.c_uint, _vp, _sz, _vp]),
     "qmha_workspace_size": (_sz, [_i, _i, _i, _i, _i]),
     # persistent K/V cache: the handle is an opaque pointer
     "qmha_kv_cache_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "qmha_kv_cache_create": (_i, [ctypes.POINTER(_vp), _vp, _sz, _i, _i, _i, _i, _i]),
+    "qmha_kv_cache_create_gqa": (_i, [ctypes.POINTER(_vp), _vp, _sz, _i, _i, _i, _i, _i, _i]),
     "qmha_kv_cache_destroy": (None, [_vp]),
     "qmha_kv_cache_len": (_i, [_vp]),
     "qmha_kv_cache_truncate": (_i, [_vp, _i]),

@@ -355,12 +355,17 @@ qmha::F16Workspace f16_slice(qmha::F16Workspace w, size_t b0, int N, int H, int 
 // Q and O have Nq rows, K and V have N; the pre-passes and the workspaces see K and V only, so they follow N.
 // Nq != N (qmha_solve_rect, checked against the table's `rect` column: int8 / fp16 only) takes the rectangular
 // main kernels; Nq == N enqueues the square paths.
-int run(const float* Q, const float* K, const float* V, float* O, int B, int Nq, int N, int d_model, int h, int variant,
-        unsigned flags, void* ws, WsSlot& slot, hipStream_t stream) {
+// K and V have h_kv heads: [B, N, h_kv * D].  h_kv == h is every call but qmha_solve_gqa's; h_kv < h (checked
+// against the `rect` column too) runs the pre-pass with h_kv heads and takes the grouped main kernels
+// (qmha_fa_gqa.hip) for every Nq and N.
+int run(const float* Q, const float* K, const float* V, float* O, int B, int Nq, int N, int d_model, int h, int h_kv,
+        int variant, unsigned flags, void* ws, WsSlot& slot, hipStream_t stream) {
     const int D = d_model / h;
     const bool causal = flags & QMHA_FLAG_CAUSAL;  // check_flags passed: int8 / fp16 at a built head size
     const bool rect = Nq != N;
     const bool masked = causal || rect;  // qmha_fa_masked.hip; plain square calls keep the non-causal main kernels
+    const bool gqa = h_kv < h;
+    const int kv_model = h_kv * D;  // row width of K and V
     bool prof;
     {
         std::lock_guard<std::mutex> lk(g_prof_mu);
@@ -368,41 +373,43 @@ int run(const float* Q, const float* K, const float* V, float* O, int B, int Nq,
     }
     ProfRec rec;
     Marks *pre_m = prof ? &rec.pre : nullptr, *main_m = prof ? &rec.main : nullptr;
-    const size_t slab = (size_t)N * d_model, qslab = (size_t)Nq * d_model;  // floats per sequence: K and V, Q and O
+    const size_t slab = (size_t)N * kv_model, qslab = (size_t)Nq * d_model;  // floats per sequence: K and V, Q and O
     int st;
     switch (variant) {
         case QMHA_FA_TC_INT8_B: {
-            const qmha::Int8Workspace w8 = qmha::int8_carve(ws, B, N, h, D);
+            const qmha::Int8Workspace w8 = qmha::int8_carve(ws, B, N, h_kv, D);
             st = run_chunked(
                 B, stream, slot, pre_m, main_m, "quant_int8 launch",
                 [&](Chunk c, hipStream_t s) {
-                    const qmha::Int8Workspace w = int8_slice(w8, c.b0, N, h, D);
+                    const qmha::Int8Workspace w = int8_slice(w8, c.b0, N, h_kv, D);
                     return qmha::launch_quant_int8(Q + c.b0 * qslab, K + c.b0 * slab, V + c.b0 * slab, w, w.Vh, /*v_mode=*/1,
-                                                   c.nb, N, h, D, d_model, s, /*first_tensor=*/1);
+                                                   c.nb, N, h_kv, D, kv_model, s, /*first_tensor=*/1);
                 },
-                rect ? "fa_int8 rect launch" : causal ? "fa_int8 causal launch" : "fa_int8 launch",
+                gqa ? "fa_int8 gqa launch" : rect ? "fa_int8 rect launch" : causal ? "fa_int8 causal launch" : "fa_int8 launch",
                 [&](Chunk c) {
-                    const qmha::Int8Workspace w = int8_slice(w8, c.b0, N, h, D);
+                    const qmha::Int8Workspace w = int8_slice(w8, c.b0, N, h_kv, D);
                     const float* q = Q + c.b0 * qslab;
                     float* o = O + c.b0 * qslab;
+                    if (gqa) return qmha::launch_fa_int8_gqa_main(w, q, o, c.nb, Nq, N, h, h_kv, D, d_model, causal, stream);
                     return masked ? qmha::launch_fa_int8_masked_main(w, q, o, c.nb, Nq, N, h, D, d_model, causal, stream)
                                   : qmha::launch_fa_int8_main(w, q, o, c.nb, N, h, D, d_model, stream);
                 });
             break;
         }
         case QMHA_FA_TC_V1A: {
-            const qmha::F16Workspace w16 = qmha::f16_carve(ws, B, N, h, D);
+            const qmha::F16Workspace w16 = qmha::f16_carve(ws, B, N, h_kv, D);
             st = run_chunked(
                 B, stream, slot, pre_m, main_m, "convert_f16 launch",
                 [&](Chunk c, hipStream_t s) {
                     return qmha::launch_convert_f16(Q + c.b0 * qslab, K + c.b0 * slab, V + c.b0 * slab,
-                                                    f16_slice(w16, c.b0, N, h, D), c.nb, N, h, D, d_model, s);
+                                                    f16_slice(w16, c.b0, N, h_kv, D), c.nb, N, h_kv, D, kv_model, s);
                 },
-                rect ? "fa_f16 rect launch" : causal ? "fa_f16 causal launch" : "fa_f16 launch",
+                gqa ? "fa_f16 gqa launch" : rect ? "fa_f16 rect launch" : causal ? "fa_f16 causal launch" : "fa_f16 launch",
                 [&](Chunk c) {
-                    const qmha::F16Workspace w = f16_slice(w16, c.b0, N, h, D);
+                    const qmha::F16Workspace w = f16_slice(w16, c.b0, N, h_kv, D);
                     const float* q = Q + c.b0 * qslab;
                     float* o = O + c.b0 * qslab;
+                    if (gqa) return qmha::launch_fa_f16_gqa_main(w, q, o, c.nb, Nq, N, h, h_kv, D, d_model, causal, stream);
                     return masked ? qmha::launch_fa_f16_masked_main(w, q, o, c.nb, Nq, N, h, D, d_model, causal, stream)
                                   : qmha::launch_fa_f16_main(w, q, o, c.nb, N, h, D, d_model, stream);
                 });
@@ -454,7 +461,7 @@ int solve_on(const float* Q, const float* K, const float* V, float* O, int B, in
     WsLease lease;
     st = lease_workspace(caller_owned ? 0 : need, stream, &lease);
     if (st != QMHA_OK) return st;
-    return run(Q, K, V, O, B, N, N, d_model, h, variant, flags, caller_owned ? caller_ws : lease.ptr, *lease.slot, stream);
+    return run(Q, K, V, O, B, N, N, d_model, h, h, variant, flags, caller_owned ? caller_ws : lease.ptr, *lease.slot, stream);
 }
 
 // qmha_solve_rect: Q / O of Nq rows, K / V of Nk.  Every check runs before any HIP call.  Nq == Nk is solve_on
@@ -484,7 +491,55 @@ int solve_rect_on(const float* Q, const float* K, const float* V, float* O, int 
     WsLease lease;
     st = lease_workspace(caller_owned ? 0 : need, stream, &lease);
     if (st != QMHA_OK) return st;
-    return run(Q, K, V, O, B, Nq, Nk, d_model, h, variant, flags, caller_owned ? caller_ws : lease.ptr, *lease.slot, stream);
+    return run(Q, K, V, O, B, Nq, Nk, d_model, h, h, variant, flags, caller_owned ? caller_ws : lease.ptr, *lease.slot, stream);
+}
+
+// 1 <= h_kv <= h, h % h_kv == 0 (h >= 1 was checked)
+int check_kv_heads(int h, int h_kv) {
+    if (h_kv < 1 || h_kv > h || h % h_kv != 0)
+        return fail(QMHA_ERR_INVALID, "h_kv must divide h and lie in 1..h (h = " + std::to_string(h) + ", h_kv = " +
+                                          std::to_string(h_kv) + ")");
+    return QMHA_OK;
+}
+
+// "grouped-query attention (h_kv < h) is not built for variant X at d = D (...)": the table's `rect` column, whose
+// kernels' grouped siblings it runs
+int check_gqa_built(int variant, int D) {
+    if (built(find_variant(variant)->rect, D)) return QMHA_OK;
+    std::string have;
+    for (const VariantRow& r : kVariants)
+        if (r.rect) have += (have.empty() ? "" : "; ") + std::string(r.name) + ": d = " + d_list(r.rect);
+    return fail(QMHA_ERR_NOSYS, std::string("grouped-query attention (h_kv < h) is not built for variant ") +
+                                    qmha_variant_name(variant) + " at d = " + std::to_string(D) + " (" + have + ")");
+}
+
+// qmha_solve_gqa: qmha_solve_rect with K and V of h_kv heads.  Every check runs before any HIP call.  h_kv == h is
+// solve_rect_on itself; h_kv < h is built for the table's `rect` column and takes the grouped kernels for every
+// Nq and Nk.  The scratch is that of the keys with h_kv heads: workspace_bytes(B, Nk, h_kv, D, variant).
+int solve_gqa_on(const float* Q, const float* K, const float* V, float* O, int B, int Nq, int Nk, int d_model, int h,
+                 int h_kv, int variant, unsigned flags, bool caller_owned, void* caller_ws, size_t caller_bytes,
+                 hipStream_t stream) {
+    int D = 0;
+    int st = check_shape(Q, K, V, O, B, Nq, d_model, h, variant, &D, "Nq");  // Q and O
+    if (st == QMHA_OK) st = check_shape(Q, K, V, O, B, Nk, d_model, h, variant, &D, "Nk");  // K and V (no wider than Q's rows)
+    if (st == QMHA_OK) st = check_kv_heads(h, h_kv);
+    if (st != QMHA_OK) return st;
+    if (h_kv == h)
+        return solve_rect_on(Q, K, V, O, B, Nq, Nk, d_model, h, variant, flags, caller_owned, caller_ws, caller_bytes, stream);
+    st = check_flag_bits(flags);
+    if (st != QMHA_OK) return st;
+    if ((flags & QMHA_FLAG_CAUSAL) && Nq > Nk)
+        return fail(QMHA_ERR_INVALID, "causal attention is bottom-right aligned and needs Nk >= Nq (Nq = " + std::to_string(Nq) +
+                                          ", Nk = " + std::to_string(Nk) + ")");
+    st = check_gqa_built(variant, D);
+    if (st != QMHA_OK) return st;
+    const size_t need = workspace_bytes(B, Nk, h_kv, D, variant);
+    if (caller_owned && caller_bytes < need) return fail(QMHA_ERR_INVALID, "workspace too small");
+    WsLease lease;
+    st = lease_workspace(caller_owned ? 0 : need, stream, &lease);
+    if (st != QMHA_OK) return st;
+    return run(Q, K, V, O, B, Nq, Nk, d_model, h, h_kv, variant, flags, caller_owned ? caller_ws : lease.ptr, *lease.slot,
+               stream);
 }
 
 // The debug hooks' skeleton: `need` bytes of the null stream's slot, body(ws) enqueues the pre-pass and the
@@ -530,7 +585,8 @@ struct qmha_kv_cache {
     std::mutex mu;
     void* mem;
     int B, cap, d_model, h, D, variant;
-    int len;  // valid rows of every head slice
+    int h_kv;  // K/V heads: the memory is the variant's carve at H = h_kv (== h unless created by _create_gqa)
+    int len;   // valid rows of every head slice
 };
 
 int qmha::tune_config(const char* env_name) {
@@ -578,6 +634,12 @@ int qmha_solve_rect(const float* Q, const float* K, const float* V, float* O, in
                          (hipStream_t)stream);
 }
 
+int qmha_solve_gqa(const float* Q, const float* K, const float* V, float* O, int B, int Nq, int Nk, int d_model, int h,
+                   int h_kv, int variant, unsigned flags, void* workspace, size_t workspace_bytes_, void* stream) {
+    return solve_gqa_on(Q, K, V, O, B, Nq, Nk, d_model, h, h_kv, variant, flags, workspace != nullptr, workspace,
+                        workspace_bytes_, (hipStream_t)stream);
+}
+
 size_t qmha_workspace_size(int B, int N, int d_model, int h, int variant) {
     if (B < 1 || N < 1 || h < 1 || d_model % h) return 0;
     return workspace_bytes(B, N, h, d_model / h, variant);
@@ -588,25 +650,32 @@ size_t qmha_kv_cache_bytes(int B, int cap, int d_model, int h, int variant) {
     return qmha_workspace_size(B, cap, d_model, h, variant);  // the variant's carve at N = cap
 }
 
-int qmha_kv_cache_create(qmha_kv_cache_t** out, void* mem, size_t bytes, int B, int cap, int d_model, int h, int variant) {
+int qmha_kv_cache_create_gqa(qmha_kv_cache_t** out, void* mem, size_t bytes, int B, int cap, int d_model, int h, int h_kv,
+                             int variant) {
     if (!out) return fail(QMHA_ERR_INVALID, "null cache handle pointer");
     *out = nullptr;
     if (!mem) return fail(QMHA_ERR_INVALID, "null cache memory");
     int D = 0;
     int st = check_shape(mem, mem, mem, mem, B, cap, d_model, h, variant, &D, "cap");  // cap >= 32, cap % 32 == 0
-    if (st == QMHA_OK) st = check_cache_built(variant, D);
+    if (st == QMHA_OK) st = check_kv_heads(h, h_kv);
+    if (st == QMHA_OK) st = h_kv < h ? check_gqa_built(variant, D) : check_cache_built(variant, D);
     if (st != QMHA_OK) return st;
     if (reinterpret_cast<uintptr_t>(mem) % 256 != 0) return fail(QMHA_ERR_INVALID, "cache memory must be 256-byte aligned");
-    const size_t need = workspace_bytes(B, cap, h, D, variant);
+    const size_t need = workspace_bytes(B, cap, h_kv, D, variant);
     if (bytes < need)
         return fail(QMHA_ERR_INVALID, "cache memory too small: " + std::to_string(bytes) + " bytes, qmha_kv_cache_bytes is " +
                                           std::to_string(need));
     qmha_kv_cache* c = new qmha_kv_cache;
     c->mem = mem;
     c->B = B, c->cap = cap, c->d_model = d_model, c->h = h, c->D = D, c->variant = variant;
+    c->h_kv = h_kv;
     c->len = 0;
     *out = c;
     return QMHA_OK;
+}
+
+int qmha_kv_cache_create(qmha_kv_cache_t** out, void* mem, size_t bytes, int B, int cap, int d_model, int h, int variant) {
+    return qmha_kv_cache_create_gqa(out, mem, bytes, B, cap, d_model, h, h, variant);
 }
 
 void qmha_kv_cache_destroy(qmha_kv_cache_t* c) { delete c; }
@@ -643,10 +712,10 @@ int qmha_kv_cache_append(qmha_kv_cache_t* c, const float* K, const float* V, int
     const int st = timed(prof ? &rec.pre : nullptr, s, "kv_cache append launch", [&] {
         const hipError_t e =
             c->variant == QMHA_FA_TC_INT8_B
-                ? qmha::launch_kv_append_int8(K, V, qmha::int8_carve(c->mem, c->B, c->cap, c->h, c->D), c->B, n, c->cap, c->len,
-                                              c->h, c->D, c->d_model, s)
-                : qmha::launch_kv_append_f16(K, V, qmha::f16_carve(c->mem, c->B, c->cap, c->h, c->D), c->B, n, c->cap, c->len,
-                                             c->h, c->D, c->d_model, s);
+                ? qmha::launch_kv_append_int8(K, V, qmha::int8_carve(c->mem, c->B, c->cap, c->h_kv, c->D), c->B, n, c->cap,
+                                              c->len, c->h_kv, c->D, c->h_kv * c->D, s)
+                : qmha::launch_kv_append_f16(K, V, qmha::f16_carve(c->mem, c->B, c->cap, c->h_kv, c->D), c->B, n, c->cap,
+                                             c->len, c->h_kv, c->D, c->h_kv * c->D, s);
         launched = e == hipSuccess;
         return e;
     });
@@ -675,6 +744,12 @@ int qmha_attend_cached(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, uns
     const bool prof = profiling_on();
     ProfRec rec;
     st = timed(prof ? &rec.main : nullptr, s, "kv_cache attend launch", [&] {
+        if (c->h_kv < c->h)  // grouped: the carve has h_kv heads
+            return c->variant == QMHA_FA_TC_INT8_B
+                       ? qmha::launch_fa_int8_gqa_cached(qmha::int8_carve(c->mem, c->B, c->cap, c->h_kv, c->D), Q, O, c->B, Nq,
+                                                         c->cap, len, c->h, c->h_kv, c->D, c->d_model, causal, s)
+                       : qmha::launch_fa_f16_gqa_cached(qmha::f16_carve(c->mem, c->B, c->cap, c->h_kv, c->D), Q, O, c->B, Nq,
+                                                        c->cap, len, c->h, c->h_kv, c->D, c->d_model, causal, s);
         return c->variant == QMHA_FA_TC_INT8_B
                    ? qmha::launch_fa_int8_masked_cached(qmha::int8_carve(c->mem, c->B, c->cap, c->h, c->D), Q, O, c->B, Nq, c->cap,
                                                         len, c->h, c->D, c->d_model, causal, s)

@@ -187,6 +187,20 @@ hipError_t launch_fa_int8_masked_cached(const Int8Workspace& w, const float* Qf,
 hipError_t launch_fa_f16_masked_cached(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int cap, int len,
                                        int H, int D, int d_model, bool causal, hipStream_t stream);
 
+// ---- grouped-query attention (qmha_fa_gqa.hip) ------------------------------------
+// H query heads share Hkv < H key/value heads (H % Hkv == 0).  Q / O: [B, Nq, d_model = H * D]; w: the variant's
+// carve over K / V of [B, Nk, Hkv * D], i.e. at H = Hkv (the pre-passes and the appends run unchanged with H = Hkv
+// and d_model = Hkv * D).  Shapes, mask and head sizes as launch_fa_*_masked_main / _cached above, for every Nq
+// and Nk (square and unmasked calls included); anything else, Hkv == H too: hipErrorInvalidValue.
+hipError_t launch_fa_int8_gqa_main(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int Hkv,
+                                   int D, int d_model, bool causal, hipStream_t stream);
+hipError_t launch_fa_f16_gqa_main(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int Hkv,
+                                  int D, int d_model, bool causal, hipStream_t stream);
+hipError_t launch_fa_int8_gqa_cached(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int cap, int len, int H,
+                                     int Hkv, int D, int d_model, bool causal, hipStream_t stream);
+hipError_t launch_fa_f16_gqa_cached(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int cap, int len, int H,
+                                    int Hkv, int D, int d_model, bool causal, hipStream_t stream);
+
 // ---- FP32 (fa: scalar VALU kernel; fa_mfma: the same contract on v_mfma_f32_32x32x2_f32) -----
 hipError_t launch_fa_f32(const float* Q, const float* K, const float* V, float* O, int B, int N, int H, int D,
                          int d_model, bool mfma, hipStream_t stream);

@@ -14,6 +14,8 @@
 //   * `flash_solve_rect` (a second function, same arguments): K and V of one shape, Q with its own row count,
 //     through qmha_solve_rect; `flash_solve` itself still wants one shape;
 //   * `KVCache` (a class): a persistent quantised K/V cache through qmha_kv_cache_* / qmha_attend_cached;
+//   * `flash_solve_gqa` and `GroupedKVCache`: the two above with `num_kv_heads` K/V heads shared by the query heads
+//     (grouped-query attention, qmha_solve_gqa / qmha_kv_cache_create_gqa); None is the multi-head form;
 //   * a rejected shape raises (TORCH_CHECK on the C-ABI status) instead of a device assert.
 #include <torch/extension.h>
 // ROCm PyTorch reports HIP devices as device type "cuda": the guard / current-stream
@@ -21,6 +23,7 @@
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
+#include <optional>
 #include <string>
 
 #include "launchers.h"
@@ -64,8 +67,9 @@ static Tensor flash_solve(const Tensor& Q, const Tensor& K, const Tensor& V, int
 
 // flash_solve with a query length of its own (qmha_solve_rect): K and V share one shape, Q has its own row
 // count and the same batch count; the result is shaped like Q.  causal: bottom-right aligned.
-static Tensor flash_solve_rect(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t d_model, int64_t num_heads,
-                               const std::string& kernel = "fa_tc_int8_b", bool causal = false) {
+// num_kv_heads (flash_solve_gqa): K and V are [Nk, num_kv_heads * d] or [B, Nk, num_kv_heads * d]; none: flash_solve_rect
+static Tensor solve_rect(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t d_model, int64_t num_heads,
+                         std::optional<int64_t> num_kv_heads, const std::string& kernel, bool causal, const char* what) {
     TORCH_CHECK(Q.is_cuda() && K.is_cuda() && V.is_cuda(), "Inputs must be CUDA tensors");
     TORCH_CHECK(Q.dtype() == torch::kFloat32, "Q must be float32");
     TORCH_CHECK(K.dtype() == torch::kFloat32, "K must be float32");
@@ -75,14 +79,21 @@ static Tensor flash_solve_rect(const Tensor& Q, const Tensor& K, const Tensor& V
     auto Vc = V.contiguous();
     TORCH_CHECK(d_model > 0 && Qc.numel() % d_model == 0, "Q.numel() must be divisible by d_model");
     TORCH_CHECK(Kc.sizes() == Vc.sizes(), "K and V must have the same shape");
-    TORCH_CHECK(Kc.numel() % d_model == 0, "K.numel() must be divisible by d_model");
-    const auto rows = [d_model](const Tensor& t, int64_t* B) {  // flash_solve's shape rule
-        const bool batched = t.dim() == 3 && t.size(2) == d_model;
+    int64_t kv_model = d_model;
+    if (num_kv_heads) {
+        TORCH_CHECK(num_heads >= 1 && d_model % num_heads == 0 && *num_kv_heads >= 1,
+                    "d_model must be divisible by num_heads, and num_kv_heads positive");
+        kv_model = *num_kv_heads * (d_model / num_heads);
+    }
+    TORCH_CHECK(Kc.numel() % kv_model == 0,
+                num_kv_heads ? "K.numel() must be divisible by num_kv_heads * d" : "K.numel() must be divisible by d_model");
+    const auto rows = [](const Tensor& t, int64_t width, int64_t* B) {  // flash_solve's shape rule
+        const bool batched = t.dim() == 3 && t.size(2) == width;
         *B = batched ? t.size(0) : 1;
-        return batched ? t.size(1) : t.numel() / d_model;
+        return batched ? t.size(1) : t.numel() / width;
     };
     int64_t B = 1, Bk = 1;
-    const int64_t Nq = rows(Qc, &B), Nk = rows(Kc, &Bk);
+    const int64_t Nq = rows(Qc, d_model, &B), Nk = rows(Kc, kv_model, &Bk);
     TORCH_CHECK(B == Bk, "Q and K must have the same batch count");
     int variant = qmha_variant_from_name(kernel.c_str());
     if (variant < 0) {
@@ -93,29 +104,58 @@ static Tensor flash_solve_rect(const Tensor& Q, const Tensor& K, const Tensor& V
     auto out = torch::empty_like(Qc);
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(Qc.device());
     const hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(Qc.device().index()).stream();
-    const int st = qmha_solve_rect(Qc.data_ptr<float>(), Kc.data_ptr<float>(), Vc.data_ptr<float>(),
-                                   out.data_ptr<float>(), static_cast<int>(B), static_cast<int>(Nq), static_cast<int>(Nk),
-                                   static_cast<int>(d_model), static_cast<int>(num_heads), variant,
-                                   causal ? QMHA_FLAG_CAUSAL : 0u, nullptr, 0, stream);
-    TORCH_CHECK(st == QMHA_OK, "flash_solve_rect(", kernel, "): ", qmha_status_string(st), ": ", qmha_last_error());
+    const unsigned flags = causal ? QMHA_FLAG_CAUSAL : 0u;
+    const int st =
+        num_kv_heads
+            ? qmha_solve_gqa(Qc.data_ptr<float>(), Kc.data_ptr<float>(), Vc.data_ptr<float>(), out.data_ptr<float>(),
+                             static_cast<int>(B), static_cast<int>(Nq), static_cast<int>(Nk), static_cast<int>(d_model),
+                             static_cast<int>(num_heads), static_cast<int>(*num_kv_heads), variant, flags, nullptr, 0, stream)
+            : qmha_solve_rect(Qc.data_ptr<float>(), Kc.data_ptr<float>(), Vc.data_ptr<float>(), out.data_ptr<float>(),
+                              static_cast<int>(B), static_cast<int>(Nq), static_cast<int>(Nk), static_cast<int>(d_model),
+                              static_cast<int>(num_heads), variant, flags, nullptr, 0, stream);
+    TORCH_CHECK(st == QMHA_OK, what, "(", kernel, "): ", qmha_status_string(st), ": ", qmha_last_error());
     return out;
+}
+
+static Tensor flash_solve_rect(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t d_model, int64_t num_heads,
+                               const std::string& kernel = "fa_tc_int8_b", bool causal = false) {
+    return solve_rect(Q, K, V, d_model, num_heads, std::nullopt, kernel, causal, "flash_solve_rect");
+}
+
+// flash_solve_rect for grouped-query attention (qmha_solve_gqa); num_kv_heads = None is flash_solve_rect
+static Tensor flash_solve_gqa(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t d_model, int64_t num_heads,
+                              std::optional<int64_t> num_kv_heads, const std::string& kernel = "fa_tc_int8_b",
+                              bool causal = false) {
+    return solve_rect(Q, K, V, d_model, num_heads, num_kv_heads, kernel, causal, "flash_solve_gqa");
 }
 
 // A persistent quantised K/V cache (qmha_kv_cache_*): the compiled form of quantizedmha_amd/torch_ext.py's KVCache.
 // Owns a uint8 tensor of qmha_kv_cache_bytes and the host handle; append / attend run on PyTorch's current stream.
 class KVCache {
 public:
-    KVCache(int64_t B, int64_t cap, int64_t d_model, int64_t num_heads, const std::string& kernel, const std::string& device)
-        : B_(B), cap_(cap), d_model_(d_model), kernel_(kernel) {
+    // num_kv_heads (GroupedKVCache): the cache holds that many K/V heads, shared by the num_heads query heads
+    KVCache(int64_t B, int64_t cap, int64_t d_model, int64_t num_heads, const std::string& kernel, const std::string& device,
+            std::optional<int64_t> num_kv_heads = std::nullopt)
+        : B_(B), cap_(cap), d_model_(d_model), kv_model_(d_model), kernel_(kernel) {
         const int variant = qmha_variant_from_name(kernel.c_str());
         TORCH_CHECK(variant >= 0, "KVCache: unknown kernel '", kernel, "'");
         c10::Device dev(device);
         TORCH_CHECK(dev.is_cuda(), "KVCache needs a CUDA device");
-        const size_t bytes = qmha_kv_cache_bytes(static_cast<int>(B), static_cast<int>(cap), static_cast<int>(d_model),
-                                                 static_cast<int>(num_heads), variant);
+        // grouped: the row width of K and V (a bad head count is left to the library's checks) and the carve of h_kv heads
+        if (num_kv_heads && num_heads > 0 && d_model % num_heads == 0) kv_model_ = *num_kv_heads * (d_model / num_heads);
+        const size_t bytes =
+            num_kv_heads ? (*num_kv_heads > 0 ? qmha_kv_cache_bytes(static_cast<int>(B), static_cast<int>(cap),
+                                                                    static_cast<int>(kv_model_), static_cast<int>(*num_kv_heads), variant)
+                                              : 0)
+                         : qmha_kv_cache_bytes(static_cast<int>(B), static_cast<int>(cap), static_cast<int>(d_model),
+                                               static_cast<int>(num_heads), variant);
         mem_ = torch::zeros({static_cast<int64_t>(bytes > 0 ? bytes : 1)}, torch::TensorOptions().dtype(torch::kUInt8).device(dev));
-        const int st = qmha_kv_cache_create(&handle_, mem_.data_ptr(), bytes, static_cast<int>(B), static_cast<int>(cap),
-                                            static_cast<int>(d_model), static_cast<int>(num_heads), variant);
+        const int st =
+            num_kv_heads
+                ? qmha_kv_cache_create_gqa(&handle_, mem_.data_ptr(), bytes, static_cast<int>(B), static_cast<int>(cap),
+                                           static_cast<int>(d_model), static_cast<int>(num_heads), static_cast<int>(*num_kv_heads), variant)
+                : qmha_kv_cache_create(&handle_, mem_.data_ptr(), bytes, static_cast<int>(B), static_cast<int>(cap),
+                                       static_cast<int>(d_model), static_cast<int>(num_heads), variant);
         TORCH_CHECK(st == QMHA_OK, "KVCache(", kernel, "): ", qmha_status_string(st), ": ", qmha_last_error());
     }
     ~KVCache() { qmha_kv_cache_destroy(handle_); }
@@ -127,7 +167,7 @@ public:
     Tensor mem() const { return mem_; }
 
     void append(const Tensor& K, const Tensor& V) {
-        auto Kc = rows(K, "K"), Vc = rows(V, "V");
+        auto Kc = rows(K, "K", kv_model_), Vc = rows(V, "V", kv_model_);
         TORCH_CHECK(Kc.sizes() == Vc.sizes(), "K and V must have the same shape");
         const c10::hip::HIPGuardMasqueradingAsCUDA guard(mem_.device());
         const hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(mem_.device().index()).stream();
@@ -136,7 +176,7 @@ public:
     }
 
     Tensor attend(const Tensor& Q, bool causal) {
-        auto Qc = rows(Q, "Q");
+        auto Qc = rows(Q, "Q", d_model_);
         auto out = torch::empty_like(Qc);
         const c10::hip::HIPGuardMasqueradingAsCUDA guard(mem_.device());
         const hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(mem_.device().index()).stream();
@@ -153,20 +193,28 @@ public:
 
 private:
     // [B, n, d_model] fp32 on the cache's device, contiguous; [n, d_model] for B = 1
-    Tensor rows(const Tensor& X, const char* name) const {
+    Tensor rows(const Tensor& X, const char* name, int64_t width) const {
         TORCH_CHECK(X.is_cuda(), "Inputs must be CUDA tensors");
         TORCH_CHECK(X.dtype() == torch::kFloat32, name, " must be float32");
         TORCH_CHECK(X.device() == mem_.device(), name, " must be on the cache's device");
         auto Xc = X.contiguous();
         if (Xc.dim() == 2 && B_ == 1) Xc = Xc.unsqueeze(0);
-        TORCH_CHECK(Xc.dim() == 3 && Xc.size(0) == B_ && Xc.size(2) == d_model_, name, " must be [B = ", B_, ", n, d_model = ",
-                    d_model_, "]", B_ == 1 ? " or [n, d_model]" : "");
+        TORCH_CHECK(Xc.dim() == 3 && Xc.size(0) == B_ && Xc.size(2) == width, name, " must be [B = ", B_, ", n, d_model = ",
+                    width, "]", B_ == 1 ? " or [n, d_model]" : "");
         return Xc;
     }
-    int64_t B_, cap_, d_model_;
+    int64_t B_, cap_, d_model_, kv_model_;
     std::string kernel_;
     Tensor mem_;
     qmha_kv_cache_t* handle_ = nullptr;
+};
+
+// KVCache over num_kv_heads K/V heads (qmha_kv_cache_create_gqa): a class of its own, KVCache keeps its argument list
+class GroupedKVCache : public KVCache {
+public:
+    GroupedKVCache(int64_t B, int64_t cap, int64_t d_model, int64_t num_heads, std::optional<int64_t> num_kv_heads,
+                   const std::string& kernel, const std::string& device)
+        : KVCache(B, cap, d_model, num_heads, kernel, device, num_kv_heads) {}
 };
 
 PYBIND11_MODULE(torch_ext, m) {
@@ -182,6 +230,27 @@ PYBIND11_MODULE(torch_ext, m) {
         .def_property_readonly("len", &KVCache::len)
         .def_property_readonly("cap", &KVCache::cap)
         .def_property_readonly("mem", &KVCache::mem);
+    pybind11::class_<GroupedKVCache, KVCache>(m, "GroupedKVCache",
+                                              "KVCache for grouped-query attention: num_kv_heads K/V heads shared by the num_heads\n"
+                                              "query heads; append(K, V) takes [B, n, num_kv_heads * d].")
+        .def(pybind11::init<int64_t, int64_t, int64_t, int64_t, std::optional<int64_t>, const std::string&, const std::string&>(),
+             pybind11::arg("B"), pybind11::arg("cap"), pybind11::arg("d_model"), pybind11::arg("num_heads"),
+             pybind11::arg("num_kv_heads") = pybind11::none(), pybind11::arg("kernel") = "fa_tc_int8_b",
+             pybind11::arg("device") = "cuda");
+    m.def("flash_solve_gqa", &flash_solve_gqa,
+          "FlashAttention solve with grouped K/V heads and separate query and key lengths (HIP, MI355X)\n\n"
+          "Args:\n"
+          "  Q: Query tensor [Nq, d_model] (or [B, Nq, d_model])\n"
+          "  K: Key tensor [Nk, num_kv_heads * d] (or [B, Nk, num_kv_heads * d]), d = d_model / num_heads\n"
+          "  V: Value tensor, shaped like K\n"
+          "  d_model: Model dimension\n"
+          "  num_heads: Number of query heads\n"
+          "  num_kv_heads: Number of K/V heads, a divisor of num_heads (default: None = num_heads)\n"
+          "  kernel: Kernel variant (default: 'fa_tc_int8_b')\n"
+          "  causal: bottom-right aligned, query row r attends keys j <= r + (Nk - Nq) (default: False)",
+          pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("d_model"),
+          pybind11::arg("num_heads"), pybind11::arg("num_kv_heads") = pybind11::none(),
+          pybind11::arg("kernel") = "fa_tc_int8_b", pybind11::arg("causal") = false);
     m.def("flash_solve_rect", &flash_solve_rect,
           "FlashAttention solve with separate query and key lengths (HIP, MI355X)\n\n"
           "Args:\n"

@@ -16,6 +16,7 @@ ROCm tensors report device type 'cuda', exactly as the reference's is_cuda() che
 flash_solve_rect (additive, no reference counterpart) is flash_solve with a query length of its own: K and V
 share one shape, Q has its own row count (cross-attention, chunked prefill; qmha_solve_rect).
 KVCache (additive) keeps the pre-passed K and V of earlier chunks: append new rows, attend with the last Nq.
+Both take num_kv_heads (additive, default None = num_heads): grouped-query attention, K and V of num_kv_heads heads.
 """
 from __future__ import annotations
 
@@ -87,6 +88,21 @@ def flash_solve_rect(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, d_model:
     like Q.  causal: bottom-right aligned, query row r attends keys j <= r + (Nk - Nq) (the Nq queries are the
     last Nq positions of a sequence of Nk; Nk >= Nq).  Nq != Nk: fa_tc_int8_b at d = 32 / 64 / 128 and
     fa_tc_v1a at d = 64 / 128; anything else raises.  Arguments and error behaviour as flash_solve."""
+    return _solve_rect(Q, K, V, d_model, num_heads, None, kernel, out, causal, "flash_solve_rect")
+
+
+def flash_solve_gqa(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, d_model: int, num_heads: int,
+                    num_kv_heads: Optional[int] = None, kernel: str = _lib.DEFAULT_KERNEL,
+                    out: Optional[torch.Tensor] = None, causal: bool = False) -> torch.Tensor:
+    """flash_solve_rect for grouped-query attention (qmha_solve_gqa): K and V are [Nk, num_kv_heads * d] or
+    [B, Nk, num_kv_heads * d] (d = d_model / num_heads) and query head k reads K/V head
+    k // (num_heads // num_kv_heads).  With fewer K/V heads than heads: fa_tc_int8_b at d = 32 / 64 / 128 and
+    fa_tc_v1a at d = 64 / 128, for every Nq and Nk; anything else raises.  num_kv_heads = None is flash_solve_rect.
+    (A function of its own: flash_solve_rect keeps the argument list its callers and tests know.)"""
+    return _solve_rect(Q, K, V, d_model, num_heads, num_kv_heads, kernel, out, causal, "flash_solve_gqa")
+
+
+def _solve_rect(Q, K, V, d_model, num_heads, num_kv_heads, kernel, out, causal, what):
     if not (Q.is_cuda and K.is_cuda and V.is_cuda):
         raise RuntimeError("Inputs must be CUDA tensors")
     for name, t in (("Q", Q), ("K", K), ("V", V)):
@@ -97,9 +113,16 @@ def flash_solve_rect(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, d_model:
     B, Nq = _shape(Qc, d_model)
     if Kc.shape != Vc.shape:
         raise RuntimeError("K and V must have the same shape")
-    if Kc.numel() % d_model != 0:
-        raise RuntimeError("K.numel() must be divisible by d_model")
-    Bk, Nk = _shape(Kc, d_model)
+    kv_model = d_model
+    if num_kv_heads is not None:
+        num_kv_heads = int(num_kv_heads)
+        if num_heads < 1 or d_model % num_heads != 0 or num_kv_heads < 1:
+            raise RuntimeError("d_model must be divisible by num_heads, and num_kv_heads positive")
+        kv_model = num_kv_heads * (d_model // num_heads)
+    if Kc.numel() % kv_model != 0:
+        raise RuntimeError("K.numel() must be divisible by d_model" if num_kv_heads is None
+                           else "K.numel() must be divisible by num_kv_heads * d")
+    Bk, Nk = _shape(Kc, kv_model)
     if Bk != B:
         raise RuntimeError("Q and K must have the same batch count")
     if kernel not in _lib.VARIANTS:
@@ -114,10 +137,14 @@ def flash_solve_rect(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, d_model:
     lib = _lib.load()
     with torch.cuda.device(Qc.device):
         stream = torch.cuda.current_stream(Qc.device).cuda_stream
-        st = lib.qmha_solve_rect(Qc.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), out.data_ptr(), B, Nq, Nk, d_model,
-                                 num_heads, _lib.variant_id(kernel), _lib.QMHA_FLAG_CAUSAL if causal else 0, None, 0,
-                                 stream)
-    _lib.check(st, f"flash_solve_rect({kernel})")
+        flags = _lib.QMHA_FLAG_CAUSAL if causal else 0
+        if num_kv_heads is None:
+            st = lib.qmha_solve_rect(Qc.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), out.data_ptr(), B, Nq, Nk, d_model,
+                                     num_heads, _lib.variant_id(kernel), flags, None, 0, stream)
+        else:
+            st = lib.qmha_solve_gqa(Qc.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), out.data_ptr(), B, Nq, Nk, d_model,
+                                    num_heads, num_kv_heads, _lib.variant_id(kernel), flags, None, 0, stream)
+    _lib.check(st, f"{what}({kernel})")
     return out
 
 
@@ -132,10 +159,19 @@ class KVCache:
     The object owns a torch.uint8 tensor of qmha_kv_cache_bytes (`.mem`).  append and attend are enqueued on torch's
     current stream; the caller keeps the operations on one cache ordered (one stream, or its own events).
     attend(Q, causal=False) needs a full cache (len == cap): every row attends all cap rows.  truncate(n) drops rows
-    from the end (n % 32 == 0, n <= len); nothing is enqueued."""
+    from the end (n % 32 == 0, n <= len); nothing is enqueued.  GroupedKVCache (below) is the same cache over fewer
+    K/V heads than query heads."""
 
     def __init__(self, B: int, cap: int, d_model: int, num_heads: int, kernel: str = _lib.DEFAULT_KERNEL, device="cuda"):
+        self._setup(B, cap, d_model, num_heads, None, kernel, device)
+
+    def _setup(self, B, cap, d_model, num_heads, num_kv_heads, kernel, device):
         self.B, self.cap, self.d_model, self.num_heads, self.kernel = int(B), int(cap), int(d_model), int(num_heads), kernel
+        self.num_kv_heads = self.num_heads if num_kv_heads is None else int(num_kv_heads)
+        # row width of K and V (d_model unless grouped; a bad head count is left to the library's checks)
+        self.kv_model = self.d_model
+        if num_kv_heads is not None and self.num_heads > 0 and self.d_model % self.num_heads == 0:
+            self.kv_model = self.num_kv_heads * (self.d_model // self.num_heads)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("KVCache needs a CUDA device")
@@ -144,12 +180,19 @@ class KVCache:
         lib = _lib.load()
         vid = _lib.variant_id(kernel)
         self._handle = None
-        nbytes = lib.qmha_kv_cache_bytes(self.B, self.cap, self.d_model, self.num_heads, vid)
+        if num_kv_heads is None:
+            nbytes = lib.qmha_kv_cache_bytes(self.B, self.cap, self.d_model, self.num_heads, vid)
+        else:  # the carve of num_kv_heads heads
+            nbytes = lib.qmha_kv_cache_bytes(self.B, self.cap, self.kv_model, self.num_kv_heads, vid) if self.num_kv_heads > 0 else 0
         # zero-filled: rows beyond len are never read, but a read-back of the tensor is then reproducible
         self.mem = torch.zeros(max(nbytes, 1), dtype=torch.uint8, device=self.device)
         handle = ctypes.c_void_p()
-        st = lib.qmha_kv_cache_create(ctypes.byref(handle), self.mem.data_ptr(), nbytes, self.B, self.cap, self.d_model,
-                                      self.num_heads, vid)
+        if num_kv_heads is None:
+            st = lib.qmha_kv_cache_create(ctypes.byref(handle), self.mem.data_ptr(), nbytes, self.B, self.cap, self.d_model,
+                                          self.num_heads, vid)
+        else:
+            st = lib.qmha_kv_cache_create_gqa(ctypes.byref(handle), self.mem.data_ptr(), nbytes, self.B, self.cap,
+                                              self.d_model, self.num_heads, self.num_kv_heads, vid)
         _lib.check(st, f"KVCache({kernel})")
         self._handle = handle
 
@@ -162,7 +205,8 @@ class KVCache:
     def len(self) -> int:
         return _lib.load().qmha_kv_cache_len(self._handle)
 
-    def _rows(self, X: torch.Tensor, name: str) -> torch.Tensor:
+    def _rows(self, X: torch.Tensor, name: str, width: Optional[int] = None) -> torch.Tensor:
+        width = self.d_model if width is None else width
         if not X.is_cuda:
             raise RuntimeError("Inputs must be CUDA tensors")
         if X.dtype != torch.float32:
@@ -172,13 +216,13 @@ class KVCache:
         Xc = X.contiguous()
         if Xc.dim() == 2 and self.B == 1:
             Xc = Xc.unsqueeze(0)
-        if Xc.dim() != 3 or Xc.shape[0] != self.B or Xc.shape[2] != self.d_model:
-            raise RuntimeError(f"{name} must be [B = {self.B}, n, d_model = {self.d_model}]"
+        if Xc.dim() != 3 or Xc.shape[0] != self.B or Xc.shape[2] != width:
+            raise RuntimeError(f"{name} must be [B = {self.B}, n, d_model = {width}]"
                                + (" or [n, d_model]" if self.B == 1 else ""))
         return Xc
 
     def append(self, K: torch.Tensor, V: torch.Tensor) -> None:
-        Kc, Vc = self._rows(K, "K"), self._rows(V, "V")
+        Kc, Vc = self._rows(K, "K", self.kv_model), self._rows(V, "V", self.kv_model)
         if Kc.shape != Vc.shape:
             raise RuntimeError("K and V must have the same shape")
         with torch.cuda.device(self.device):
@@ -202,6 +246,17 @@ class KVCache:
 
     def truncate(self, n: int) -> None:
         _lib.check(_lib.load().qmha_kv_cache_truncate(self._handle, int(n)), "KVCache.truncate")
+
+
+class GroupedKVCache(KVCache):
+    """KVCache for grouped-query attention (qmha_kv_cache_create_gqa): the cache holds num_kv_heads K/V heads shared
+    by the num_heads query heads, append takes [B, n, num_kv_heads * d] (d = d_model / num_heads), attend takes
+    [B, Nq, d_model] as before, and `.mem` is num_heads / num_kv_heads times smaller.  num_kv_heads = None is KVCache.
+    (A class of its own: KVCache keeps the argument list its callers and tests know.)"""
+
+    def __init__(self, B: int, cap: int, d_model: int, num_heads: int, num_kv_heads: Optional[int] = None,
+                 kernel: str = _lib.DEFAULT_KERNEL, device="cuda"):
+        self._setup(B, cap, d_model, num_heads, num_kv_heads, kernel, device)
 
 
 def quantize_int8(X: torch.Tensor, d_model: int, num_heads: int, layout: int = 0):

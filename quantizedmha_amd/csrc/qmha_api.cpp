@@ -357,7 +357,7 @@ qmha::F16Workspace f16_slice(qmha::F16Workspace w, size_t b0, int N, int H, int 
 // main kernels; Nq == N enqueues the square paths.
 // K and V have h_kv heads: [B, N, h_kv * D].  h_kv == h is every call but qmha_solve_gqa's; h_kv < h (checked
 // against the `rect` column too) runs the pre-pass with h_kv heads and takes the grouped main kernels
-// (qmha_fa_gqa.hip) for every Nq and N.
+// (qmha_fa_masked.hip's Grouped instances) for every Nq and N.
 int run(const float* Q, const float* K, const float* V, float* O, int B, int Nq, int N, int d_model, int h, int h_kv,
         int variant, unsigned flags, void* ws, WsSlot& slot, hipStream_t stream) {
     const int D = d_model / h;

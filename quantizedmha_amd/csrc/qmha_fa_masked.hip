@@ -1,7 +1,8 @@
 // qmha_fa_masked.hip -- the main kernels of the int8 and fp16 fused attention paths that visit a masked or
-// partial set of key tiles, for gfx950 (MI355X): square causal (is_causal=True) and
-// rectangular (Nq != Nk: cross-attention and chunked prefill).  One int8 and one fp16
-// kernel template; a compile-time geometry type (SquareCausal, Rect: below) supplies what differs.
+// partial set of key tiles, for gfx950 (MI355X): square causal (is_causal=True),
+// rectangular (Nq != Nk: cross-attention and chunked prefill) and grouped-query (h query
+// heads on h_kv < h K/V heads).  One int8 and one fp16 kernel template; a compile-time
+// geometry type (SquareCausal, Rect, Grouped: below) supplies what differs.
 //
 // Square causal: query row r attends keys j <= r of its own sequence (Nq = Nk = N).  Both kernels keep the
 // geometry of the non-causal main kernels, so they consume the unchanged pre-pass outputs (qmha_prepass.hip):
@@ -37,9 +38,25 @@
 //   A wave's last tile is min(g + diag_off, Gk - 1); the workgroup's KV loop ends at the stage holding the last
 //   tile of its last active wave, and the partial last stage brings in that many tiles only.  With an offset
 //   every int8 workgroup of a head still costs the same; without the mask both passes cost Gk tiles.
-// Out of range by construction: K/V reads go through buffer descriptors of exactly the (b, h) slice
+// Grouped: Q and O are [B, Nq, h * D], K and V [B, Nk, h_kv * D], G = h / h_kv; the pre-pass runs unchanged with
+// H = h_kv, so the workspace holds B * h_kv slices of Nk rows.  The rows, the diagonal and the cached form are Rect's.
+//   K/V slice.  The launch index's slice is the K/V slice bh = b * h_kv + kvh (the kernels' H argument is the number
+//     of K/V heads, which is h for the other geometries): the K/V bases, the buffer extents and the sK / sV index
+//     use it; query rows and O rows keep d_model = h * D and column k * D of query head k.
+//   Units.  One K/V slice serves U = G * Gq units: unit u = qg * G + j is query group qg of query head
+//     kvh * G + j.  A workgroup holds four consecutive units (nqb = ceil(U / 4)); a wave is active when u < U;
+//     diag and last take qg = u / G.  qg is non-decreasing in u, so the workgroup's last tile is that of its last
+//     active unit.  With G = 4 a workgroup is the four heads of one query group: one shared diagonal, no wave
+//     idle under the mask (decode, Nq = 32: four active waves per workgroup where Rect has one).  G is a
+//     run-time, wave-uniform argument (any G >= 2).  For SquareCausal and Rect a unit is a query group of the
+//     slice's own head: U = Gq, qg = u, k = kvh.
+//   Grid.  B * h_kv * masked_pairs(nqb) for int8 (mirrored unit-block pairs), B * h_kv * nqb for fp16 (heaviest
+//     first); xcd_remap keeps the workgroups of one K/V slice on one XCD, so the G heads re-read K/V from its L2.
+//   A wave's arithmetic and tile order are those of the Rect instance, so a query head's result is that of the
+//   multi-head call on K / V expanded G times, bit for bit.
+// Out of range by construction: K/V reads go through buffer descriptors of exactly the (b, kvh) slice
 // (Nk * D, Nk * 2D bytes) and a stage issues whole tiles t <= Gk - 1 only; sK / sV are read at t <= Gk - 1
-// of slice bh * Gk; Q and O rows are touched by active waves (g < Gq) only.
+// of slice bh * Gk; Q and O rows are touched by active waves only (u < U: qg < Gq, query head < h).
 //
 // int8 (fa_tc_int8_b contract): the tile of qmha_fa_int8_kernel -- i8 MFMA for Q@K^T, exact-integer f16
 //   MFMA for P@V, one sP per 32x32 tile, the anchored O / l state -- on the Ki / Vh / sK / sV workspace.
@@ -58,7 +75,8 @@ static constexpr float kLazySumCapC = 4096.0f;  // the fp16 lazy base's cap (DES
 constexpr int kWaves = 4, kSG = 2;
 
 // The geometry of a launch, a kernel argument: the rows of Q / O and of K / V, and which key tiles query
-// group g visits -- tiles t <= last(g), masked on tile diag(g).
+// group g visits -- tiles t <= last(g), masked on tile diag(g).  And the units of a K/V slice (the header's
+// "Units"): how many, and which query group and query head unit u is.
 // Square causal: the diagonal of group g is tile g, which is also its last; nothing beyond N is passed or
 // computed, so these instances carry no offset and no clamp.
 struct SquareCausal {
@@ -69,6 +87,9 @@ struct SquareCausal {
     __device__ int gk() const { return N / QMHA_GROUP; }
     __device__ int diag(int g) const { return g; }
     __device__ int last(int g) const { return g; }
+    __host__ __device__ int units() const { return N / QMHA_GROUP; }
+    __device__ int group(int u) const { return u; }
+    __device__ int head(int kvh, int u) const { return kvh; }
 };
 // Rectangular.  causal: bottom-right aligned, diag_off = Gk - Gq (Nk >= Nq, checked by the launchers);
 // else diag_off = Gk, a diagonal no tile reaches
@@ -90,12 +111,26 @@ struct Rect {
     __device__ int gk() const { return Nk / QMHA_GROUP; }
     __device__ int diag(int g) const { return g + diag_off; }  // >= Gk: none
     __device__ int last(int g) const { return min(g + diag_off, gk() - 1); }
+    __host__ __device__ int units() const { return Nq / QMHA_GROUP; }
+    __device__ int group(int u) const { return u; }
+    __device__ int head(int kvh, int u) const { return kvh; }
+};
+// Grouped-query: Rect's rows and diagonal (its cached form too), and G query heads per K/V head.  The divisions
+// are unsigned: scalar, through a reciprocal, as the launch-index ones are.
+struct Grouped : Rect {
+    int G;
+    Grouped(Rect r, int g) : Rect(r), G(g) {}
+    __host__ __device__ int units() const { return G * (Nq / QMHA_GROUP); }
+    __device__ int group(int u) const { return (int)((unsigned)u / (unsigned)G); }
+    __device__ int head(int kvh, int u) const { return kvh * G + (int)((unsigned)u % (unsigned)G); }
 };
 
 // A geometry that also carries the buffers of a dumping instance (int8 kernel; QkDump and PDump in
 // qmha_kernels.hpp): the debug hook's twin of a shipped instance, whose own arguments stay as they are.
 template <class Geo>
 struct Dumping : Geo {
+    // the dump's arrays are indexed by the query slice b * h + k, which the kernel takes to be its K/V slice
+    static_assert(!std::is_same<Geo, Grouped>::value, "the dump indexes by query slice: Grouped has no twin");
     static constexpr bool kDump = true;
     QkDump qk;
     PDump pd;
@@ -165,10 +200,10 @@ __global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_int8_mask
     __shared__ __attribute__((aligned(16))) char lds[2][KBYTES + VBYTES];
 
     const int Nq = geo.nq(), Nk = geo.nk();
-    const int Gq = Nq / QMHA_GROUP, Gk = geo.gk();
+    const int Gq = Nq / QMHA_GROUP, Gk = geo.gk(), U = geo.units();
     int bh, pi;
     masked_wg(nqb, bh, pi);
-    const int b = bh / H, k = bh % H;
+    const int b = bh / H, kvh = bh % H;  // bh: the K/V slice (H K/V heads)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int half = lane >> 5, col = lane & 31;
@@ -176,10 +211,11 @@ __global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_int8_mask
     for (int pass = 0; pass < 2; ++pass) {  // the pair's large q-block, then its mirror (uniform)
     const int qb = pass == 0 ? nqb - 1 - pi : pi;
     if (pass == 1 && pi == nqb - 1 - pi) break;  // odd nqb: the middle q-block has no partner
-    const int qg = qb * WAVES + wave;
-    const bool active = qg < Gq;  // wave-uniform; an inactive wave still stages and syncs
+    const int u = qb * WAVES + wave;
+    const bool active = u < U;  // wave-uniform; an inactive wave still stages and syncs
+    const int qg = geo.group(u), k = geo.head(kvh, u);  // query group, query head
     // the workgroup's last tile: that of its last active wave
-    const int wg_last = geo.last(min(qb * WAVES + WAVES - 1, Gq - 1));
+    const int wg_last = geo.last(geo.group(min(qb * WAVES + WAVES - 1, U - 1)));
     const int nst = wg_last / SG + 1;
     const int my_diag = geo.diag(qg);              // this wave's diagonal tile
     const int my_last = active ? geo.last(qg) : -1;  // this wave computes tiles t <= my_last
@@ -418,16 +454,17 @@ __global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_f16_maske
     __shared__ __attribute__((aligned(16))) char lds[2][KBYTES + VBYTES];
 
     const int Nq = geo.nq(), Nk = geo.nk();
-    const int Gq = Nq / QMHA_GROUP;
+    const int U = geo.units();
     int bh, qb0;
     masked_wg_single(nqb, bh, qb0);
-    const int b = bh / H, k = bh % H;
+    const int b = bh / H, kvh = bh % H;  // bh: the K/V slice (H K/V heads)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int qg = qb0 * WAVES + wave;
-    const bool active = qg < Gq;
+    const int u = qb0 * WAVES + wave;
+    const bool active = u < U;
+    const int qg = geo.group(u), k = geo.head(kvh, u);  // query group, query head
     const int grp = lane >> 4, r16 = lane & 15;
-    const int wg_last = geo.last(min(qb0 * WAVES + WAVES - 1, Gq - 1));  // of the last active wave
+    const int wg_last = geo.last(geo.group(min(qb0 * WAVES + WAVES - 1, U - 1)));  // of the last active wave
     const int nst = wg_last / SG + 1;
     const int my_diag = geo.diag(qg);  // this wave's diagonal tile
     const int my_last = active ? geo.last(qg) : -1;
@@ -607,92 +644,121 @@ __global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_f16_maske
 }
 
 // ---------------------------------------------------------------------------------------
-// host launchers: square causal calls take the SquareCausal instances, everything else the Rect ones
+// host launchers: square causal calls take the SquareCausal instances, grouped calls (Hkv < H) the Grouped ones,
+// everything else the Rect ones
 // ---------------------------------------------------------------------------------------
 static bool masked_shape_ok(int Nq, int Nk, bool causal) {
     return Nq >= QMHA_GROUP && Nk >= QMHA_GROUP && Nq % QMHA_GROUP == 0 && Nk % QMHA_GROUP == 0 && !(causal && Nk < Nq);
 }
-static int masked_nqb(int Nq) { return (Nq / QMHA_GROUP + kWaves - 1) / kWaves; }
+// K/V cache: a cache of `cap` rows of which `len` are valid, Nk = cap.  causal: Rect::cached; else
+// every row attends all cap rows, so len == cap.
+static bool cached_shape_ok(int Nq, int cap, int len, bool causal) {
+    if (!masked_shape_ok(Nq, cap, false) || len % QMHA_GROUP != 0) return false;
+    return causal ? Nq <= len && len <= cap : len == cap;
+}
+static Rect cached_geo(int Nq, int cap, int len, bool causal) { return causal ? Rect::cached(Nq, cap, len) : Rect(Nq, cap, false); }
+static bool grouped_heads_ok(int B, int H, int Hkv, int D, int d_model) {
+    return B >= 1 && Hkv >= 1 && Hkv < H && H % Hkv == 0 && d_model == H * D;
+}
+static int masked_nqb(int units) { return (units + kWaves - 1) / kWaves; }  // unit blocks per K/V slice
 
-// `wrap` turns the launch's geometry into the kernel's Geo argument: itself, or Dumping<> for the debug twin.
-// `given`: launch the Rect instance with this geometry (the K/V cache, which has checked it) and not the call's own.
-template <class Wrap>
-static hipError_t fa_int8_masked_launch(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
-                                        int d_model, bool causal, hipStream_t stream, Wrap&& wrap, const Rect* given = nullptr) {
-    if (!given && !masked_shape_ok(Nq, Nk, causal)) return hipErrorInvalidValue;
-    const int nqb = masked_nqb(Nq);
-    auto launch = [&](auto geo, auto d) {
-        hipLaunchKernelGGL((qmha_fa_int8_masked_kernel<decltype(d)::value, decltype(geo)>), dim3(B * H * masked_pairs(nqb)), dim3(kWaves * 64),
-                           0, stream, Qf, w.Ki, w.Vh, w.sK, w.sV, O, geo, H, d_model, nqb, softmax_scale_log2(D));
+// The geometry of a call of its own, checked, handed to `launch`
+template <class Launch>
+static hipError_t masked_call(int Nq, int Nk, bool causal, Launch&& launch) {
+    if (!masked_shape_ok(Nq, Nk, causal)) return hipErrorInvalidValue;
+    return causal && Nq == Nk ? launch(SquareCausal{Nq}) : launch(Rect(Nq, Nk, causal));
+}
+
+// Launch the instance of `geo`, which the caller has checked, over B * H K/V slices
+template <class Geo>
+static hipError_t fa_int8_masked_launch(const Int8Workspace& w, const float* Qf, float* O, int B, int H, int D, int d_model,
+                                        hipStream_t stream, Geo geo) {
+    const int nqb = masked_nqb(geo.units());
+    auto launch = [&](auto d) {
+        hipLaunchKernelGGL((qmha_fa_int8_masked_kernel<decltype(d)::value, Geo>), dim3(B * H * masked_pairs(nqb)), dim3(kWaves * 64), 0,
+                           stream, Qf, w.Ki, w.Vh, w.sK, w.sV, O, geo, H, d_model, nqb, softmax_scale_log2(D));
         return hipGetLastError();
     };
-    auto by_d = [&](auto geo) {
-        switch (D) {
-            case 32: return launch(geo, std::integral_constant<int, 32>{});
-            case 64: return launch(geo, std::integral_constant<int, 64>{});
-            case 128: return launch(geo, std::integral_constant<int, 128>{});
-            default: return hipErrorInvalidValue;
-        }
-    };
-    return !given && causal && Nq == Nk ? by_d(wrap(SquareCausal{Nq})) : by_d(wrap(given ? *given : Rect(Nq, Nk, causal)));
+    switch (D) {
+        case 32: return launch(std::integral_constant<int, 32>{});
+        case 64: return launch(std::integral_constant<int, 64>{});
+        case 128: return launch(std::integral_constant<int, 128>{});
+        default: return hipErrorInvalidValue;
+    }
 }
 
 hipError_t launch_fa_int8_masked_main(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
                                       int d_model, bool causal, hipStream_t stream) {
-    return fa_int8_masked_launch(w, Qf, O, B, Nq, Nk, H, D, d_model, causal, stream, [](auto geo) { return geo; });
+    return masked_call(Nq, Nk, causal, [&](auto geo) { return fa_int8_masked_launch(w, Qf, O, B, H, D, d_model, stream, geo); });
 }
 
 // The dumping twin of the instance launch_fa_int8_masked_main launches for this shape: the same grid and
 // arguments, the geometry wrapped in Dumping<>
 hipError_t launch_fa_int8_masked_pstage_dump(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H,
                                              int D, int d_model, bool causal, QkDump dbg, PDump pd) {
-    return fa_int8_masked_launch(w, Qf, O, B, Nq, Nk, H, D, d_model, causal, nullptr,
-                                 [&](auto geo) { return Dumping<decltype(geo)>(geo, dbg, pd); });
+    return masked_call(Nq, Nk, causal, [&](auto geo) {
+        return fa_int8_masked_launch(w, Qf, O, B, H, D, d_model, nullptr, Dumping<decltype(geo)>(geo, dbg, pd));
+    });
 }
 
-static hipError_t fa_f16_masked_launch(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
-                                       int d_model, bool causal, hipStream_t stream, const Rect* given = nullptr) {
-    if (!given && !masked_shape_ok(Nq, Nk, causal)) return hipErrorInvalidValue;
-    const int nqb = masked_nqb(Nq);
-    auto launch = [&](auto geo, auto d) {
-        hipLaunchKernelGGL((qmha_fa_f16_masked_kernel<decltype(d)::value, decltype(geo)>), dim3(B * H * nqb), dim3(kWaves * 64), 0, stream,
-                           Qf, w.Kh, w.Vt, O, geo, H, d_model, nqb, softmax_scale_log2(D));
+template <class Geo>
+static hipError_t fa_f16_masked_launch(const F16Workspace& w, const float* Qf, float* O, int B, int H, int D, int d_model,
+                                       hipStream_t stream, Geo geo) {
+    const int nqb = masked_nqb(geo.units());
+    auto launch = [&](auto d) {
+        hipLaunchKernelGGL((qmha_fa_f16_masked_kernel<decltype(d)::value, Geo>), dim3(B * H * nqb), dim3(kWaves * 64), 0, stream, Qf,
+                           w.Kh, w.Vt, O, geo, H, d_model, nqb, softmax_scale_log2(D));
         return hipGetLastError();
     };
-    auto by_d = [&](auto geo) {
-        switch (D) {
-            case 64: return launch(geo, std::integral_constant<int, 64>{});
-            case 128: return launch(geo, std::integral_constant<int, 128>{});
-            default: return hipErrorInvalidValue;
-        }
-    };
-    return !given && causal && Nq == Nk ? by_d(SquareCausal{Nq}) : by_d(given ? *given : Rect(Nq, Nk, causal));
+    switch (D) {
+        case 64: return launch(std::integral_constant<int, 64>{});
+        case 128: return launch(std::integral_constant<int, 128>{});
+        default: return hipErrorInvalidValue;
+    }
 }
 
 hipError_t launch_fa_f16_masked_main(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
                                      int d_model, bool causal, hipStream_t stream) {
-    return fa_f16_masked_launch(w, Qf, O, B, Nq, Nk, H, D, d_model, causal, stream);
+    return masked_call(Nq, Nk, causal, [&](auto geo) { return fa_f16_masked_launch(w, Qf, O, B, H, D, d_model, stream, geo); });
 }
 
-// K/V cache: always the Rect instances (also at Nq == len, where a call of its own takes the
-// SquareCausal ones), with Nk = cap.  causal: Rect::cached; else every row attends all cap rows, so len == cap.
-static bool cached_shape_ok(int Nq, int cap, int len, bool causal) {
-    if (!masked_shape_ok(Nq, cap, false) || len % QMHA_GROUP != 0) return false;
-    return causal ? Nq <= len && len <= cap : len == cap;
-}
-
+// K/V cache: always the Rect instances (also at Nq == len, where a call of its own takes the SquareCausal ones)
 hipError_t launch_fa_int8_masked_cached(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int cap, int len,
                                         int H, int D, int d_model, bool causal, hipStream_t stream) {
     if (!cached_shape_ok(Nq, cap, len, causal)) return hipErrorInvalidValue;
-    const Rect geo = causal ? Rect::cached(Nq, cap, len) : Rect(Nq, cap, false);
-    return fa_int8_masked_launch(w, Qf, O, B, Nq, cap, H, D, d_model, causal, stream, [](auto g) { return g; }, &geo);
+    return fa_int8_masked_launch(w, Qf, O, B, H, D, d_model, stream, cached_geo(Nq, cap, len, causal));
 }
 
 hipError_t launch_fa_f16_masked_cached(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int cap, int len,
                                        int H, int D, int d_model, bool causal, hipStream_t stream) {
     if (!cached_shape_ok(Nq, cap, len, causal)) return hipErrorInvalidValue;
-    const Rect geo = causal ? Rect::cached(Nq, cap, len) : Rect(Nq, cap, false);
-    return fa_f16_masked_launch(w, Qf, O, B, Nq, cap, H, D, d_model, causal, stream, &geo);
+    return fa_f16_masked_launch(w, Qf, O, B, H, D, d_model, stream, cached_geo(Nq, cap, len, causal));
+}
+
+// Grouped-query (Hkv < H): always the Grouped instances, for every Nq and Nk, over B * Hkv K/V slices
+hipError_t launch_fa_int8_gqa_main(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int Hkv,
+                                   int D, int d_model, bool causal, hipStream_t stream) {
+    if (!grouped_heads_ok(B, H, Hkv, D, d_model) || !masked_shape_ok(Nq, Nk, causal)) return hipErrorInvalidValue;
+    return fa_int8_masked_launch(w, Qf, O, B, Hkv, D, d_model, stream, Grouped(Rect(Nq, Nk, causal), H / Hkv));
+}
+
+hipError_t launch_fa_f16_gqa_main(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int Hkv,
+                                  int D, int d_model, bool causal, hipStream_t stream) {
+    if (!grouped_heads_ok(B, H, Hkv, D, d_model) || !masked_shape_ok(Nq, Nk, causal)) return hipErrorInvalidValue;
+    return fa_f16_masked_launch(w, Qf, O, B, Hkv, D, d_model, stream, Grouped(Rect(Nq, Nk, causal), H / Hkv));
+}
+
+hipError_t launch_fa_int8_gqa_cached(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int cap, int len, int H,
+                                     int Hkv, int D, int d_model, bool causal, hipStream_t stream) {
+    if (!grouped_heads_ok(B, H, Hkv, D, d_model) || !cached_shape_ok(Nq, cap, len, causal)) return hipErrorInvalidValue;
+    return fa_int8_masked_launch(w, Qf, O, B, Hkv, D, d_model, stream, Grouped(cached_geo(Nq, cap, len, causal), H / Hkv));
+}
+
+hipError_t launch_fa_f16_gqa_cached(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int cap, int len, int H,
+                                    int Hkv, int D, int d_model, bool causal, hipStream_t stream) {
+    if (!grouped_heads_ok(B, H, Hkv, D, d_model) || !cached_shape_ok(Nq, cap, len, causal)) return hipErrorInvalidValue;
+    return fa_f16_masked_launch(w, Qf, O, B, Hkv, D, d_model, stream, Grouped(cached_geo(Nq, cap, len, causal), H / Hkv));
 }
 
 }  // namespace qmha
+

@@ -217,9 +217,12 @@ def test_production_library_has_one_kernel_per_variant_and_d(built):
     # per-block d = 32 / 64 / 128 (pipelined, and the one-tile kernel they run at N = 32) and 96 / 160 / 192 /
     # 224 / 256 (one-tile kernel), per-tensor d = 32 / 64 / 128
     assert len(dumps) == 14, dumps
-    # one twin of every shipped masked int8 instance (d = 32 / 64 / 128, both geometries), and of nothing else
-    assert sorted(masked_dumps) == sorted(k for k in per if k[0].startswith("qmha_fa_int8_masked_kernel[")), masked_dumps
+    # one twin of every shipped SquareCausal and Rect masked int8 instance (d = 32 / 64 / 128), and of nothing else:
+    # the Grouped instances have none
+    plain = ("qmha_fa_int8_masked_kernel[SquareCausal]", "qmha_fa_int8_masked_kernel[Rect]")
+    assert sorted(masked_dumps) == sorted(k for k in per if k[0] in plain), masked_dumps
     assert len(masked_dumps) == 6, masked_dumps
+    assert sorted(d for n, d in per if n == "qmha_fa_int8_masked_kernel[Grouped]") == ["128", "32", "64"], sorted(per)
     for name, d, twin in dumps:  # exactly the production schedule (same WAVES, flags, PAD) plus the stores
         if name == "qmha_fa_int8_pt_v3_kernel":  # the 8-wave production instance (the 4-wave one has no twin)
             assert twin in per[(name, d)], (name, d, twin)

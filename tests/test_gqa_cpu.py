@@ -2,8 +2,8 @@
 
 Every check of the two entry points runs before any HIP call, so each rejection is reached here with dummy pointers
 (as tests/test_rect_cpu.py and tests/test_kvcache_cpu.py do).  There is no size function of its own: the scratch and
-the cache are those of a call with h_kv heads.  The shipped library holds exactly five grouped main kernels, no dumping
-twin of them, and still ten masked ones.
+the cache are those of a call with h_kv heads.  The shipped library holds exactly five grouped main kernels (the Grouped
+instances of the masked templates), no dumping twin of them, and still ten masked ones of the other two geometries.
 """
 import ctypes
 import os
@@ -164,17 +164,20 @@ def test_equal_head_counts_are_the_multi_head_entry_points(lib):
 
 
 def test_library_has_five_grouped_kernels_and_ten_masked(lib):
+    """The grouped kernels are the Grouped instances of the masked templates: five of them, beside the ten of the
+    SquareCausal and Rect geometries."""
     path = os.path.join(ROOT, "quantizedmha_amd", "lib", "libqmha.so")
     syms = subprocess.run(["nm", path], capture_output=True, text=True, check=True).stdout
-    stubs = sorted(set(re.findall(r"__device_stub__(qmha_fa_\w+?_gqa_kernel)ILi(\d+)E(\w*)", syms)))
-    assert [(n, d) for n, d, _ in stubs] == [("qmha_fa_f16_gqa_kernel", "128"), ("qmha_fa_f16_gqa_kernel", "64"),
-                                             ("qmha_fa_int8_gqa_kernel", "128"), ("qmha_fa_int8_gqa_kernel", "32"),
-                                             ("qmha_fa_int8_gqa_kernel", "64")], stubs
-    # one template argument (D): no dumping twin, no second geometry
-    assert all(rest.startswith("EEv") and "Dumping" not in rest for _, _, rest in stubs), stubs
-    assert not re.search(r"gqa\w*Dumping|Dumping\w*Grouped", syms)
     masked = set(re.findall(r"__device_stub__(qmha_fa_\w+?_masked_kernel)ILi(\d+)ENS_\d+([A-Za-z]+?)E(\w*)", syms))
-    assert len(masked) == 10, sorted(masked)
+    stubs = sorted((n, d, rest) for n, d, g, rest in masked if g == "Grouped")
+    assert [(n, d) for n, d, _ in stubs] == [("qmha_fa_f16_masked_kernel", "128"), ("qmha_fa_f16_masked_kernel", "64"),
+                                             ("qmha_fa_int8_masked_kernel", "128"), ("qmha_fa_int8_masked_kernel", "32"),
+                                             ("qmha_fa_int8_masked_kernel", "64")], stubs
+    # no template argument beyond (D, geometry): no dumping twin, no second instance
+    assert all(rest.startswith("EEv") and "Dumping" not in rest for _, _, rest in stubs), stubs
+    assert "_gqa_kernel" not in syms
+    assert not re.search(r"Dumping\w*Grouped", syms)
+    assert len(masked) == 15, sorted(masked)
 
 
 def test_python_binding_accepts_num_kv_heads():

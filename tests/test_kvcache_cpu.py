@@ -152,7 +152,10 @@ def test_library_has_five_append_kernels_and_ten_masked(lib):
                      ("qmha_kv_append_int8_kernel", "128"), ("qmha_kv_append_int8_kernel", "32"),
                      ("qmha_kv_append_int8_kernel", "64")], stubs
     masked = set(re.findall(r"__device_stub__(qmha_fa_\w+?_masked_kernel)ILi(\d+)ENS_\d+([A-Za-z]+?)E(\w*)", syms))
-    assert len(masked) == 10, sorted(masked)
+    # the cache runs the shipped Rect instances: still ten of the SquareCausal and Rect geometries, and beside them
+    # nothing but the five grouped-query ones
+    assert len([m for m in masked if m[2] in ("SquareCausal", "Rect")]) == 10, sorted(masked)
+    assert len(masked) == 15 and {m[2] for m in masked} == {"SquareCausal", "Rect", "Grouped"}, sorted(masked)
 
 
 def test_python_binding_has_kvcache():

@@ -218,15 +218,15 @@ def test_rect_caller_workspace_one_byte_short_is_invalid(built, vid):
 def test_rect_kernels_one_instance_per_head_size(built):
     """The causal switch is a runtime argument: one rectangular (Rect geometry) qmha_fa_int8_masked_kernel per d in
     {32, 64, 128} and one qmha_fa_f16_masked_kernel per d in {64, 128}; beside them exactly one square-causal
-    (SquareCausal geometry) instance per head size, ten kernels in all."""
+    (SquareCausal geometry) and one grouped-query (Grouped geometry) instance per head size, fifteen kernels in all."""
     path = os.path.join(ROOT, "quantizedmha_amd", "lib", "libqmha.so")
     syms = subprocess.run(["nm", path], capture_output=True, text=True, check=True).stdout
     stubs = sorted(re.findall(r"__device_stub__(qmha_fa_\w+?_masked_kernel)ILi(\d+)ENS_\d+([A-Za-z]+?)E(\w*)", syms))
     per_d = [("qmha_fa_f16_masked_kernel", 128), ("qmha_fa_f16_masked_kernel", 64), ("qmha_fa_int8_masked_kernel", 128),
              ("qmha_fa_int8_masked_kernel", 32), ("qmha_fa_int8_masked_kernel", 64)]
-    for geo in ("Rect", "SquareCausal"):
+    for geo in ("Rect", "SquareCausal", "Grouped"):
         assert [(n, int(d)) for n, d, g, _ in stubs if g == geo] == per_d, (geo, stubs)
-    assert len(stubs) == 10 and "_rect_kernel" not in syms and "_causal_kernel" not in syms, stubs
+    assert len(stubs) == 15 and "_rect_kernel" not in syms and "_causal_kernel" not in syms, stubs
     # the rectangular instances take no template argument beyond (D, geometry): causal or not is decided at run time
     assert all(rest.startswith("EEv") for _, _, _, rest in stubs), stubs
 

@@ -31,8 +31,8 @@ BIN = os.path.join(ROOT, "quantizedmha_amd", "bin")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-KERNEL_SOURCES = ["qmha_fa_int8.hip", "qmha_fa_f16.hip", "qmha_fa_masked.hip", "qmha_fa_gqa.hip", "qmha_prepass.hip",
-                  "qmha_fa_f32.hip", "qmha_unfused.hip", "qmha_api.cpp"]
+KERNEL_SOURCES = ["qmha_fa_int8.hip", "qmha_fa_f16.hip", "qmha_fa_masked.hip", "qmha_prepass.hip", "qmha_fa_f32.hip",
+                  "qmha_unfused.hip", "qmha_api.cpp"]
 # profiling builds (QMHA_EXTRA_FLAGS=-DQMHA_ABLATION) enable the tuning alternatives of the fp16 / fp32 / api
 # sources.  The r01-r03 int8 experiment source (ablation perturbations, ring / DMA-split / TSHADOW / ACC1
 # schedules, the per-workgroup timeline) was removed in round 5 -- it had fallen behind the production
@@ -80,7 +80,6 @@ def header_deps():
 FILE_FLAGS = {"qmha_fa_int8.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + os.environ.get("QMHA_INT8_FLAGS", "").split(),
               "qmha_fa_f16.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + os.environ.get("QMHA_F16_FLAGS", "").split(),
               "qmha_fa_masked.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + os.environ.get("QMHA_CAUSAL_FLAGS", "").split(),
-              "qmha_fa_gqa.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + os.environ.get("QMHA_CAUSAL_FLAGS", "").split(),
               "qmha_fa_f32.hip": os.environ.get("QMHA_F32_FLAGS", "").split()}
 
 

@@ -138,7 +138,7 @@ def main():
                           "gqa": [[round(x, 5) for x in r] for r in rows[1]]},
             "clock_probe": bench.clock_probe(dev),
             "isa_sha16": {"ref_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_masked_kernelILi{a.d}ENS_4RectE"),
-                          "gqa_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_gqa_kernelILi{a.d}E"),
+                          "gqa_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_masked_kernelILi{a.d}ENS_7GroupedE"),
                           "append": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_kv_append_{stem}_kernelILi{a.d}E")},
             "device": torch.cuda.get_device_properties(dev).name,
         }

@@ -190,6 +190,31 @@ int qmha_kv_cache_truncate(qmha_kv_cache_t *c, int len);
 int qmha_kv_cache_append(qmha_kv_cache_t *c, const float *K, const float *V, int n, void *stream);
 int qmha_attend_cached(qmha_kv_cache_t *c, const float *Q, float *O, int Nq, unsigned flags, void *stream);
 
+/*
+ * Per-sequence lengths, read on the device -- a batch whose sequences differ in length in one cache, and a decode step
+ * that is captured once and replayed while the lengths advance in device memory.  pos and lens are DEVICE int32[B]
+ * arrays that the kernels read when they run; the host never reads them, so nothing is baked into a capture but the
+ * two pointers.  Both calls address the rows append / attend address (they may be mixed with them on one cache) and
+ * neither reads or changes the cache's host `len`: the caller owns the lengths.  Multi-head and grouped caches alike.
+ *
+ *   append_at      K, V: [B, n, h_kv * d] as for append; n % 32 == 0, 32 <= n <= cap, checked on the host.  Sequence b's n
+ *                  rows go to cache rows [pos[b], pos[b] + n), with the bytes append writes for them at len == pos[b];
+ *                  nothing else is written.  On the device, pos[b] is valid when pos[b] >= 0, pos[b] % 32 == 0 and
+ *                  pos[b] + n <= cap; a sequence with an invalid pos[b] writes nothing at all (a slot left out of a step).
+ *   attend_varlen  Q, O: [B, Nq, d_model], Nq % 32 == 0; flags as for attend; QMHA_FLAG_CAUSAL needs Nq <= cap; checked
+ *                  on the host.  On the device, L = lens[b] is valid when L % 32 == 0, L <= cap and L >= Nq (causal) or
+ *                  L >= 32 (flags == 0).  A valid sequence computes what attend computes at len == L, bit for bit: causal,
+ *                  row r attends rows j <= r + (L - Nq); flags == 0, every row attends rows [0, L) -- also at L < cap,
+ *                  which attend cannot do.  Rows at and beyond L are never read.  An invalid sequence (L == 0: an empty
+ *                  slot) has its Nq rows of O written as zeros and none of its K/V read.
+ *
+ * Null pos / lens: QMHA_ERR_INVALID.  Every host check runs before any HIP call; no allocation, no synchronisation;
+ * the cache's mutex is held across the enqueue; qmha_profile records are those of append / attend.
+ */
+int qmha_kv_cache_append_at(qmha_kv_cache_t *c, const float *K, const float *V, int n, const int32_t *pos, void *stream);
+int qmha_attend_cached_varlen(qmha_kv_cache_t *c, const float *Q, float *O, int Nq, const int32_t *lens, unsigned flags,
+                              void *stream);
+
 /* Blocking convenience used by the per-variant `solve` shims and the JAX raw-pointer
  * binding (extensions/jax/jax_ext.cpp:12-28): batch 1, synchronises the device stream. */
 int qmha_solve_variant(const float *Q, const float *K, const float *V, float *O, int N, int d_model, int h,

@@ -35,6 +35,9 @@ SIGNATURES = {
     "qmha_kv_cache_truncate": (_i, [_vp, _i]),
     "qmha_kv_cache_append": (_i, [_vp, _vp, _vp, _i, _vp]),
     "qmha_attend_cached": (_i, [_vp, _vp, _vp, _i, ctypes.c_uint, _vp]),
+    # per-sequence rows / lengths: device int32[B] pointers
+    "qmha_kv_cache_append_at": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "qmha_attend_cached_varlen": (_i, [_vp, _vp, _vp, _i, _vp, ctypes.c_uint, _vp]),
     "qmha_solve_ws": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "qmha_solve_variant": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     "qmha_quantize_int8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),

@@ -760,6 +760,56 @@ int qmha_attend_cached(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, uns
     return st;
 }
 
+// ---- per-sequence lengths read on the device: the host `len` is neither read nor changed ----
+int qmha_kv_cache_append_at(qmha_kv_cache_t* c, const float* K, const float* V, int n, const int32_t* pos, void* stream) {
+    if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+    if (!K || !V) return fail(QMHA_ERR_INVALID, "null tensor pointer");
+    if (!pos) return fail(QMHA_ERR_INVALID, "append_at: null pos (a device int32[B])");
+    if (n < 32 || n % 32 != 0) return fail(QMHA_ERR_INVALID, "append_at: n must be a positive multiple of 32");
+    if (n > c->cap)
+        return fail(QMHA_ERR_INVALID, "append_at: n = " + std::to_string(n) + " rows exceed cap = " + std::to_string(c->cap));
+    std::lock_guard<std::mutex> lk(c->mu);  // held across the enqueue
+    const hipStream_t s = (hipStream_t)stream;
+    const bool prof = profiling_on();
+    ProfRec rec;
+    const int st = timed(prof ? &rec.pre : nullptr, s, "kv_cache append_at launch", [&] {
+        return c->variant == QMHA_FA_TC_INT8_B
+                   ? qmha::launch_kv_place_int8(K, V, qmha::int8_carve(c->mem, c->B, c->cap, c->h_kv, c->D), c->B, n, c->cap, pos,
+                                                c->h_kv, c->D, c->h_kv * c->D, s)
+                   : qmha::launch_kv_place_f16(K, V, qmha::f16_carve(c->mem, c->B, c->cap, c->h_kv, c->D), c->B, n, c->cap, pos,
+                                               c->h_kv, c->D, c->h_kv * c->D, s);
+    });
+    if (st == QMHA_OK && prof) keep_record(std::move(rec));
+    return st;
+}
+
+int qmha_attend_cached_varlen(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, const int32_t* lens, unsigned flags,
+                              void* stream) {
+    if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+    int D = 0;
+    int st = check_shape(Q, Q, Q, O, c->B, Nq, c->d_model, c->h, c->variant, &D, "Nq");
+    if (st == QMHA_OK) st = check_flag_bits(flags);
+    if (st != QMHA_OK) return st;
+    if (!lens) return fail(QMHA_ERR_INVALID, "attend_varlen: null lens (a device int32[B])");
+    const bool causal = flags & QMHA_FLAG_CAUSAL;
+    if (causal && Nq > c->cap)
+        return fail(QMHA_ERR_INVALID, "causal attention is bottom-right aligned and needs Nq <= cap (Nq = " + std::to_string(Nq) +
+                                          ", cap = " + std::to_string(c->cap) + ")");
+    std::lock_guard<std::mutex> lk(c->mu);  // held across the enqueue
+    const hipStream_t s = (hipStream_t)stream;
+    const bool prof = profiling_on();
+    ProfRec rec;
+    st = timed(prof ? &rec.main : nullptr, s, "kv_cache attend_varlen launch", [&] {
+        return c->variant == QMHA_FA_TC_INT8_B
+                   ? qmha::launch_fa_int8_varlen(qmha::int8_carve(c->mem, c->B, c->cap, c->h_kv, c->D), Q, O, lens, c->B, Nq, c->cap,
+                                                 c->h, c->h_kv, c->D, c->d_model, causal, s)
+                   : qmha::launch_fa_f16_varlen(qmha::f16_carve(c->mem, c->B, c->cap, c->h_kv, c->D), Q, O, lens, c->B, Nq, c->cap,
+                                                c->h, c->h_kv, c->D, c->d_model, causal, s);
+    });
+    if (st == QMHA_OK && prof) keep_record(std::move(rec));
+    return st;
+}
+
 int qmha_solve_variant(const float* Q, const float* K, const float* V, float* O, int N, int d_model, int h,
                        int variant) {
     // blocking like the reference (launchers.h:64): hipStreamSynchronize.  r04 A/B: polling

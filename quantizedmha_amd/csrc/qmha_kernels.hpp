@@ -201,6 +201,22 @@ hipError_t launch_fa_int8_gqa_cached(const Int8Workspace& w, const float* Qf, fl
 hipError_t launch_fa_f16_gqa_cached(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int cap, int len, int H,
                                     int Hkv, int D, int d_model, bool causal, hipStream_t stream);
 
+// ---- per-sequence lengths read on the device (qmha_kv_cache_append_at, qmha_attend_cached_varlen) ----
+// pos, lens: DEVICE int32[B], read by the kernels; the grids follow the host arguments only.  w: the carve of Hkv heads
+// at N = cap (Hkv == H: a multi-head cache).  Place: sequence b's n rows go to rows [pos[b], pos[b] + n) of its slices,
+// byte for byte what launch_kv_append_* writes at len = pos[b]; pos[b] < 0, pos[b] % 32 != 0 or pos[b] + n > cap: that
+// sequence writes nothing.  Attend: sequence b computes what launch_fa_*_{masked,gqa}_cached computes at len = lens[b]
+// -- without the mask over rows [0, lens[b]), whatever cap is --; lens[b] % 32 != 0, > cap, < Nq (causal) or < 32 (not):
+// its O rows are zeros and none of its K/V is read.  Bad host arguments, a null pos / lens too: hipErrorInvalidValue.
+hipError_t launch_kv_place_int8(const float* K, const float* V, const Int8Workspace& w, int B, int n, int cap,
+                                const int32_t* pos, int H, int D, int d_model, hipStream_t stream);
+hipError_t launch_kv_place_f16(const float* K, const float* V, const F16Workspace& w, int B, int n, int cap,
+                               const int32_t* pos, int H, int D, int d_model, hipStream_t stream);
+hipError_t launch_fa_int8_varlen(const Int8Workspace& w, const float* Qf, float* O, const int32_t* lens, int B, int Nq, int cap,
+                                 int H, int Hkv, int D, int d_model, bool causal, hipStream_t stream);
+hipError_t launch_fa_f16_varlen(const F16Workspace& w, const float* Qf, float* O, const int32_t* lens, int B, int Nq, int cap,
+                                int H, int Hkv, int D, int d_model, bool causal, hipStream_t stream);
+
 // ---- FP32 (fa: scalar VALU kernel; fa_mfma: the same contract on v_mfma_f32_32x32x2_f32) -----
 hipError_t launch_fa_f32(const float* Q, const float* K, const float* V, float* O, int B, int N, int H, int D,
                          int d_model, bool mfma, hipStream_t stream);

@@ -7,6 +7,8 @@
 //   qmha_convert_f16_kernel fa_tc_v1a.cu:300-330: K as f16 rows, V in the f16 V^T operand order (RNE)
 //   qmha_kv_append_{int8,f16}_kernel  the same per-group work for the new rows of a persistent K/V cache
 //                           (qmha_kv_cache_append), written behind the cache's valid rows
+//   qmha_kv_place_{int8,f16}_kernel   the append kernels' body with a row per sequence, read from device memory
+//                           (qmha_kv_cache_append_at)
 #include <atomic>
 
 #include "qmha_common.hpp"
@@ -176,68 +178,52 @@ __global__ __launch_bounds__(256) void qmha_convert_f16_kernel(
 // fp16 kernel the loads, the RNE conversion and the vt_group_store of qmha_convert_f16_kernel.
 // Nothing outside groups [len / 32, (len + n) / 32) of a slice is written.
 // ---------------------------------------------------------------------------------------
+// The bodies are qmha_kv_append_{int8,f16}.inc, included inside the __global__ with `len` in scope (why a text
+// include: DESIGN.md 15.3): the append kernels' `len` is their argument, the place kernels' (qmha_kv_cache_append_at,
+// DESIGN.md 15) is their wave's place_row().
 template <int D>
 __global__ __launch_bounds__(256) void qmha_kv_append_int8_kernel(
     const float* __restrict__ K, const float* __restrict__ V, int8_t* __restrict__ Ki, _Float16* __restrict__ Vh,
     float* __restrict__ sK, float* __restrict__ sV, int n, int cap, int len, int H, int d_model, int total_groups) {
-    __shared__ __attribute__((aligned(16))) char vtr[4][D * QMHA_VT_PITCH];
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int item = blockIdx.x * 4 + wave;  // (bh, g)
-    if (item >= total_groups) return;        // wave-uniform
-    const int Gn = n / QMHA_GROUP, Gc = cap / QMHA_GROUP;
-    const int bh = item / Gn, g = item % Gn;
-    const int b = bh / H, k = bh % H;
-    // quant_row_group / quant_v_group index source and destination by ONE row count: group g of n-row arrays,
-    // element (bh n + 32 g) D of the rows, entry bh Gn + g of the scales and of the 64 D-byte V blocks.  They are
-    // called with the chunk's n, which is right for the source; every destination pointer is moved ahead by what
-    // the cache's index of the same group has more: group (bh Gc + len / 32 + g) - (bh Gn + g) = bh (Gc - Gn) +
-    // len / 32 (>= 0, wave-uniform), so the functions -- and the pre-pass kernels built from them -- stay as they are.
-    const size_t ahead = (size_t)bh * (Gc - Gn) + len / QMHA_GROUP;  // in groups
-    if (blockIdx.y == 1)
-        quant_v_group<D, 1>(V, Vh + ahead * (size_t)(32 * D), sV + ahead, vtr[wave], lane, b, k, g, bh, n, Gn, d_model);
-    else
-        quant_row_group<D>(K, Ki + ahead * (size_t)(QMHA_GROUP * D), sK + ahead, lane, b, k, g, bh, n, Gn, d_model);
+#include "qmha_kv_append_int8.inc"
 }
 
 template <int D>
 __global__ __launch_bounds__(256) void qmha_kv_append_f16_kernel(
     const float* __restrict__ K, const float* __restrict__ V, _Float16* __restrict__ Kh, _Float16* __restrict__ Vt,
     int n, int cap, int len, int H, int d_model, int total_groups) {
-    constexpr int C4 = D / 4, RPI = 64 / C4, NI = 32 / RPI;
-    __shared__ __attribute__((aligned(16))) char vtr[4][D * QMHA_VT_PITCH];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int item = blockIdx.x * 4 + wave;
-    if (item >= total_groups) return;  // wave-uniform; the LDS tile is per wave, no workgroup barrier follows
-    const int Gn = n / QMHA_GROUP, Gc = cap / QMHA_GROUP;
-    const int bh = item / Gn, g = item % Gn;
-    const int b = bh / H, k = bh % H;
-    const int gd = len / QMHA_GROUP + g;
-    v4f x[NI];
-    if (blockIdx.y == 1) {  // V^T operand order: NI consecutive rows per lane (the vt_group_store map)
-        const int rq = lane / C4, c4 = lane % C4;
-        const float* base = V + ((size_t)b * n + (size_t)g * QMHA_GROUP) * d_model + (size_t)k * D + 4 * c4;
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-            x[i] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(base + (size_t)(NI * rq + i) * d_model));
-        vt_group_store<D, false>(vtr[wave], x, 1.0f, lane, reinterpret_cast<char*>(Vt + ((size_t)bh * Gc + gd) * (size_t)(32 * D)));
-        return;
-    }
-    const int ri = lane / C4, ci = lane % C4;  // K: f16 rows
-    const float* base = K + ((size_t)b * n + (size_t)g * QMHA_GROUP) * d_model + (size_t)k * D + 4 * ci;
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-        x[i] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(base + (size_t)(i * RPI + ri) * d_model));
-    _Float16* dst = Kh + ((size_t)bh * cap + (size_t)gd * QMHA_GROUP) * D + 4 * ci;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        v4h hv;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) hv[c] = (_Float16)x[i][c];  // RNE (= __float2half)
-        *reinterpret_cast<v4h*>(dst + (size_t)(i * RPI + ri) * D) = hv;
-    }
+#include "qmha_kv_append_f16.inc"
 }
 
+// The row of its sequence's slices at which a wave of a place kernel writes: pos[b] of the sequence b its item (the
+// bodies' (bh, g)) belongs to, or -1 -- the wave returns, having written nothing; b is per wave and no workgroup
+// barrier follows -- for an item past the grid's and for an invalid pos[b]: pos[b] < 0, pos[b] % 32 != 0 (two's
+// complement: of a negative value too) or pos[b] + n > cap (n <= cap, checked by the launchers).
+__device__ __forceinline__ int place_row(const int32_t* __restrict__ pos, int n, int cap, int H, int total_groups) {
+    const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= total_groups) return -1;
+    const int p = pos[item / (n / QMHA_GROUP) / H];
+    return p >= 0 && (p & (QMHA_GROUP - 1)) == 0 && p <= cap - n ? p : -1;
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void qmha_kv_place_int8_kernel(
+    const float* __restrict__ K, const float* __restrict__ V, int8_t* __restrict__ Ki, _Float16* __restrict__ Vh,
+    float* __restrict__ sK, float* __restrict__ sV, int n, int cap, const int32_t* __restrict__ pos, int H, int d_model,
+    int total_groups) {
+    const int len = place_row(pos, n, cap, H, total_groups);
+    if (len < 0) return;
+#include "qmha_kv_append_int8.inc"
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void qmha_kv_place_f16_kernel(
+    const float* __restrict__ K, const float* __restrict__ V, _Float16* __restrict__ Kh, _Float16* __restrict__ Vt,
+    int n, int cap, const int32_t* __restrict__ pos, int H, int d_model, int total_groups) {
+    const int len = place_row(pos, n, cap, H, total_groups);
+    if (len < 0) return;
+#include "qmha_kv_append_f16.inc"
+}
 
 // ---------------------------------------------------------------------------------------
 // Every other head size the reference accepts (d % 32 == 0, include/config.h:32; d = 96, 160, 192,
@@ -721,6 +707,45 @@ hipError_t launch_kv_append_f16(const float* K, const float* V, const F16Workspa
     case d:                                                                                                         \
         hipLaunchKernelGGL((qmha_kv_append_f16_kernel<d>), grid, dim3(256), 0, stream, K, V, w.Kh, w.Vt, n, cap, len, \
                            H, d_model, total);                                                                      \
+        return hipGetLastError();
+        QMHA_CASE(64) QMHA_CASE(128)
+#undef QMHA_CASE
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// ---- K/V cache placement: as the appends, rows [pos[b], pos[b] + n) of sequence b's slices; pos is read on the device ----
+static bool kv_place_shape_ok(int B, int n, int cap, const int32_t* pos, int H) {
+    return pos && kv_append_shape_ok(B, n, cap, 0, H);
+}
+
+hipError_t launch_kv_place_int8(const float* K, const float* V, const Int8Workspace& w, int B, int n, int cap,
+                                const int32_t* pos, int H, int D, int d_model, hipStream_t stream) {
+    if (!kv_place_shape_ok(B, n, cap, pos, H)) return hipErrorInvalidValue;
+    const int total = B * H * (n / QMHA_GROUP);
+    const dim3 grid((total + 3) / 4, 2);
+    switch (D) {
+#define QMHA_CASE(d)                                                                                                   \
+    case d:                                                                                                            \
+        hipLaunchKernelGGL((qmha_kv_place_int8_kernel<d>), grid, dim3(256), 0, stream, K, V, w.Ki, w.Vh, w.sK, w.sV, n, \
+                           cap, pos, H, d_model, total);                                                               \
+        return hipGetLastError();
+        QMHA_CASE(32) QMHA_CASE(64) QMHA_CASE(128)
+#undef QMHA_CASE
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_kv_place_f16(const float* K, const float* V, const F16Workspace& w, int B, int n, int cap,
+                               const int32_t* pos, int H, int D, int d_model, hipStream_t stream) {
+    if (!kv_place_shape_ok(B, n, cap, pos, H)) return hipErrorInvalidValue;
+    const int total = B * H * (n / QMHA_GROUP);
+    const dim3 grid((total + 3) / 4, 2);
+    switch (D) {
+#define QMHA_CASE(d)                                                                                               \
+    case d:                                                                                                        \
+        hipLaunchKernelGGL((qmha_kv_place_f16_kernel<d>), grid, dim3(256), 0, stream, K, V, w.Kh, w.Vt, n, cap, pos, \
+                           H, d_model, total);                                                                     \
         return hipGetLastError();
         QMHA_CASE(64) QMHA_CASE(128)
 #undef QMHA_CASE

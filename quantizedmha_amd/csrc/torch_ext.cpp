@@ -16,6 +16,8 @@
 //   * `KVCache` (a class): a persistent quantised K/V cache through qmha_kv_cache_* / qmha_attend_cached;
 //   * `flash_solve_gqa` and `GroupedKVCache`: the two above with `num_kv_heads` K/V heads shared by the query heads
 //     (grouped-query attention, qmha_solve_gqa / qmha_kv_cache_create_gqa); None is the multi-head form;
+//   * both caches' `append_at` / `attend_varlen`: a row / a length per sequence in int32 [B] device tensors that the
+//     kernels read (qmha_kv_cache_append_at / qmha_attend_cached_varlen);
 //   * a rejected shape raises (TORCH_CHECK on the C-ABI status) instead of a device assert.
 #include <torch/extension.h>
 // ROCm PyTorch reports HIP devices as device type "cuda": the guard / current-stream
@@ -191,7 +193,48 @@ public:
         TORCH_CHECK(st == QMHA_OK, "KVCache.truncate: ", qmha_status_string(st), ": ", qmha_last_error());
     }
 
+    // append with a row per sequence (qmha_kv_cache_append_at): pos is int32 [B] on the device, read by the kernel
+    void append_at(const Tensor& K, const Tensor& V, const Tensor& pos) {
+        auto Kc = rows(K, "K", kv_model_), Vc = rows(V, "V", kv_model_);
+        TORCH_CHECK(Kc.sizes() == Vc.sizes(), "K and V must have the same shape");
+        per_seq(pos, "pos");
+        const c10::hip::HIPGuardMasqueradingAsCUDA guard(mem_.device());
+        const hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(mem_.device().index()).stream();
+        const int st = qmha_kv_cache_append_at(handle_, Kc.data_ptr<float>(), Vc.data_ptr<float>(), static_cast<int>(Kc.size(1)),
+                                               pos.data_ptr<int32_t>(), stream);
+        TORCH_CHECK(st == QMHA_OK, "KVCache.append_at(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+    }
+
+    // attend with a length per sequence (qmha_attend_cached_varlen): lens is int32 [B] on the device, read by the kernel
+    Tensor attend_varlen(const Tensor& Q, const Tensor& lens, bool causal, std::optional<Tensor> out_opt) {
+        auto Qc = rows(Q, "Q", d_model_);
+        per_seq(lens, "lens");
+        Tensor out;
+        if (out_opt) {
+            out = *out_opt;
+            TORCH_CHECK(out.numel() == Qc.numel() && out.dtype() == torch::kFloat32 && out.device() == Qc.device() &&
+                            out.is_contiguous(),
+                        "out must be a contiguous float32 tensor of Q's size on Q's device");
+        } else {
+            out = torch::empty_like(Qc);
+        }
+        const c10::hip::HIPGuardMasqueradingAsCUDA guard(mem_.device());
+        const hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(mem_.device().index()).stream();
+        const int st = qmha_attend_cached_varlen(handle_, Qc.data_ptr<float>(), out.data_ptr<float>(), static_cast<int>(Qc.size(1)),
+                                                 lens.data_ptr<int32_t>(), causal ? QMHA_FLAG_CAUSAL : 0u, stream);
+        TORCH_CHECK(st == QMHA_OK, "KVCache.attend_varlen(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+        return out_opt ? out : out.view(Q.sizes());
+    }
+
 private:
+    // a per-sequence int32 [B] tensor on the cache's device, contiguous: the kernel reads it, the host does not
+    void per_seq(const Tensor& t, const char* name) const {
+        TORCH_CHECK(t.is_cuda(), name, " must be a CUDA tensor");
+        TORCH_CHECK(t.dtype() == torch::kInt32, name, " must be int32");
+        TORCH_CHECK(t.device() == mem_.device(), name, " must be on the cache's device");
+        TORCH_CHECK(t.dim() == 1 && t.size(0) == B_ && t.is_contiguous(), name, " must be a contiguous tensor of shape [B = ", B_,
+                    "]");
+    }
     // [B, n, d_model] fp32 on the cache's device, contiguous; [n, d_model] for B = 1
     Tensor rows(const Tensor& X, const char* name, int64_t width) const {
         TORCH_CHECK(X.is_cuda(), "Inputs must be CUDA tensors");
@@ -227,6 +270,13 @@ PYBIND11_MODULE(torch_ext, m) {
         .def("append", &KVCache::append, pybind11::arg("K"), pybind11::arg("V"))
         .def("attend", &KVCache::attend, pybind11::arg("Q"), pybind11::arg("causal") = true)
         .def("truncate", &KVCache::truncate, pybind11::arg("n"))
+        .def("append_at", &KVCache::append_at, pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("pos"),
+             "append with a row per sequence: sequence b's rows go to cache rows [pos[b], pos[b] + n); pos: int32 [B] on the\n"
+             "device, read by the kernel; an invalid pos[b] writes nothing for that sequence.")
+        .def("attend_varlen", &KVCache::attend_varlen, pybind11::arg("Q"), pybind11::arg("lens"), pybind11::arg("causal") = true,
+             pybind11::arg("out") = pybind11::none(),
+             "attend with a length per sequence: sequence b attends its first lens[b] cache rows; lens: int32 [B] on the\n"
+             "device, read by the kernel; an invalid lens[b] gives zeros for that sequence.")
         .def_property_readonly("len", &KVCache::len)
         .def_property_readonly("cap", &KVCache::cap)
         .def_property_readonly("mem", &KVCache::mem);

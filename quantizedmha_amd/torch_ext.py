@@ -160,7 +160,10 @@ class KVCache:
     current stream; the caller keeps the operations on one cache ordered (one stream, or its own events).
     attend(Q, causal=False) needs a full cache (len == cap): every row attends all cap rows.  truncate(n) drops rows
     from the end (n % 32 == 0, n <= len); nothing is enqueued.  GroupedKVCache (below) is the same cache over fewer
-    K/V heads than query heads."""
+    K/V heads than query heads.
+    append_at(K, V, pos) / attend_varlen(Q, lens) take a row / a length per sequence from int32 [B] tensors on the
+    device, read by the kernels when they run: sequences of different lengths in one cache, and a step that is captured
+    once and replayed while the caller advances pos / lens in device memory.  They leave `len` alone."""
 
     def __init__(self, B: int, cap: int, d_model: int, num_heads: int, kernel: str = _lib.DEFAULT_KERNEL, device="cuda"):
         self._setup(B, cap, d_model, num_heads, None, kernel, device)
@@ -246,6 +249,53 @@ class KVCache:
 
     def truncate(self, n: int) -> None:
         _lib.check(_lib.load().qmha_kv_cache_truncate(self._handle, int(n)), "KVCache.truncate")
+
+    def _per_seq(self, t: torch.Tensor, name: str) -> torch.Tensor:
+        """A per-sequence int32 [B] tensor on the cache's device, read by the kernel when it runs (not by the host)."""
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{name} must be a CUDA tensor")
+        if t.dtype != torch.int32:
+            raise RuntimeError(f"{name} must be int32")
+        if t.device != self.device:
+            raise RuntimeError(f"{name} must be on the cache's device {self.device}")
+        if t.dim() != 1 or t.shape[0] != self.B or not t.is_contiguous():
+            raise RuntimeError(f"{name} must be a contiguous tensor of shape [B = {self.B}]")
+        return t
+
+    def append_at(self, K: torch.Tensor, V: torch.Tensor, pos: torch.Tensor) -> None:
+        """append with a row per sequence (qmha_kv_cache_append_at): sequence b's n rows go to cache rows
+        [pos[b], pos[b] + n).  pos: int32 [B] on the device, read by the kernel -- the tensor itself, not a copy, so a
+        captured call follows later changes of it.  A sequence whose pos[b] is negative, no multiple of 32 or beyond
+        cap - n writes nothing.  `len` is neither read nor changed."""
+        Kc, Vc = self._rows(K, "K", self.kv_model), self._rows(V, "V", self.kv_model)
+        if Kc.shape != Vc.shape:
+            raise RuntimeError("K and V must have the same shape")
+        pos = self._per_seq(pos, "pos")
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            st = _lib.load().qmha_kv_cache_append_at(self._handle, Kc.data_ptr(), Vc.data_ptr(), Kc.shape[1], pos.data_ptr(),
+                                                     stream)
+        _lib.check(st, f"KVCache.append_at({self.kernel})")
+
+    def attend_varlen(self, Q: torch.Tensor, lens: torch.Tensor, causal: bool = True,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """attend with a length per sequence (qmha_attend_cached_varlen): sequence b attends its first lens[b] cache
+        rows -- causal: row r attends rows j <= r + (lens[b] - Nq); causal=False: every row attends rows [0, lens[b]),
+        whatever cap is.  lens: int32 [B] on the device, read by the kernel (the tensor itself, as append_at's pos).  A
+        sequence whose lens[b] is no multiple of 32, above cap, or below Nq (causal) / 32 (not) gets zeros."""
+        Qc = self._rows(Q, "Q")
+        lens = self._per_seq(lens, "lens")
+        if out is None:
+            out = torch.empty_like(Qc)
+        elif (out.numel() != Qc.numel() or out.dtype != torch.float32 or out.device != Qc.device
+              or not out.is_contiguous()):
+            raise RuntimeError("out must be a contiguous float32 tensor of Q's size on Q's device")
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            st = _lib.load().qmha_attend_cached_varlen(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[1],
+                                                       lens.data_ptr(), _lib.QMHA_FLAG_CAUSAL if causal else 0, stream)
+        _lib.check(st, f"KVCache.attend_varlen({self.kernel})")
+        return out.view(Q.shape) if out.numel() == Q.numel() and out.dim() != Q.dim() else out
 
 
 class GroupedKVCache(KVCache):

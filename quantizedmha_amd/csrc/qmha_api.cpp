@@ -50,17 +50,19 @@ struct VariantRow {
     int id;
     const char* name;
     size_t (*ws_bytes)(int B, int N, int H, int D);  // nullptr: no scratch
-    unsigned plain, causal;                          // built head sizes without / with QMHA_FLAG_CAUSAL
-    unsigned rect;                                   // built head sizes of qmha_solve_rect with Nq != Nk
+    unsigned plain;                                  // built head sizes of a square call without flags
+    // built head sizes of the masked templates (qmha_fa_masked.hip): causal, rectangular and grouped-query calls and
+    // the K/V cache are all instances of them and so are built together
+    unsigned masked;
 };
 constexpr VariantRow kVariants[] = {
-    {QMHA_FA, "fa", nullptr, kEveryD, 0, 0},
-    {QMHA_FA_TC_V1A, "fa_tc_v1a", qmha::f16_workspace_bytes, kEveryD, d_mask(64, 128), d_mask(64, 128)},
+    {QMHA_FA, "fa", nullptr, kEveryD, 0},
+    {QMHA_FA_TC_V1A, "fa_tc_v1a", qmha::f16_workspace_bytes, kEveryD, d_mask(64, 128)},
     {QMHA_FA_TC_INT8_B, "fa_tc_int8_b", [](int B, int N, int H, int D) { return qmha::int8_workspace_bytes(B, N, H, D); },
-     kEveryD, kTunedD, kTunedD},
-    {QMHA_UNFUSED, "unfused", qmha::unfused_workspace_bytes, kEveryD, 0, 0},
-    {QMHA_FA_MFMA, "fa_mfma", nullptr, kEveryD, 0, 0},
-    {QMHA_FA_TC_INT8_PT, "fa_tc_int8_pt", qmha::int8_pt_workspace_bytes, kTunedD, 0, 0},  // no reference counterpart
+     kEveryD, kTunedD},
+    {QMHA_UNFUSED, "unfused", qmha::unfused_workspace_bytes, kEveryD, 0},
+    {QMHA_FA_MFMA, "fa_mfma", nullptr, kEveryD, 0},
+    {QMHA_FA_TC_INT8_PT, "fa_tc_int8_pt", qmha::int8_pt_workspace_bytes, kTunedD, 0},  // no reference counterpart
 };
 
 const VariantRow* find_variant(int id) {
@@ -106,22 +108,60 @@ int check_shape(const void* Q, const void* K, const void* V, const void* O, int 
     return QMHA_OK;
 }
 
-// qmha_solve_opts' flags, checked before any launch: unknown bits are invalid; QMHA_FLAG_CAUSAL is built
-// for the variants and head sizes of the table's `causal` column
+// the flags of qmha_solve_opts and every later entry point: unknown bits are invalid
 int check_flag_bits(unsigned flags) {
     const unsigned unknown = flags & ~(unsigned)QMHA_FLAG_CAUSAL;
     return unknown ? fail(QMHA_ERR_INVALID, "unknown flag bits " + std::to_string(unknown)) : QMHA_OK;
 }
-int check_flags(int variant, int D, unsigned flags) {
-    if (int st = check_flag_bits(flags)) return st;
-    if ((flags & QMHA_FLAG_CAUSAL) && !built(find_variant(variant)->causal, D)) {
-        std::string have;
-        for (const VariantRow& r : kVariants)
-            if (r.causal) have += (have.empty() ? "" : "; ") + std::string(r.name) + ": d = " + d_list(r.causal);
-        return fail(QMHA_ERR_NOSYS, std::string("causal attention is not built for variant ") + qmha_variant_name(variant) +
-                                        " at d = " + std::to_string(D) + " (" + have + ")");
-    }
+
+// "<feature> is not built for variant X at d = D (<who has it>)" unless the table's `masked` column has D
+int not_built(const char* feature, int variant, int D) {
+    if (built(find_variant(variant)->masked, D)) return QMHA_OK;
+    std::string have;
+    for (const VariantRow& r : kVariants)
+        if (r.masked) have += (have.empty() ? "" : "; ") + std::string(r.name) + ": d = " + d_list(r.masked);
+    return fail(QMHA_ERR_NOSYS, std::string(feature) + " is not built for variant " + qmha_variant_name(variant) + " at d = " +
+                                    std::to_string(D) + " (" + have + ")");
+}
+constexpr const char* kGroupedFeature = "grouped-query attention (h_kv < h)";
+
+// 1 <= h_kv <= h, h % h_kv == 0 (h >= 1 was checked)
+int check_kv_heads(int h, int h_kv) {
+    if (h_kv < 1 || h_kv > h || h % h_kv != 0)
+        return fail(QMHA_ERR_INVALID, "h_kv must divide h and lie in 1..h (h = " + std::to_string(h) + ", h_kv = " +
+                                          std::to_string(h_kv) + ")");
     return QMHA_OK;
+}
+
+// One call of any solve entry point.  Q and O are [B, Nq, d_model], K and V [B, Nk, h_kv * d]; the entry points
+// without an Nk or an h_kv fill in Nq and h (`square`: their one row count is called N in the messages).
+struct Call {
+    const float *Q, *K, *V;
+    float* O;
+    int B, Nq, Nk, d_model, h, h_kv, variant;
+    unsigned flags;
+    bool square;
+    bool caller_owned;  // scratch is the caller's ws_bytes at ws (the slot is leased all the same), else the slot's own
+    void* ws;
+    size_t ws_bytes;
+};
+
+// Every check of a call but its workspace's size, run once and before any HIP call.  The order decides which
+// error a call that is wrong in several ways reports (tests/test_hostpath_cpu.py).
+int check_call(const Call& c, int* D) {
+    int st = check_shape(c.Q, c.K, c.V, c.O, c.B, c.Nq, c.d_model, c.h, c.variant, D, c.square ? "N" : "Nq");
+    if (st == QMHA_OK) st = check_shape(c.Q, c.K, c.V, c.O, c.B, c.Nk, c.d_model, c.h, c.variant, D, c.square ? "N" : "Nk");
+    if (st == QMHA_OK) st = check_kv_heads(c.h, c.h_kv);
+    if (st == QMHA_OK) st = check_flag_bits(c.flags);
+    if (st != QMHA_OK) return st;
+    const bool causal = c.flags & QMHA_FLAG_CAUSAL;
+    if (causal && c.Nq > c.Nk)
+        return fail(QMHA_ERR_INVALID, "causal attention is bottom-right aligned and needs Nk >= Nq (Nq = " +
+                                          std::to_string(c.Nq) + ", Nk = " + std::to_string(c.Nk) + ")");
+    // the kind of call names the feature; all three are the masked templates
+    if (c.h_kv < c.h) return not_built(kGroupedFeature, c.variant, *D);
+    if (c.Nq != c.Nk) return not_built("rectangular attention (Nq != Nk)", c.variant, *D);
+    return causal ? not_built("causal attention", c.variant, *D) : QMHA_OK;
 }
 
 // ---- profiling --------------------------------------------------------------------------
@@ -135,6 +175,15 @@ std::mutex g_prof_mu;
 bool g_prof_on = false;
 std::vector<ProfRec> g_prof_recs;
 std::vector<hipEvent_t> g_event_pool;
+
+bool profiling_on() {
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    return g_prof_on;
+}
+void keep_record(ProfRec&& rec) {
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    g_prof_recs.push_back(std::move(rec));
+}
 
 hipEvent_t take_event() {
     if (!g_event_pool.empty()) {
@@ -353,24 +402,20 @@ qmha::F16Workspace f16_slice(qmha::F16Workspace w, size_t b0, int N, int H, int 
 
 // Enqueue one checked call on `stream`; `ws` holds workspace_bytes(...) bytes and `slot` is leased by the caller.
 // Q and O have Nq rows, K and V have N; the pre-passes and the workspaces see K and V only, so they follow N.
-// Nq != N (qmha_solve_rect, checked against the table's `rect` column: int8 / fp16 only) takes the rectangular
-// main kernels; Nq == N enqueues the square paths.
-// K and V have h_kv heads: [B, N, h_kv * D].  h_kv == h is every call but qmha_solve_gqa's; h_kv < h (checked
-// against the `rect` column too) runs the pre-pass with h_kv heads and takes the grouped main kernels
-// (qmha_fa_masked.hip's Grouped instances) for every Nq and N.
-int run(const float* Q, const float* K, const float* V, float* O, int B, int Nq, int N, int d_model, int h, int h_kv,
-        int variant, unsigned flags, void* ws, WsSlot& slot, hipStream_t stream) {
+// A causal, rectangular (Nq != N) or grouped (h_kv < h: the pre-pass runs with h_kv heads) call -- check_call passed:
+// int8 / fp16 at a head size of the `masked` column -- takes the masked main kernels (qmha::launch_fa_masked); a
+// plain square call keeps the non-causal ones.
+int run(const Call& call, void* ws, WsSlot& slot, hipStream_t stream) {
+    const float *Q = call.Q, *K = call.K, *V = call.V;
+    float* O = call.O;
+    const int B = call.B, Nq = call.Nq, N = call.Nk, d_model = call.d_model, h = call.h, h_kv = call.h_kv, variant = call.variant;
     const int D = d_model / h;
-    const bool causal = flags & QMHA_FLAG_CAUSAL;  // check_flags passed: int8 / fp16 at a built head size
-    const bool rect = Nq != N;
-    const bool masked = causal || rect;  // qmha_fa_masked.hip; plain square calls keep the non-causal main kernels
-    const bool gqa = h_kv < h;
+    const bool causal = call.flags & QMHA_FLAG_CAUSAL;
+    const bool rect = Nq != N, gqa = h_kv < h;
+    const bool masked = causal || rect || gqa;
     const int kv_model = h_kv * D;  // row width of K and V
-    bool prof;
-    {
-        std::lock_guard<std::mutex> lk(g_prof_mu);
-        prof = g_prof_on;
-    }
+    const auto masked_call = [&](int nb) { return qmha::MaskedCall{nb, Nq, N, h, h_kv, D, d_model, causal, -1, nullptr}; };
+    const bool prof = profiling_on();
     ProfRec rec;
     Marks *pre_m = prof ? &rec.pre : nullptr, *main_m = prof ? &rec.main : nullptr;
     const size_t slab = (size_t)N * kv_model, qslab = (size_t)Nq * d_model;  // floats per sequence: K and V, Q and O
@@ -390,8 +435,7 @@ int run(const float* Q, const float* K, const float* V, float* O, int B, int Nq,
                     const qmha::Int8Workspace w = int8_slice(w8, c.b0, N, h_kv, D);
                     const float* q = Q + c.b0 * qslab;
                     float* o = O + c.b0 * qslab;
-                    if (gqa) return qmha::launch_fa_int8_gqa_main(w, q, o, c.nb, Nq, N, h, h_kv, D, d_model, causal, stream);
-                    return masked ? qmha::launch_fa_int8_masked_main(w, q, o, c.nb, Nq, N, h, D, d_model, causal, stream)
+                    return masked ? qmha::launch_fa_masked(w, q, o, masked_call(c.nb), stream)
                                   : qmha::launch_fa_int8_main(w, q, o, c.nb, N, h, D, d_model, stream);
                 });
             break;
@@ -409,8 +453,7 @@ int run(const float* Q, const float* K, const float* V, float* O, int B, int Nq,
                     const qmha::F16Workspace w = f16_slice(w16, c.b0, N, h_kv, D);
                     const float* q = Q + c.b0 * qslab;
                     float* o = O + c.b0 * qslab;
-                    if (gqa) return qmha::launch_fa_f16_gqa_main(w, q, o, c.nb, Nq, N, h, h_kv, D, d_model, causal, stream);
-                    return masked ? qmha::launch_fa_f16_masked_main(w, q, o, c.nb, Nq, N, h, D, d_model, causal, stream)
+                    return masked ? qmha::launch_fa_masked(w, q, o, masked_call(c.nb), stream)
                                   : qmha::launch_fa_f16_main(w, q, o, c.nb, N, h, D, d_model, stream);
                 });
             break;
@@ -437,109 +480,24 @@ int run(const float* Q, const float* K, const float* V, float* O, int B, int Nq,
             break;
         default: return fail(QMHA_ERR_INVALID, "unknown variant");
     }
-    if (st != QMHA_OK) return st;
-    if (prof) {
-        std::lock_guard<std::mutex> lk(g_prof_mu);
-        g_prof_recs.push_back(std::move(rec));
-    }
-    return QMHA_OK;
+    if (st == QMHA_OK && prof) keep_record(std::move(rec));
+    return st;
 }
 
-// The one solve path behind qmha_solve_ex / _ws / _opts: checks (before any HIP call), the slot's lease held
-// until the last kernel is enqueued, run().  caller_owned: scratch is the caller's `caller_bytes` at caller_ws,
-// else the slot's own.  A caller workspace leases the slot all the same (need == 0): the overlap side
-// stream lives there.
-int solve_on(const float* Q, const float* K, const float* V, float* O, int B, int N, int d_model, int h, int variant,
-             unsigned flags, bool caller_owned, void* caller_ws, size_t caller_bytes, hipStream_t stream) {
+// The one solve path behind every qmha_solve_* entry point: check_call (before any HIP call), the slot's lease held
+// until the last kernel is enqueued, run().  The scratch is that of the keys: workspace_bytes(B, Nk, h_kv, ...).  A
+// caller workspace leases the slot all the same (need == 0): the overlap side stream lives there.
+int solve_on(const Call& c, void* stream_) {
+    const hipStream_t stream = (hipStream_t)stream_;
     int D = 0;
-    int st = check_shape(Q, K, V, O, B, N, d_model, h, variant, &D);
+    int st = check_call(c, &D);
     if (st != QMHA_OK) return st;
-    st = check_flags(variant, D, flags);
-    if (st != QMHA_OK) return st;
-    const size_t need = workspace_bytes(B, N, h, D, variant);
-    if (caller_owned && caller_bytes < need) return fail(QMHA_ERR_INVALID, "workspace too small");
+    const size_t need = workspace_bytes(c.B, c.Nk, c.h_kv, D, c.variant);
+    if (c.caller_owned && c.ws_bytes < need) return fail(QMHA_ERR_INVALID, "workspace too small");
     WsLease lease;
-    st = lease_workspace(caller_owned ? 0 : need, stream, &lease);
+    st = lease_workspace(c.caller_owned ? 0 : need, stream, &lease);
     if (st != QMHA_OK) return st;
-    return run(Q, K, V, O, B, N, N, d_model, h, h, variant, flags, caller_owned ? caller_ws : lease.ptr, *lease.slot, stream);
-}
-
-// qmha_solve_rect: Q / O of Nq rows, K / V of Nk.  Every check runs before any HIP call.  Nq == Nk is solve_on
-// itself (the square paths, every variant); Nq != Nk is built for the table's `rect` column.  The scratch is
-// that of the keys: workspace_bytes(B, Nk, ...).
-int solve_rect_on(const float* Q, const float* K, const float* V, float* O, int B, int Nq, int Nk, int d_model, int h,
-                  int variant, unsigned flags, bool caller_owned, void* caller_ws, size_t caller_bytes, hipStream_t stream) {
-    int D = 0;
-    int st = check_shape(Q, K, V, O, B, Nq, d_model, h, variant, &D, "Nq");  // Q and O
-    if (st == QMHA_OK) st = check_shape(Q, K, V, O, B, Nk, d_model, h, variant, &D, "Nk");  // K and V
-    if (st == QMHA_OK) st = check_flag_bits(flags);
-    if (st != QMHA_OK) return st;
-    if ((flags & QMHA_FLAG_CAUSAL) && Nq > Nk)
-        return fail(QMHA_ERR_INVALID, "causal attention is bottom-right aligned and needs Nk >= Nq (Nq = " + std::to_string(Nq) +
-                                          ", Nk = " + std::to_string(Nk) + ")");
-    if (Nq == Nk)
-        return solve_on(Q, K, V, O, B, Nk, d_model, h, variant, flags, caller_owned, caller_ws, caller_bytes, stream);
-    if (!built(find_variant(variant)->rect, D)) {
-        std::string have;
-        for (const VariantRow& r : kVariants)
-            if (r.rect) have += (have.empty() ? "" : "; ") + std::string(r.name) + ": d = " + d_list(r.rect);
-        return fail(QMHA_ERR_NOSYS, std::string("rectangular attention (Nq != Nk) is not built for variant ") +
-                                        qmha_variant_name(variant) + " at d = " + std::to_string(D) + " (" + have + ")");
-    }
-    const size_t need = workspace_bytes(B, Nk, h, D, variant);
-    if (caller_owned && caller_bytes < need) return fail(QMHA_ERR_INVALID, "workspace too small");
-    WsLease lease;
-    st = lease_workspace(caller_owned ? 0 : need, stream, &lease);
-    if (st != QMHA_OK) return st;
-    return run(Q, K, V, O, B, Nq, Nk, d_model, h, h, variant, flags, caller_owned ? caller_ws : lease.ptr, *lease.slot, stream);
-}
-
-// 1 <= h_kv <= h, h % h_kv == 0 (h >= 1 was checked)
-int check_kv_heads(int h, int h_kv) {
-    if (h_kv < 1 || h_kv > h || h % h_kv != 0)
-        return fail(QMHA_ERR_INVALID, "h_kv must divide h and lie in 1..h (h = " + std::to_string(h) + ", h_kv = " +
-                                          std::to_string(h_kv) + ")");
-    return QMHA_OK;
-}
-
-// "grouped-query attention (h_kv < h) is not built for variant X at d = D (...)": the table's `rect` column, whose
-// kernels' grouped siblings it runs
-int check_gqa_built(int variant, int D) {
-    if (built(find_variant(variant)->rect, D)) return QMHA_OK;
-    std::string have;
-    for (const VariantRow& r : kVariants)
-        if (r.rect) have += (have.empty() ? "" : "; ") + std::string(r.name) + ": d = " + d_list(r.rect);
-    return fail(QMHA_ERR_NOSYS, std::string("grouped-query attention (h_kv < h) is not built for variant ") +
-                                    qmha_variant_name(variant) + " at d = " + std::to_string(D) + " (" + have + ")");
-}
-
-// qmha_solve_gqa: qmha_solve_rect with K and V of h_kv heads.  Every check runs before any HIP call.  h_kv == h is
-// solve_rect_on itself; h_kv < h is built for the table's `rect` column and takes the grouped kernels for every
-// Nq and Nk.  The scratch is that of the keys with h_kv heads: workspace_bytes(B, Nk, h_kv, D, variant).
-int solve_gqa_on(const float* Q, const float* K, const float* V, float* O, int B, int Nq, int Nk, int d_model, int h,
-                 int h_kv, int variant, unsigned flags, bool caller_owned, void* caller_ws, size_t caller_bytes,
-                 hipStream_t stream) {
-    int D = 0;
-    int st = check_shape(Q, K, V, O, B, Nq, d_model, h, variant, &D, "Nq");  // Q and O
-    if (st == QMHA_OK) st = check_shape(Q, K, V, O, B, Nk, d_model, h, variant, &D, "Nk");  // K and V (no wider than Q's rows)
-    if (st == QMHA_OK) st = check_kv_heads(h, h_kv);
-    if (st != QMHA_OK) return st;
-    if (h_kv == h)
-        return solve_rect_on(Q, K, V, O, B, Nq, Nk, d_model, h, variant, flags, caller_owned, caller_ws, caller_bytes, stream);
-    st = check_flag_bits(flags);
-    if (st != QMHA_OK) return st;
-    if ((flags & QMHA_FLAG_CAUSAL) && Nq > Nk)
-        return fail(QMHA_ERR_INVALID, "causal attention is bottom-right aligned and needs Nk >= Nq (Nq = " + std::to_string(Nq) +
-                                          ", Nk = " + std::to_string(Nk) + ")");
-    st = check_gqa_built(variant, D);
-    if (st != QMHA_OK) return st;
-    const size_t need = workspace_bytes(B, Nk, h_kv, D, variant);
-    if (caller_owned && caller_bytes < need) return fail(QMHA_ERR_INVALID, "workspace too small");
-    WsLease lease;
-    st = lease_workspace(caller_owned ? 0 : need, stream, &lease);
-    if (st != QMHA_OK) return st;
-    return run(Q, K, V, O, B, Nq, Nk, d_model, h, h_kv, variant, flags, caller_owned ? caller_ws : lease.ptr, *lease.slot,
-               stream);
+    return run(c, c.caller_owned ? c.ws : lease.ptr, *lease.slot, stream);
 }
 
 // The debug hooks' skeleton: `need` bytes of the null stream's slot, body(ws) enqueues the pre-pass and the
@@ -556,25 +514,6 @@ int debug_run(size_t need, Body&& body) {
     return QMHA_OK;
 }
 
-// "persistent K/V cache is not built for variant X at d = D (...)": the table's `rect` column, whose kernels it runs
-int check_cache_built(int variant, int D) {
-    if (built(find_variant(variant)->rect, D)) return QMHA_OK;
-    std::string have;
-    for (const VariantRow& r : kVariants)
-        if (r.rect) have += (have.empty() ? "" : "; ") + std::string(r.name) + ": d = " + d_list(r.rect);
-    return fail(QMHA_ERR_NOSYS, std::string("the persistent K/V cache is not built for variant ") + qmha_variant_name(variant) +
-                                    " at d = " + std::to_string(D) + " (" + have + ")");
-}
-
-bool profiling_on() {
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    return g_prof_on;
-}
-void keep_record(ProfRec&& rec) {
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    g_prof_recs.push_back(std::move(rec));
-}
-
 }  // namespace
 
 // ---- persistent K/V cache ---------------------------------------------------------
@@ -588,6 +527,34 @@ struct qmha_kv_cache {
     int h_kv;  // K/V heads: the memory is the variant's carve at H = h_kv (== h unless created by _create_gqa)
     int len;   // valid rows of every head slice
 };
+
+namespace {
+
+// f(the cache's memory as its variant's workspace); the one place that knows the precision of a cache
+template <class F>
+hipError_t with_carve(const qmha_kv_cache& c, F&& f) {
+    return c.variant == QMHA_FA_TC_INT8_B ? f(qmha::int8_carve(c.mem, c.B, c.cap, c.h_kv, c.D))
+                                          : f(qmha::f16_carve(c.mem, c.B, c.cap, c.h_kv, c.D));
+}
+
+// One operation on a cache, after the checks that need no lock: `mu` held across check(len) -- the checks against the
+// valid rows -- and the enqueue of launch(workspace, len) on `stream`, timed on the record's `marks` list when profiling
+template <class Check, class Launch>
+int cache_enqueue(qmha_kv_cache* c, Marks ProfRec::*marks, void* stream, const char* what, Check&& check, Launch&& launch) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    const int len = c->len;
+    int st = check(len);
+    if (st != QMHA_OK) return st;
+    const bool prof = profiling_on();
+    ProfRec rec;
+    st = timed(prof ? &(rec.*marks) : nullptr, (hipStream_t)stream, what,
+               [&] { return with_carve(*c, [&](const auto& w) { return launch(w, len); }); });
+    if (st == QMHA_OK && prof) keep_record(std::move(rec));
+    return st;
+}
+const auto kNoLenCheck = [](int) { return QMHA_OK; };
+
+}  // namespace
 
 int qmha::tune_config(const char* env_name) {
     static std::mutex mu;
@@ -613,31 +580,33 @@ extern "C" {
 int qmha_solve_ws(const float* Q, const float* K, const float* V, float* O, int B, int N, int d_model, int h,
                   int variant, void* workspace, size_t workspace_bytes_, void* stream) {
     // always the caller's scratch: a null one holds no bytes, whatever size is claimed
-    return solve_on(Q, K, V, O, B, N, d_model, h, variant, 0, true, workspace, workspace ? workspace_bytes_ : 0,
-                    (hipStream_t)stream);
+    return solve_on({Q, K, V, O, B, N, N, d_model, h, h, variant, 0, true, true, workspace, workspace ? workspace_bytes_ : 0},
+                    stream);
 }
 
 int qmha_solve_ex(const float* Q, const float* K, const float* V, float* O, int B, int N, int d_model, int h,
                   int variant, void* stream) {
-    return solve_on(Q, K, V, O, B, N, d_model, h, variant, 0, false, nullptr, 0, (hipStream_t)stream);
+    return solve_on({Q, K, V, O, B, N, N, d_model, h, h, variant, 0, true, false, nullptr, 0}, stream);
 }
 
+// _opts, _rect and _gqa: a null workspace is the library's scratch
 int qmha_solve_opts(const float* Q, const float* K, const float* V, float* O, int B, int N, int d_model, int h,
                     int variant, unsigned flags, void* workspace, size_t workspace_bytes_, void* stream) {
-    return solve_on(Q, K, V, O, B, N, d_model, h, variant, flags, workspace != nullptr, workspace, workspace_bytes_,
-                    (hipStream_t)stream);
+    return solve_on({Q, K, V, O, B, N, N, d_model, h, h, variant, flags, true, workspace != nullptr, workspace, workspace_bytes_},
+                    stream);
 }
 
 int qmha_solve_rect(const float* Q, const float* K, const float* V, float* O, int B, int Nq, int Nk, int d_model, int h,
                     int variant, unsigned flags, void* workspace, size_t workspace_bytes_, void* stream) {
-    return solve_rect_on(Q, K, V, O, B, Nq, Nk, d_model, h, variant, flags, workspace != nullptr, workspace, workspace_bytes_,
-                         (hipStream_t)stream);
+    return solve_on({Q, K, V, O, B, Nq, Nk, d_model, h, h, variant, flags, false, workspace != nullptr, workspace, workspace_bytes_},
+                    stream);
 }
 
 int qmha_solve_gqa(const float* Q, const float* K, const float* V, float* O, int B, int Nq, int Nk, int d_model, int h,
                    int h_kv, int variant, unsigned flags, void* workspace, size_t workspace_bytes_, void* stream) {
-    return solve_gqa_on(Q, K, V, O, B, Nq, Nk, d_model, h, h_kv, variant, flags, workspace != nullptr, workspace,
-                        workspace_bytes_, (hipStream_t)stream);
+    return solve_on({Q, K, V, O, B, Nq, Nk, d_model, h, h_kv, variant, flags, false, workspace != nullptr, workspace,
+                     workspace_bytes_},
+                    stream);
 }
 
 size_t qmha_workspace_size(int B, int N, int d_model, int h, int variant) {
@@ -658,7 +627,7 @@ int qmha_kv_cache_create_gqa(qmha_kv_cache_t** out, void* mem, size_t bytes, int
     int D = 0;
     int st = check_shape(mem, mem, mem, mem, B, cap, d_model, h, variant, &D, "cap");  // cap >= 32, cap % 32 == 0
     if (st == QMHA_OK) st = check_kv_heads(h, h_kv);
-    if (st == QMHA_OK) st = h_kv < h ? check_gqa_built(variant, D) : check_cache_built(variant, D);
+    if (st == QMHA_OK) st = not_built(h_kv < h ? kGroupedFeature : "the persistent K/V cache", variant, D);
     if (st != QMHA_OK) return st;
     if (reinterpret_cast<uintptr_t>(mem) % 256 != 0) return fail(QMHA_ERR_INVALID, "cache memory must be 256-byte aligned");
     const size_t need = workspace_bytes(B, cap, h_kv, D, variant);
@@ -700,28 +669,21 @@ int qmha_kv_cache_truncate(qmha_kv_cache_t* c, int len) {
 int qmha_kv_cache_append(qmha_kv_cache_t* c, const float* K, const float* V, int n, void* stream) {
     if (!c) return fail(QMHA_ERR_INVALID, "null cache");
     if (!K || !V) return fail(QMHA_ERR_INVALID, "null tensor pointer");
-    std::lock_guard<std::mutex> lk(c->mu);  // held across the enqueue
     if (n < 32 || n % 32 != 0) return fail(QMHA_ERR_INVALID, "append: n must be a positive multiple of 32");
-    if ((long long)c->len + n > c->cap)
-        return fail(QMHA_ERR_INVALID, "append: " + std::to_string(n) + " rows behind len = " + std::to_string(c->len) +
-                                          " exceed cap = " + std::to_string(c->cap));
-    const hipStream_t s = (hipStream_t)stream;
-    const bool prof = profiling_on();
-    ProfRec rec;
-    bool launched = false;
-    const int st = timed(prof ? &rec.pre : nullptr, s, "kv_cache append launch", [&] {
-        const hipError_t e =
-            c->variant == QMHA_FA_TC_INT8_B
-                ? qmha::launch_kv_append_int8(K, V, qmha::int8_carve(c->mem, c->B, c->cap, c->h_kv, c->D), c->B, n, c->cap,
-                                              c->len, c->h_kv, c->D, c->h_kv * c->D, s)
-                : qmha::launch_kv_append_f16(K, V, qmha::f16_carve(c->mem, c->B, c->cap, c->h_kv, c->D), c->B, n, c->cap,
-                                             c->len, c->h_kv, c->D, c->h_kv * c->D, s);
-        launched = e == hipSuccess;
-        return e;
-    });
-    if (launched) c->len += n;  // the rows are on their way whatever became of the closing profile event
-    if (st == QMHA_OK && prof) keep_record(std::move(rec));
-    return st;
+    return cache_enqueue(
+        c, &ProfRec::pre, stream, "kv_cache append launch",
+        [&](int len) {
+            if ((long long)len + n > c->cap)
+                return fail(QMHA_ERR_INVALID, "append: " + std::to_string(n) + " rows behind len = " + std::to_string(len) +
+                                                  " exceed cap = " + std::to_string(c->cap));
+            return (int)QMHA_OK;
+        },
+        [&](const auto& w, int len) {
+            const hipError_t e = qmha::launch_kv_append(K, V, w, c->B, n, c->cap, len, nullptr, c->h_kv, c->D, c->h_kv * c->D,
+                                                        (hipStream_t)stream);
+            if (e == hipSuccess) c->len = len + n;  // the rows are on their way whatever becomes of the closing profile event
+            return e;
+        });
 }
 
 int qmha_attend_cached(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, unsigned flags, void* stream) {
@@ -731,33 +693,22 @@ int qmha_attend_cached(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, uns
     if (st == QMHA_OK) st = check_flag_bits(flags);
     if (st != QMHA_OK) return st;
     const bool causal = flags & QMHA_FLAG_CAUSAL;
-    std::lock_guard<std::mutex> lk(c->mu);  // held across the enqueue
-    const int len = c->len;
-    if (causal && Nq > len)
-        return fail(QMHA_ERR_INVALID, "causal attention is bottom-right aligned and needs len >= Nq (Nq = " + std::to_string(Nq) +
-                                          ", len = " + std::to_string(len) + ")");
-    if (!causal && len != c->cap)
-        return fail(QMHA_ERR_INVALID, "attention without QMHA_FLAG_CAUSAL reads all cap = " + std::to_string(c->cap) +
-                                          " rows and the cache holds len = " + std::to_string(len) +
-                                          ": the kernel has no unmasked mode that stops before cap");
-    const hipStream_t s = (hipStream_t)stream;
-    const bool prof = profiling_on();
-    ProfRec rec;
-    st = timed(prof ? &rec.main : nullptr, s, "kv_cache attend launch", [&] {
-        if (c->h_kv < c->h)  // grouped: the carve has h_kv heads
-            return c->variant == QMHA_FA_TC_INT8_B
-                       ? qmha::launch_fa_int8_gqa_cached(qmha::int8_carve(c->mem, c->B, c->cap, c->h_kv, c->D), Q, O, c->B, Nq,
-                                                         c->cap, len, c->h, c->h_kv, c->D, c->d_model, causal, s)
-                       : qmha::launch_fa_f16_gqa_cached(qmha::f16_carve(c->mem, c->B, c->cap, c->h_kv, c->D), Q, O, c->B, Nq,
-                                                        c->cap, len, c->h, c->h_kv, c->D, c->d_model, causal, s);
-        return c->variant == QMHA_FA_TC_INT8_B
-                   ? qmha::launch_fa_int8_masked_cached(qmha::int8_carve(c->mem, c->B, c->cap, c->h, c->D), Q, O, c->B, Nq, c->cap,
-                                                        len, c->h, c->D, c->d_model, causal, s)
-                   : qmha::launch_fa_f16_masked_cached(qmha::f16_carve(c->mem, c->B, c->cap, c->h, c->D), Q, O, c->B, Nq, c->cap,
-                                                       len, c->h, c->D, c->d_model, causal, s);
-    });
-    if (st == QMHA_OK && prof) keep_record(std::move(rec));
-    return st;
+    return cache_enqueue(
+        c, &ProfRec::main, stream, "kv_cache attend launch",
+        [&](int len) {
+            if (causal && Nq > len)
+                return fail(QMHA_ERR_INVALID, "causal attention is bottom-right aligned and needs len >= Nq (Nq = " +
+                                                  std::to_string(Nq) + ", len = " + std::to_string(len) + ")");
+            if (!causal && len != c->cap)
+                return fail(QMHA_ERR_INVALID, "attention without QMHA_FLAG_CAUSAL reads all cap = " + std::to_string(c->cap) +
+                                                  " rows and the cache holds len = " + std::to_string(len) +
+                                                  ": the kernel has no unmasked mode that stops before cap");
+            return (int)QMHA_OK;
+        },
+        [&](const auto& w, int len) {
+            return qmha::launch_fa_masked(w, Q, O, {c->B, Nq, c->cap, c->h, c->h_kv, c->D, c->d_model, causal, len, nullptr},
+                                          (hipStream_t)stream);
+        });
 }
 
 // ---- per-sequence lengths read on the device: the host `len` is neither read nor changed ----
@@ -768,19 +719,9 @@ int qmha_kv_cache_append_at(qmha_kv_cache_t* c, const float* K, const float* V, 
     if (n < 32 || n % 32 != 0) return fail(QMHA_ERR_INVALID, "append_at: n must be a positive multiple of 32");
     if (n > c->cap)
         return fail(QMHA_ERR_INVALID, "append_at: n = " + std::to_string(n) + " rows exceed cap = " + std::to_string(c->cap));
-    std::lock_guard<std::mutex> lk(c->mu);  // held across the enqueue
-    const hipStream_t s = (hipStream_t)stream;
-    const bool prof = profiling_on();
-    ProfRec rec;
-    const int st = timed(prof ? &rec.pre : nullptr, s, "kv_cache append_at launch", [&] {
-        return c->variant == QMHA_FA_TC_INT8_B
-                   ? qmha::launch_kv_place_int8(K, V, qmha::int8_carve(c->mem, c->B, c->cap, c->h_kv, c->D), c->B, n, c->cap, pos,
-                                                c->h_kv, c->D, c->h_kv * c->D, s)
-                   : qmha::launch_kv_place_f16(K, V, qmha::f16_carve(c->mem, c->B, c->cap, c->h_kv, c->D), c->B, n, c->cap, pos,
-                                               c->h_kv, c->D, c->h_kv * c->D, s);
+    return cache_enqueue(c, &ProfRec::pre, stream, "kv_cache append_at launch", kNoLenCheck, [&](const auto& w, int) {
+        return qmha::launch_kv_append(K, V, w, c->B, n, c->cap, 0, pos, c->h_kv, c->D, c->h_kv * c->D, (hipStream_t)stream);
     });
-    if (st == QMHA_OK && prof) keep_record(std::move(rec));
-    return st;
 }
 
 int qmha_attend_cached_varlen(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, const int32_t* lens, unsigned flags,
@@ -795,19 +736,10 @@ int qmha_attend_cached_varlen(qmha_kv_cache_t* c, const float* Q, float* O, int 
     if (causal && Nq > c->cap)
         return fail(QMHA_ERR_INVALID, "causal attention is bottom-right aligned and needs Nq <= cap (Nq = " + std::to_string(Nq) +
                                           ", cap = " + std::to_string(c->cap) + ")");
-    std::lock_guard<std::mutex> lk(c->mu);  // held across the enqueue
-    const hipStream_t s = (hipStream_t)stream;
-    const bool prof = profiling_on();
-    ProfRec rec;
-    st = timed(prof ? &rec.main : nullptr, s, "kv_cache attend_varlen launch", [&] {
-        return c->variant == QMHA_FA_TC_INT8_B
-                   ? qmha::launch_fa_int8_varlen(qmha::int8_carve(c->mem, c->B, c->cap, c->h_kv, c->D), Q, O, lens, c->B, Nq, c->cap,
-                                                 c->h, c->h_kv, c->D, c->d_model, causal, s)
-                   : qmha::launch_fa_f16_varlen(qmha::f16_carve(c->mem, c->B, c->cap, c->h_kv, c->D), Q, O, lens, c->B, Nq, c->cap,
-                                                c->h, c->h_kv, c->D, c->d_model, causal, s);
+    return cache_enqueue(c, &ProfRec::main, stream, "kv_cache attend_varlen launch", kNoLenCheck, [&](const auto& w, int) {
+        return qmha::launch_fa_masked(w, Q, O, {c->B, Nq, c->cap, c->h, c->h_kv, c->D, c->d_model, causal, -1, lens},
+                                      (hipStream_t)stream);
     });
-    if (st == QMHA_OK && prof) keep_record(std::move(rec));
-    return st;
 }
 
 int qmha_solve_variant(const float* Q, const float* K, const float* V, float* O, int N, int d_model, int h,
@@ -897,15 +829,9 @@ int qmha_debug_fa_int8_pstage(const float* Q, const float* K, const float* V, fl
                               int32_t* T, float* l) {
     // qmha_solve_rect's checks for fa_tc_int8_b, then run()'s choice of main kernel
     int D = 0;
-    int st = check_shape(Q, K, V, O, B, Nq, d_model, h, QMHA_FA_TC_INT8_B, &D, "Nq");
-    if (st == QMHA_OK) st = check_shape(Q, K, V, O, B, Nk, d_model, h, QMHA_FA_TC_INT8_B, &D, "Nk");
-    if (st == QMHA_OK) st = check_flag_bits(flags);
+    const int st = check_call({Q, K, V, O, B, Nq, Nk, d_model, h, h, QMHA_FA_TC_INT8_B, flags, false, false, nullptr, 0}, &D);
     if (st != QMHA_OK) return st;
     const bool causal = flags & QMHA_FLAG_CAUSAL;
-    if (causal && Nq > Nk) return fail(QMHA_ERR_INVALID, "causal attention is bottom-right aligned and needs Nk >= Nq");
-    const VariantRow* row = find_variant(QMHA_FA_TC_INT8_B);
-    if ((causal && !built(row->causal, D)) || (Nq != Nk && !built(row->rect, D)))
-        return fail(QMHA_ERR_NOSYS, "debug P-stage dump: fa_tc_int8_b has no causal / rectangular kernel at d = " + std::to_string(D));
     if (!S || !Qi || !sQ || !m || !sP || !Pi || !T || !l) return fail(QMHA_ERR_INVALID, "debug P-stage dump: null buffer");
     return debug_run(qmha::int8_workspace_bytes(B, Nk, h, D), [&](void* ws) -> int {
         const qmha::Int8Workspace w = qmha::int8_carve(ws, B, Nk, h, D);
@@ -914,7 +840,7 @@ int qmha_debug_fa_int8_pstage(const float* Q, const float* K, const float* V, fl
         const qmha::QkDump dbg{S, Qi, sQ};
         const qmha::PDump pd{m, sP, Pi, T, l};
         if (causal || Nq != Nk)
-            QMHA_HIP_TRY(qmha::launch_fa_int8_masked_pstage_dump(w, Q, O, B, Nq, Nk, h, D, d_model, causal, dbg, pd),
+            QMHA_HIP_TRY(qmha::launch_fa_int8_masked_pstage_dump(w, Q, O, {B, Nq, Nk, h, h, D, d_model, causal, -1, nullptr}, dbg, pd),
                          "fa_int8 masked P-stage dump launch");
         else
             QMHA_HIP_TRY(qmha::launch_fa_int8_pstage_dump(w, Q, O, B, Nk, h, D, d_model, dbg, pd), "fa_int8 P-stage dump launch");

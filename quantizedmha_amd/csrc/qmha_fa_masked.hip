@@ -279,8 +279,8 @@ __global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_f16_varle
 }
 
 // ---------------------------------------------------------------------------------------
-// host launchers: square causal calls take the SquareCausal instances, grouped calls (Hkv < H) the Grouped ones,
-// everything else the Rect ones
+// host launchers (MaskedCall in qmha_kernels.hpp): per-sequence lengths take the varlen kernels, grouped calls
+// (Hkv < H) the Grouped instances, square causal calls of their own the SquareCausal ones, everything else Rect
 // ---------------------------------------------------------------------------------------
 static bool masked_shape_ok(int Nq, int Nk, bool causal) {
     return Nq >= QMHA_GROUP && Nk >= QMHA_GROUP && Nq % QMHA_GROUP == 0 && Nk % QMHA_GROUP == 0 && !(causal && Nk < Nq);
@@ -291,149 +291,86 @@ static bool cached_shape_ok(int Nq, int cap, int len, bool causal) {
     if (!masked_shape_ok(Nq, cap, false) || len % QMHA_GROUP != 0) return false;
     return causal ? Nq <= len && len <= cap : len == cap;
 }
-static Rect cached_geo(int Nq, int cap, int len, bool causal) { return causal ? Rect::cached(Nq, cap, len) : Rect(Nq, cap, false); }
-static bool grouped_heads_ok(int B, int H, int Hkv, int D, int d_model) {
-    return B >= 1 && Hkv >= 1 && Hkv < H && H % Hkv == 0 && d_model == H * D;
-}
 static int masked_nqb(int units) { return (units + kWaves - 1) / kWaves; }  // unit blocks per K/V slice
 
-// The geometry of a call of its own, checked, handed to `launch`
+// The geometry of a call, checked, handed to `launch`.  The varlen grid follows Nq, B, Hkv and G only; what lens
+// holds is the kernels' business.
 template <class Launch>
-static hipError_t masked_call(int Nq, int Nk, bool causal, Launch&& launch) {
-    if (!masked_shape_ok(Nq, Nk, causal)) return hipErrorInvalidValue;
-    return causal && Nq == Nk ? launch(SquareCausal{Nq}) : launch(Rect(Nq, Nk, causal));
+static hipError_t masked_geo(const MaskedCall& c, Launch&& launch) {
+    if (c.B < 1 || c.Hkv < 1 || c.Hkv > c.H || c.H % c.Hkv != 0 || c.d_model != c.H * c.D) return hipErrorInvalidValue;
+    const bool cached = !c.lens && c.len >= 0;
+    if (!(cached ? cached_shape_ok(c.Nq, c.Nk, c.len, c.causal) : masked_shape_ok(c.Nq, c.Nk, c.causal))) return hipErrorInvalidValue;
+    const int G = c.H / c.Hkv;
+    if (c.lens) return launch(Varlen(c.Nq, c.Nk, G, c.causal));
+    if (!cached && G == 1 && c.causal && c.Nq == c.Nk) return launch(SquareCausal{c.Nq});
+    const Rect r = cached && c.causal ? Rect::cached(c.Nq, c.Nk, c.len) : Rect(c.Nq, c.Nk, c.causal);
+    return G > 1 ? launch(Grouped(r, G)) : launch(r);
 }
 
-// Launch the instance of `geo`, which the caller has checked, over B * H K/V slices
+// Launch the instance of `geo` over the call's B * Hkv K/V slices (the kernels' H argument); stream: the dump's is null
 template <class Geo>
-static hipError_t fa_int8_masked_launch(const Int8Workspace& w, const float* Qf, float* O, int B, int H, int D, int d_model,
-                                        hipStream_t stream, Geo geo) {
+static hipError_t fa_masked_launch(const Int8Workspace& w, const float* Qf, float* O, const MaskedCall& c, hipStream_t stream, Geo geo) {
     const int nqb = masked_nqb(geo.units());
-    auto launch = [&](auto d) {
-        hipLaunchKernelGGL((qmha_fa_int8_masked_kernel<decltype(d)::value, Geo>), dim3(B * H * masked_pairs(nqb)), dim3(kWaves * 64), 0,
-                           stream, Qf, w.Ki, w.Vh, w.sK, w.sV, O, geo, H, d_model, nqb, softmax_scale_log2(D));
+    const dim3 grid(c.B * c.Hkv * masked_pairs(nqb)), block(kWaves * 64);
+    return int8_masked_d(c.D, [&](auto d) {
+        if constexpr (std::is_same<Geo, Varlen>::value)
+            hipLaunchKernelGGL((qmha_fa_int8_varlen_kernel<decltype(d)::value>), grid, block, 0, stream, Qf, w.Ki, w.Vh, w.sK, w.sV, O,
+                               geo, c.lens, c.Hkv, c.d_model, nqb, softmax_scale_log2(c.D));
+        else
+            hipLaunchKernelGGL((qmha_fa_int8_masked_kernel<decltype(d)::value, Geo>), grid, block, 0, stream, Qf, w.Ki, w.Vh, w.sK,
+                               w.sV, O, geo, c.Hkv, c.d_model, nqb, softmax_scale_log2(c.D));
         return hipGetLastError();
-    };
-    switch (D) {
-        case 32: return launch(std::integral_constant<int, 32>{});
-        case 64: return launch(std::integral_constant<int, 64>{});
-        case 128: return launch(std::integral_constant<int, 128>{});
-        default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t launch_fa_int8_masked_main(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
-                                      int d_model, bool causal, hipStream_t stream) {
-    return masked_call(Nq, Nk, causal, [&](auto geo) { return fa_int8_masked_launch(w, Qf, O, B, H, D, d_model, stream, geo); });
-}
-
-// The dumping twin of the instance launch_fa_int8_masked_main launches for this shape: the same grid and
-// arguments, the geometry wrapped in Dumping<>
-hipError_t launch_fa_int8_masked_pstage_dump(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H,
-                                             int D, int d_model, bool causal, QkDump dbg, PDump pd) {
-    return masked_call(Nq, Nk, causal, [&](auto geo) {
-        return fa_int8_masked_launch(w, Qf, O, B, H, D, d_model, nullptr, Dumping<decltype(geo)>(geo, dbg, pd));
     });
 }
 
 template <class Geo>
-static hipError_t fa_f16_masked_launch(const F16Workspace& w, const float* Qf, float* O, int B, int H, int D, int d_model,
-                                       hipStream_t stream, Geo geo) {
+static hipError_t fa_masked_launch(const F16Workspace& w, const float* Qf, float* O, const MaskedCall& c, hipStream_t stream, Geo geo) {
     const int nqb = masked_nqb(geo.units());
-    auto launch = [&](auto d) {
-        hipLaunchKernelGGL((qmha_fa_f16_masked_kernel<decltype(d)::value, Geo>), dim3(B * H * nqb), dim3(kWaves * 64), 0, stream, Qf,
-                           w.Kh, w.Vt, O, geo, H, d_model, nqb, softmax_scale_log2(D));
+    const dim3 grid(c.B * c.Hkv * nqb), block(kWaves * 64);
+    return f16_masked_d(c.D, [&](auto d) {
+        if constexpr (std::is_same<Geo, Varlen>::value)
+            hipLaunchKernelGGL((qmha_fa_f16_varlen_kernel<decltype(d)::value>), grid, block, 0, stream, Qf, w.Kh, w.Vt, O, geo, c.lens,
+                               c.Hkv, c.d_model, nqb, softmax_scale_log2(c.D));
+        else
+            hipLaunchKernelGGL((qmha_fa_f16_masked_kernel<decltype(d)::value, Geo>), grid, block, 0, stream, Qf, w.Kh, w.Vt, O, geo,
+                               c.Hkv, c.d_model, nqb, softmax_scale_log2(c.D));
         return hipGetLastError();
-    };
-    switch (D) {
-        case 64: return launch(std::integral_constant<int, 64>{});
-        case 128: return launch(std::integral_constant<int, 128>{});
-        default: return hipErrorInvalidValue;
-    }
+    });
 }
 
-hipError_t launch_fa_f16_masked_main(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
-                                     int d_model, bool causal, hipStream_t stream) {
-    return masked_call(Nq, Nk, causal, [&](auto geo) { return fa_f16_masked_launch(w, Qf, O, B, H, D, d_model, stream, geo); });
+// The instances of this file, in the order they stand in its code object (kernels are emitted as they are
+// instantiated).  The order is part of the shipped bytes: the dumping twins reach their out-of-line dump lambdas
+// PC-relative, so what stands before them shows in their code (isa_id).
+#define QMHA_INSTANCE(W, ...) \
+    template hipError_t fa_masked_launch<__VA_ARGS__>(const W&, const float*, float*, const MaskedCall&, hipStream_t, __VA_ARGS__);
+QMHA_INSTANCE(Int8Workspace, SquareCausal)
+QMHA_INSTANCE(Int8Workspace, Dumping<SquareCausal>)
+QMHA_INSTANCE(Int8Workspace, Dumping<Rect>)
+QMHA_INSTANCE(F16Workspace, SquareCausal)
+QMHA_INSTANCE(Int8Workspace, Rect)
+QMHA_INSTANCE(F16Workspace, Rect)
+QMHA_INSTANCE(Int8Workspace, Grouped)
+QMHA_INSTANCE(F16Workspace, Grouped)
+QMHA_INSTANCE(Int8Workspace, Varlen)
+QMHA_INSTANCE(F16Workspace, Varlen)
+#undef QMHA_INSTANCE
+
+hipError_t launch_fa_masked(const Int8Workspace& w, const float* Qf, float* O, const MaskedCall& c, hipStream_t stream) {
+    return masked_geo(c, [&](auto geo) { return fa_masked_launch(w, Qf, O, c, stream, geo); });
 }
 
-// K/V cache: always the Rect instances (also at Nq == len, where a call of its own takes the SquareCausal ones)
-hipError_t launch_fa_int8_masked_cached(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int cap, int len,
-                                        int H, int D, int d_model, bool causal, hipStream_t stream) {
-    if (!cached_shape_ok(Nq, cap, len, causal)) return hipErrorInvalidValue;
-    return fa_int8_masked_launch(w, Qf, O, B, H, D, d_model, stream, cached_geo(Nq, cap, len, causal));
+hipError_t launch_fa_masked(const F16Workspace& w, const float* Qf, float* O, const MaskedCall& c, hipStream_t stream) {
+    return masked_geo(c, [&](auto geo) { return fa_masked_launch(w, Qf, O, c, stream, geo); });
 }
 
-hipError_t launch_fa_f16_masked_cached(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int cap, int len,
-                                       int H, int D, int d_model, bool causal, hipStream_t stream) {
-    if (!cached_shape_ok(Nq, cap, len, causal)) return hipErrorInvalidValue;
-    return fa_f16_masked_launch(w, Qf, O, B, H, D, d_model, stream, cached_geo(Nq, cap, len, causal));
-}
-
-// Grouped-query (Hkv < H): always the Grouped instances, for every Nq and Nk, over B * Hkv K/V slices
-hipError_t launch_fa_int8_gqa_main(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int Hkv,
-                                   int D, int d_model, bool causal, hipStream_t stream) {
-    if (!grouped_heads_ok(B, H, Hkv, D, d_model) || !masked_shape_ok(Nq, Nk, causal)) return hipErrorInvalidValue;
-    return fa_int8_masked_launch(w, Qf, O, B, Hkv, D, d_model, stream, Grouped(Rect(Nq, Nk, causal), H / Hkv));
-}
-
-hipError_t launch_fa_f16_gqa_main(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int Hkv,
-                                  int D, int d_model, bool causal, hipStream_t stream) {
-    if (!grouped_heads_ok(B, H, Hkv, D, d_model) || !masked_shape_ok(Nq, Nk, causal)) return hipErrorInvalidValue;
-    return fa_f16_masked_launch(w, Qf, O, B, Hkv, D, d_model, stream, Grouped(Rect(Nq, Nk, causal), H / Hkv));
-}
-
-hipError_t launch_fa_int8_gqa_cached(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int cap, int len, int H,
-                                     int Hkv, int D, int d_model, bool causal, hipStream_t stream) {
-    if (!grouped_heads_ok(B, H, Hkv, D, d_model) || !cached_shape_ok(Nq, cap, len, causal)) return hipErrorInvalidValue;
-    return fa_int8_masked_launch(w, Qf, O, B, Hkv, D, d_model, stream, Grouped(cached_geo(Nq, cap, len, causal), H / Hkv));
-}
-
-hipError_t launch_fa_f16_gqa_cached(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int cap, int len, int H,
-                                    int Hkv, int D, int d_model, bool causal, hipStream_t stream) {
-    if (!grouped_heads_ok(B, H, Hkv, D, d_model) || !cached_shape_ok(Nq, cap, len, causal)) return hipErrorInvalidValue;
-    return fa_f16_masked_launch(w, Qf, O, B, Hkv, D, d_model, stream, Grouped(cached_geo(Nq, cap, len, causal), H / Hkv));
-}
-
-// Per-sequence lengths: the varlen kernels over B * Hkv K/V slices, Hkv == H (G = 1) included.  The
-// grid follows Nq, B, Hkv and G only; what lens holds is the kernels' business.
-static bool varlen_call_ok(int B, int Nq, int cap, int H, int Hkv, int D, int d_model, bool causal, const int32_t* lens) {
-    return lens && B >= 1 && Hkv >= 1 && Hkv <= H && H % Hkv == 0 && d_model == H * D && masked_shape_ok(Nq, cap, causal);
-}
-
-hipError_t launch_fa_int8_varlen(const Int8Workspace& w, const float* Qf, float* O, const int32_t* lens, int B, int Nq, int cap,
-                                 int H, int Hkv, int D, int d_model, bool causal, hipStream_t stream) {
-    if (!varlen_call_ok(B, Nq, cap, H, Hkv, D, d_model, causal, lens)) return hipErrorInvalidValue;
-    const Varlen geo(Nq, cap, H / Hkv, causal);
-    const int nqb = masked_nqb(geo.units());
-    switch (D) {
-#define QMHA_CASE(d)                                                                                                          \
-    case d:                                                                                                                   \
-        hipLaunchKernelGGL((qmha_fa_int8_varlen_kernel<d>), dim3(B * Hkv * masked_pairs(nqb)), dim3(kWaves * 64), 0, stream, Qf, \
-                           w.Ki, w.Vh, w.sK, w.sV, O, geo, lens, Hkv, d_model, nqb, softmax_scale_log2(D));                    \
-        return hipGetLastError();
-        QMHA_CASE(32) QMHA_CASE(64) QMHA_CASE(128)
-#undef QMHA_CASE
-        default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t launch_fa_f16_varlen(const F16Workspace& w, const float* Qf, float* O, const int32_t* lens, int B, int Nq, int cap,
-                                int H, int Hkv, int D, int d_model, bool causal, hipStream_t stream) {
-    if (!varlen_call_ok(B, Nq, cap, H, Hkv, D, d_model, causal, lens)) return hipErrorInvalidValue;
-    const Varlen geo(Nq, cap, H / Hkv, causal);
-    const int nqb = masked_nqb(geo.units());
-    switch (D) {
-#define QMHA_CASE(d)                                                                                                      \
-    case d:                                                                                                               \
-        hipLaunchKernelGGL((qmha_fa_f16_varlen_kernel<d>), dim3(B * Hkv * nqb), dim3(kWaves * 64), 0, stream, Qf, w.Kh, w.Vt, \
-                           O, geo, lens, Hkv, d_model, nqb, softmax_scale_log2(D));                                        \
-        return hipGetLastError();
-        QMHA_CASE(64) QMHA_CASE(128)
-#undef QMHA_CASE
-        default: return hipErrorInvalidValue;
-    }
+// The dumping twin of the instance launch_fa_masked launches: the same grid and arguments, the geometry wrapped in
+// Dumping<>, which the grouped and varlen geometries do not have
+hipError_t launch_fa_int8_masked_pstage_dump(const Int8Workspace& w, const float* Qf, float* O, const MaskedCall& c, QkDump dbg,
+                                             PDump pd) {
+    return masked_geo(c, [&](auto geo) {
+        if constexpr (std::is_base_of<Grouped, decltype(geo)>::value) return hipErrorInvalidValue;
+        else return fa_masked_launch(w, Qf, O, c, nullptr, Dumping<decltype(geo)>(geo, dbg, pd));
+    });
 }
 
 }  // namespace qmha
-

@@ -6,6 +6,7 @@
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace qmha {
 
@@ -128,14 +129,12 @@ struct PDump {
 };
 hipError_t launch_fa_int8_dump(const Int8Workspace& w, const float* Qf, float* O, int B, int N, int H, int D,
                                int d_model, QkDump dbg, hipStream_t stream);
-// The dumping twin of the kernel launch_fa_int8_main (Nq == Nk, not causal) or launch_fa_int8_masked_main would
-// launch for this shape, N = 32 included; every buffer of dbg and pd is written.  On the null stream, for the
-// blocking debug hook: the non-causal twins' device variable is set before the launch and cleared after it with
+// The dumping twin of the kernel launch_fa_int8_main (Nq == Nk, not causal; launch_fa_masked's is declared with it
+// below) would launch for this shape, N = 32 included; every buffer of dbg and pd is written.  On the null stream, for
+// the blocking debug hook: the non-causal twins' device variable is set before the launch and cleared after it with
 // blocking copies.
 hipError_t launch_fa_int8_pstage_dump(const Int8Workspace& w, const float* Qf, float* O, int B, int N, int H, int D,
                                       int d_model, QkDump dbg, PDump pd);
-hipError_t launch_fa_int8_masked_pstage_dump(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk,
-                                             int H, int D, int d_model, bool causal, QkDump dbg, PDump pd);
 hipError_t launch_fa_int8_pt_dump(const Int8Workspace& w, const float* Qf, float* O, int B, int N, int H, int D,
                                   int d_model, QkDump dbg, hipStream_t stream);
 
@@ -160,62 +159,63 @@ hipError_t launch_convert_f16(const float* Q, const float* K, const float* V, co
 hipError_t launch_fa_f16_main(const F16Workspace& w, const float* Qf, float* O, int B, int N, int H, int D, int d_model,
                               hipStream_t stream);
 
-// ---- causal and rectangular main kernels (qmha_fa_masked.hip) ---------------
-// the same workspaces as the non-causal paths (the pre-pass is unchanged, run with N = Nk); Q / O have Nq rows.
-// causal: bottom-right aligned (row r attends keys j <= r + Nk - Nq, Nk >= Nq; Nq == Nk: j <= r, the square
-// causal instances).  Nq, Nk multiples of 32; int8: d in {32, 64, 128}; fp16: d in {64, 128} (qmha_api.cpp's
-// variant table); anything else: hipErrorInvalidValue
-hipError_t launch_fa_int8_masked_main(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H,
-                                      int D, int d_model, bool causal, hipStream_t stream);
-hipError_t launch_fa_f16_masked_main(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int D,
-                                     int d_model, bool causal, hipStream_t stream);
+// ---- the built head sizes of the masked and cache kernels: f(std::integral_constant<int, D>) --------
+template <class F>
+hipError_t int8_masked_d(int D, F&& f) {
+    switch (D) {
+        case 32: return f(std::integral_constant<int, 32>{});
+        case 64: return f(std::integral_constant<int, 64>{});
+        case 128: return f(std::integral_constant<int, 128>{});
+        default: return hipErrorInvalidValue;
+    }
+}
+template <class F>
+hipError_t f16_masked_d(int D, F&& f) {
+    switch (D) {
+        case 64: return f(std::integral_constant<int, 64>{});
+        case 128: return f(std::integral_constant<int, 128>{});
+        default: return hipErrorInvalidValue;
+    }
+}
 
-// ---- persistent K/V cache (qmha_kv_cache_*) ---------------------------------------
-// w: the variant's carve at N = cap, in caller-owned memory; `len` of its `cap` rows per head slice are valid.
-// Append (qmha_prepass.hip): the pre-pass of the n new rows K, V [B, n, d_model] into rows [len, len + n) of every
-// slice; n, cap, len multiples of 32, len + n <= cap; the bytes are those the pre-pass of a whole call writes there.
-hipError_t launch_kv_append_int8(const float* K, const float* V, const Int8Workspace& w, int B, int n, int cap, int len,
-                                 int H, int D, int d_model, hipStream_t stream);
-hipError_t launch_kv_append_f16(const float* K, const float* V, const F16Workspace& w, int B, int n, int cap, int len,
-                                int H, int D, int d_model, hipStream_t stream);
-// Attend (qmha_fa_masked.hip): the shipped Rect instances with Nk = cap.  causal: bottom-right aligned over the first
-// `len` rows (row r attends cache rows j <= r + len - Nq; Nq <= len <= cap), diag_off = (len - Nq) / 32, so no tile
-// at or beyond len / 32 is staged or computed.  Not causal: every row attends all cap rows, which needs len == cap
-// (the kernel has no unmasked mode that stops before cap / 32).  Anything else: hipErrorInvalidValue.
-hipError_t launch_fa_int8_masked_cached(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int cap, int len,
-                                        int H, int D, int d_model, bool causal, hipStream_t stream);
-hipError_t launch_fa_f16_masked_cached(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int cap, int len,
-                                       int H, int D, int d_model, bool causal, hipStream_t stream);
+// ---- masked main kernels (qmha_fa_masked.hip) ---------------------
+// One launch of the masked templates.  Q / O: [B, Nq, d_model = H * D].  w: the variant's carve over K / V of Hkv heads
+// and Nk rows -- the workspace of the non-causal paths, whose pre-pass ran unchanged with N = Nk, H = Hkv and
+// d_model = Hkv * D; Hkv < H (H % Hkv == 0) is grouped-query attention.  Nq, Nk multiples of 32.  Three modes:
+//   a call of its own (len < 0, lens null): all Nk rows.  causal: bottom-right aligned, row r attends keys
+//     j <= r + Nk - Nq (Nk >= Nq).  Hkv == H: SquareCausal when causal and Nq == Nk, else Rect; Hkv < H: Grouped.
+//   a K/V cache (len >= 0): Nk = cap, and `len` of the cap rows per slice are valid (len % 32 == 0).  causal: over the
+//     first len rows (j <= r + len - Nq, Nq <= len <= cap), diag_off = (len - Nq) / 32, so no tile at or beyond
+//     len / 32 is staged or computed; not causal: every row attends all cap rows, which needs len == cap.  Always Rect
+//     (or Grouped over it), also at Nq == len.
+//   per-sequence lengths (lens: DEVICE int32[B], read by the kernel; the grid follows the host arguments only): the
+//     varlen kernels, Hkv == H included.  Sequence b computes what the cache mode computes at len = lens[b] -- without
+//     the mask over rows [0, lens[b]), whatever cap is --; lens[b] % 32 != 0, > cap, < Nq (causal) or < 32 (not): its O
+//     rows are zeros and none of its K/V is read.
+// B * Hkv K/V slices per grid.  int8: d in {32, 64, 128}; fp16: d in {64, 128} (qmha_api.cpp's variant table).  A shape
+// or head count outside the above, d_model != H * D, an unbuilt d: hipErrorInvalidValue, nothing launched.
+struct MaskedCall {
+    int B, Nq, Nk, H, Hkv, D, d_model;
+    bool causal;
+    int len;
+    const int32_t* lens;
+};
+hipError_t launch_fa_masked(const Int8Workspace& w, const float* Qf, float* O, const MaskedCall& c, hipStream_t stream);
+hipError_t launch_fa_masked(const F16Workspace& w, const float* Qf, float* O, const MaskedCall& c, hipStream_t stream);
+// The dumping twin of the instance launch_fa_masked launches for a call of its own with Hkv == H; no other mode has one
+hipError_t launch_fa_int8_masked_pstage_dump(const Int8Workspace& w, const float* Qf, float* O, const MaskedCall& c, QkDump dbg,
+                                             PDump pd);
 
-// ---- grouped-query attention (qmha_fa_masked.hip, the Grouped instances) ----------
-// H query heads share Hkv < H key/value heads (H % Hkv == 0).  Q / O: [B, Nq, d_model = H * D]; w: the variant's
-// carve over K / V of [B, Nk, Hkv * D], i.e. at H = Hkv (the pre-passes and the appends run unchanged with H = Hkv
-// and d_model = Hkv * D).  Shapes, mask and head sizes as launch_fa_*_masked_main / _cached above, for every Nq
-// and Nk (square and unmasked calls included); anything else, Hkv == H too: hipErrorInvalidValue.
-hipError_t launch_fa_int8_gqa_main(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int Hkv,
-                                   int D, int d_model, bool causal, hipStream_t stream);
-hipError_t launch_fa_f16_gqa_main(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int Nk, int H, int Hkv,
-                                  int D, int d_model, bool causal, hipStream_t stream);
-hipError_t launch_fa_int8_gqa_cached(const Int8Workspace& w, const float* Qf, float* O, int B, int Nq, int cap, int len, int H,
-                                     int Hkv, int D, int d_model, bool causal, hipStream_t stream);
-hipError_t launch_fa_f16_gqa_cached(const F16Workspace& w, const float* Qf, float* O, int B, int Nq, int cap, int len, int H,
-                                    int Hkv, int D, int d_model, bool causal, hipStream_t stream);
-
-// ---- per-sequence lengths read on the device (qmha_kv_cache_append_at, qmha_attend_cached_varlen) ----
-// pos, lens: DEVICE int32[B], read by the kernels; the grids follow the host arguments only.  w: the carve of Hkv heads
-// at N = cap (Hkv == H: a multi-head cache).  Place: sequence b's n rows go to rows [pos[b], pos[b] + n) of its slices,
-// byte for byte what launch_kv_append_* writes at len = pos[b]; pos[b] < 0, pos[b] % 32 != 0 or pos[b] + n > cap: that
-// sequence writes nothing.  Attend: sequence b computes what launch_fa_*_{masked,gqa}_cached computes at len = lens[b]
-// -- without the mask over rows [0, lens[b]), whatever cap is --; lens[b] % 32 != 0, > cap, < Nq (causal) or < 32 (not):
-// its O rows are zeros and none of its K/V is read.  Bad host arguments, a null pos / lens too: hipErrorInvalidValue.
-hipError_t launch_kv_place_int8(const float* K, const float* V, const Int8Workspace& w, int B, int n, int cap,
-                                const int32_t* pos, int H, int D, int d_model, hipStream_t stream);
-hipError_t launch_kv_place_f16(const float* K, const float* V, const F16Workspace& w, int B, int n, int cap,
-                               const int32_t* pos, int H, int D, int d_model, hipStream_t stream);
-hipError_t launch_fa_int8_varlen(const Int8Workspace& w, const float* Qf, float* O, const int32_t* lens, int B, int Nq, int cap,
-                                 int H, int Hkv, int D, int d_model, bool causal, hipStream_t stream);
-hipError_t launch_fa_f16_varlen(const F16Workspace& w, const float* Qf, float* O, const int32_t* lens, int B, int Nq, int cap,
-                                int H, int Hkv, int D, int d_model, bool causal, hipStream_t stream);
+// ---- K/V cache append (qmha_prepass.hip) ----------------------------------------
+// w: the variant's carve of H heads at N = cap, in caller-owned memory.  The pre-pass of the n new rows K, V
+// [B, n, d_model = H * D] into rows [len, len + n) of every slice, byte for byte what the pre-pass of a whole call writes
+// there; n, cap, len multiples of 32, len + n <= cap.  pos non-null (DEVICE int32[B], read by the kernel; len ignored):
+// sequence b's rows go to [pos[b], pos[b] + n); pos[b] < 0, pos[b] % 32 != 0 or pos[b] + n > cap: that sequence writes
+// nothing.  Bad host arguments: hipErrorInvalidValue.
+hipError_t launch_kv_append(const float* K, const float* V, const Int8Workspace& w, int B, int n, int cap, int len,
+                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream);
+hipError_t launch_kv_append(const float* K, const float* V, const F16Workspace& w, int B, int n, int cap, int len,
+                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream);
 
 // ---- FP32 (fa: scalar VALU kernel; fa_mfma: the same contract on v_mfma_f32_32x32x2_f32) -----
 hipError_t launch_fa_f32(const float* Q, const float* K, const float* V, float* O, int B, int N, int H, int D,

@@ -674,83 +674,43 @@ hipError_t launch_convert_f16(const float* Q, const float* K, const float* V, co
     }
 }
 
-// ---- K/V cache append: w is the carve at N = cap; rows [len, len + n) of every head slice are written ----
+// ---- K/V cache append: w is the carve at N = cap; rows [len, len + n) of every head slice are written, or, with a
+// pos (read on the device), rows [pos[b], pos[b] + n) of sequence b's by the place kernels ----
 static bool kv_append_shape_ok(int B, int n, int cap, int len, int H) {
     return B >= 1 && H >= 1 && n >= QMHA_GROUP && n % QMHA_GROUP == 0 && cap % QMHA_GROUP == 0 && len >= 0 &&
            len % QMHA_GROUP == 0 && (long long)len + n <= cap;
 }
 
-hipError_t launch_kv_append_int8(const float* K, const float* V, const Int8Workspace& w, int B, int n, int cap, int len,
-                                 int H, int D, int d_model, hipStream_t stream) {
-    if (!kv_append_shape_ok(B, n, cap, len, H)) return hipErrorInvalidValue;
+hipError_t launch_kv_append(const float* K, const float* V, const Int8Workspace& w, int B, int n, int cap, int len,
+                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream) {
+    if (!kv_append_shape_ok(B, n, cap, pos ? 0 : len, H)) return hipErrorInvalidValue;
     const int total = B * H * (n / QMHA_GROUP);
     const dim3 grid((total + 3) / 4, 2);
-    switch (D) {
-#define QMHA_CASE(d)                                                                                                    \
-    case d:                                                                                                             \
-        hipLaunchKernelGGL((qmha_kv_append_int8_kernel<d>), grid, dim3(256), 0, stream, K, V, w.Ki, w.Vh, w.sK, w.sV, n, \
-                           cap, len, H, d_model, total);                                                                \
+    return int8_masked_d(D, [&](auto d) {
+        if (pos)
+            hipLaunchKernelGGL((qmha_kv_place_int8_kernel<decltype(d)::value>), grid, dim3(256), 0, stream, K, V, w.Ki, w.Vh, w.sK,
+                               w.sV, n, cap, pos, H, d_model, total);
+        else
+            hipLaunchKernelGGL((qmha_kv_append_int8_kernel<decltype(d)::value>), grid, dim3(256), 0, stream, K, V, w.Ki, w.Vh, w.sK,
+                               w.sV, n, cap, len, H, d_model, total);
         return hipGetLastError();
-        QMHA_CASE(32) QMHA_CASE(64) QMHA_CASE(128)
-#undef QMHA_CASE
-        default: return hipErrorInvalidValue;
-    }
+    });
 }
 
-hipError_t launch_kv_append_f16(const float* K, const float* V, const F16Workspace& w, int B, int n, int cap, int len,
-                                int H, int D, int d_model, hipStream_t stream) {
-    if (!kv_append_shape_ok(B, n, cap, len, H)) return hipErrorInvalidValue;
+hipError_t launch_kv_append(const float* K, const float* V, const F16Workspace& w, int B, int n, int cap, int len,
+                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream) {
+    if (!kv_append_shape_ok(B, n, cap, pos ? 0 : len, H)) return hipErrorInvalidValue;
     const int total = B * H * (n / QMHA_GROUP);
     const dim3 grid((total + 3) / 4, 2);
-    switch (D) {
-#define QMHA_CASE(d)                                                                                                \
-    case d:                                                                                                         \
-        hipLaunchKernelGGL((qmha_kv_append_f16_kernel<d>), grid, dim3(256), 0, stream, K, V, w.Kh, w.Vt, n, cap, len, \
-                           H, d_model, total);                                                                      \
+    return f16_masked_d(D, [&](auto d) {
+        if (pos)
+            hipLaunchKernelGGL((qmha_kv_place_f16_kernel<decltype(d)::value>), grid, dim3(256), 0, stream, K, V, w.Kh, w.Vt, n, cap,
+                               pos, H, d_model, total);
+        else
+            hipLaunchKernelGGL((qmha_kv_append_f16_kernel<decltype(d)::value>), grid, dim3(256), 0, stream, K, V, w.Kh, w.Vt, n, cap,
+                               len, H, d_model, total);
         return hipGetLastError();
-        QMHA_CASE(64) QMHA_CASE(128)
-#undef QMHA_CASE
-        default: return hipErrorInvalidValue;
-    }
-}
-
-// ---- K/V cache placement: as the appends, rows [pos[b], pos[b] + n) of sequence b's slices; pos is read on the device ----
-static bool kv_place_shape_ok(int B, int n, int cap, const int32_t* pos, int H) {
-    return pos && kv_append_shape_ok(B, n, cap, 0, H);
-}
-
-hipError_t launch_kv_place_int8(const float* K, const float* V, const Int8Workspace& w, int B, int n, int cap,
-                                const int32_t* pos, int H, int D, int d_model, hipStream_t stream) {
-    if (!kv_place_shape_ok(B, n, cap, pos, H)) return hipErrorInvalidValue;
-    const int total = B * H * (n / QMHA_GROUP);
-    const dim3 grid((total + 3) / 4, 2);
-    switch (D) {
-#define QMHA_CASE(d)                                                                                                   \
-    case d:                                                                                                            \
-        hipLaunchKernelGGL((qmha_kv_place_int8_kernel<d>), grid, dim3(256), 0, stream, K, V, w.Ki, w.Vh, w.sK, w.sV, n, \
-                           cap, pos, H, d_model, total);                                                               \
-        return hipGetLastError();
-        QMHA_CASE(32) QMHA_CASE(64) QMHA_CASE(128)
-#undef QMHA_CASE
-        default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t launch_kv_place_f16(const float* K, const float* V, const F16Workspace& w, int B, int n, int cap,
-                               const int32_t* pos, int H, int D, int d_model, hipStream_t stream) {
-    if (!kv_place_shape_ok(B, n, cap, pos, H)) return hipErrorInvalidValue;
-    const int total = B * H * (n / QMHA_GROUP);
-    const dim3 grid((total + 3) / 4, 2);
-    switch (D) {
-#define QMHA_CASE(d)                                                                                               \
-    case d:                                                                                                        \
-        hipLaunchKernelGGL((qmha_kv_place_f16_kernel<d>), grid, dim3(256), 0, stream, K, V, w.Kh, w.Vt, n, cap, pos, \
-                           H, d_model, total);                                                                     \
-        return hipGetLastError();
-        QMHA_CASE(64) QMHA_CASE(128)
-#undef QMHA_CASE
-        default: return hipErrorInvalidValue;
-    }
+    });
 }
 
 }  // namespace qmha

@@ -32,38 +32,67 @@
 
 using torch::Tensor;
 
-static Tensor flash_solve(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t d_model, int64_t num_heads,
-                          const std::string& kernel = "fa_tc_int8_b", bool causal = false) {
+// Q, K and V of a solve, made contiguous: all on the GPU and float32, with the reference's messages
+struct Inputs { Tensor Q, K, V; };
+static Inputs fp32_inputs(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t d_model) {
     TORCH_CHECK(Q.is_cuda() && K.is_cuda() && V.is_cuda(), "Inputs must be CUDA tensors");
     TORCH_CHECK(Q.dtype() == torch::kFloat32, "Q must be float32");
     TORCH_CHECK(K.dtype() == torch::kFloat32, "K must be float32");
     TORCH_CHECK(V.dtype() == torch::kFloat32, "V must be float32");
-    auto Qc = Q.contiguous();
-    auto Kc = K.contiguous();
-    auto Vc = V.contiguous();
-    const int64_t q_elems = Qc.numel();
-    TORCH_CHECK(d_model > 0 && q_elems % d_model == 0, "Q.numel() must be divisible by d_model");
-    TORCH_CHECK(Kc.sizes() == Qc.sizes() && Vc.sizes() == Qc.sizes(), "Q, K and V must have the same shape");
-    // [B, N, d_model] is B sequences; any other layout is one sequence of numel / d_model rows,
-    // as in the reference (torch_ext.cpp:23-25), e.g. [N, h, d]
-    const bool batched = Qc.dim() == 3 && Qc.size(2) == d_model;
-    const int64_t B = batched ? Qc.size(0) : 1;
-    const int64_t N = batched ? Qc.size(1) : q_elems / d_model;
-    int variant = qmha_variant_from_name(kernel.c_str());
-    if (variant < 0) {
-        TORCH_WARN("Kernel selection supports fa, fa_tc_v1a, fa_tc_int8_b, unfused, fa_mfma, fa_tc_int8_pt; '", kernel,
-                   "' routing to default 'fa_tc_int8_b'");
-        variant = QMHA_FA_TC_INT8_B;
-    }
-    auto out = torch::empty_like(Qc);
-    const c10::hip::HIPGuardMasqueradingAsCUDA guard(Qc.device());
-    const hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(Qc.device().index()).stream();
+    Inputs in{Q.contiguous(), K.contiguous(), V.contiguous()};
+    TORCH_CHECK(d_model > 0 && in.Q.numel() % d_model == 0, "Q.numel() must be divisible by d_model");
+    return in;
+}
+
+// an unknown kernel name warns and routes to the default (torch_ext.cpp:32-34)
+static int known_variant(const std::string& kernel) {
+    const int variant = qmha_variant_from_name(kernel.c_str());
+    if (variant >= 0) return variant;
+    TORCH_WARN("Kernel selection supports fa, fa_tc_v1a, fa_tc_int8_b, unfused, fa_mfma, fa_tc_int8_pt; '", kernel,
+               "' routing to default 'fa_tc_int8_b'");
+    return QMHA_FA_TC_INT8_B;
+}
+
+// the caller's `out`, checked against Qc by size, or a new tensor like Qc
+static Tensor out_for(const std::optional<Tensor>& out, const Tensor& Qc) {
+    if (!out) return torch::empty_like(Qc);
+    TORCH_CHECK(out->numel() == Qc.numel() && out->dtype() == torch::kFloat32 && out->device() == Qc.device() &&
+                    out->is_contiguous(),
+                "out must be a contiguous float32 tensor of Q's size on Q's device");
+    return *out;
+}
+
+// [B, N, width] is B sequences; anything else one sequence of numel / width rows (reference torch_ext.cpp:23-25)
+static int64_t rows_of(const Tensor& t, int64_t width, int64_t* B) {
+    const bool batched = t.dim() == 3 && t.size(2) == width;
+    *B = batched ? t.size(0) : 1;
+    return batched ? t.size(1) : t.numel() / width;
+}
+
+// `device` made current for as long as the result lives, and PyTorch's current stream there
+struct OnStream {
+    c10::hip::HIPGuardMasqueradingAsCUDA guard;
+    hipStream_t stream;
+};
+static OnStream current_stream(const c10::Device& device) {
+    return {c10::hip::HIPGuardMasqueradingAsCUDA(device), c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(device.index()).stream()};
+}
+
+static Tensor flash_solve(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t d_model, int64_t num_heads,
+                          const std::string& kernel = "fa_tc_int8_b", bool causal = false) {
+    const Inputs in = fp32_inputs(Q, K, V, d_model);
+    TORCH_CHECK(in.K.sizes() == in.Q.sizes() && in.V.sizes() == in.Q.sizes(), "Q, K and V must have the same shape");
+    int64_t B = 1;
+    const int64_t N = rows_of(in.Q, d_model, &B);
+    const int variant = known_variant(kernel);
+    auto out = torch::empty_like(in.Q);
+    const OnStream on = current_stream(in.Q.device());
     // causal = false enqueues exactly what qmha_solve_ex does (flags == 0)
-    const int st = qmha_solve_opts(Qc.data_ptr<float>(), Kc.data_ptr<float>(), Vc.data_ptr<float>(),
+    const int st = qmha_solve_opts(in.Q.data_ptr<float>(), in.K.data_ptr<float>(), in.V.data_ptr<float>(),
                                    out.data_ptr<float>(), static_cast<int>(B), static_cast<int>(N),
                                    static_cast<int>(d_model), static_cast<int>(num_heads), variant,
-                                   causal ? QMHA_FLAG_CAUSAL : 0u, nullptr, 0, stream);
-    TORCH_CHECK(st == QMHA_OK, "flash_solve(", kernel, "): ", qmha_status_string(st), ": ", qmha_last_error());
+                                   causal ? QMHA_FLAG_CAUSAL : 0u, nullptr, 0, on.stream);
+    TORCH_CHECK(st == QMHA_OK, "flash_solve", "(", kernel, "): ", qmha_status_string(st), ": ", qmha_last_error());
     return out;
 }
 
@@ -72,49 +101,31 @@ static Tensor flash_solve(const Tensor& Q, const Tensor& K, const Tensor& V, int
 // num_kv_heads (flash_solve_gqa): K and V are [Nk, num_kv_heads * d] or [B, Nk, num_kv_heads * d]; none: flash_solve_rect
 static Tensor solve_rect(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t d_model, int64_t num_heads,
                          std::optional<int64_t> num_kv_heads, const std::string& kernel, bool causal, const char* what) {
-    TORCH_CHECK(Q.is_cuda() && K.is_cuda() && V.is_cuda(), "Inputs must be CUDA tensors");
-    TORCH_CHECK(Q.dtype() == torch::kFloat32, "Q must be float32");
-    TORCH_CHECK(K.dtype() == torch::kFloat32, "K must be float32");
-    TORCH_CHECK(V.dtype() == torch::kFloat32, "V must be float32");
-    auto Qc = Q.contiguous();
-    auto Kc = K.contiguous();
-    auto Vc = V.contiguous();
-    TORCH_CHECK(d_model > 0 && Qc.numel() % d_model == 0, "Q.numel() must be divisible by d_model");
-    TORCH_CHECK(Kc.sizes() == Vc.sizes(), "K and V must have the same shape");
+    const Inputs in = fp32_inputs(Q, K, V, d_model);
+    TORCH_CHECK(in.K.sizes() == in.V.sizes(), "K and V must have the same shape");
     int64_t kv_model = d_model;
     if (num_kv_heads) {
         TORCH_CHECK(num_heads >= 1 && d_model % num_heads == 0 && *num_kv_heads >= 1,
                     "d_model must be divisible by num_heads, and num_kv_heads positive");
         kv_model = *num_kv_heads * (d_model / num_heads);
     }
-    TORCH_CHECK(Kc.numel() % kv_model == 0,
+    TORCH_CHECK(in.K.numel() % kv_model == 0,
                 num_kv_heads ? "K.numel() must be divisible by num_kv_heads * d" : "K.numel() must be divisible by d_model");
-    const auto rows = [](const Tensor& t, int64_t width, int64_t* B) {  // flash_solve's shape rule
-        const bool batched = t.dim() == 3 && t.size(2) == width;
-        *B = batched ? t.size(0) : 1;
-        return batched ? t.size(1) : t.numel() / width;
-    };
     int64_t B = 1, Bk = 1;
-    const int64_t Nq = rows(Qc, d_model, &B), Nk = rows(Kc, kv_model, &Bk);
+    const int64_t Nq = rows_of(in.Q, d_model, &B), Nk = rows_of(in.K, kv_model, &Bk);
     TORCH_CHECK(B == Bk, "Q and K must have the same batch count");
-    int variant = qmha_variant_from_name(kernel.c_str());
-    if (variant < 0) {
-        TORCH_WARN("Kernel selection supports fa, fa_tc_v1a, fa_tc_int8_b, unfused, fa_mfma, fa_tc_int8_pt; '", kernel,
-                   "' routing to default 'fa_tc_int8_b'");
-        variant = QMHA_FA_TC_INT8_B;
-    }
-    auto out = torch::empty_like(Qc);
-    const c10::hip::HIPGuardMasqueradingAsCUDA guard(Qc.device());
-    const hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(Qc.device().index()).stream();
+    const int variant = known_variant(kernel);
+    auto out = torch::empty_like(in.Q);
+    const OnStream on = current_stream(in.Q.device());
     const unsigned flags = causal ? QMHA_FLAG_CAUSAL : 0u;
     const int st =
         num_kv_heads
-            ? qmha_solve_gqa(Qc.data_ptr<float>(), Kc.data_ptr<float>(), Vc.data_ptr<float>(), out.data_ptr<float>(),
+            ? qmha_solve_gqa(in.Q.data_ptr<float>(), in.K.data_ptr<float>(), in.V.data_ptr<float>(), out.data_ptr<float>(),
                              static_cast<int>(B), static_cast<int>(Nq), static_cast<int>(Nk), static_cast<int>(d_model),
-                             static_cast<int>(num_heads), static_cast<int>(*num_kv_heads), variant, flags, nullptr, 0, stream)
-            : qmha_solve_rect(Qc.data_ptr<float>(), Kc.data_ptr<float>(), Vc.data_ptr<float>(), out.data_ptr<float>(),
+                             static_cast<int>(num_heads), static_cast<int>(*num_kv_heads), variant, flags, nullptr, 0, on.stream)
+            : qmha_solve_rect(in.Q.data_ptr<float>(), in.K.data_ptr<float>(), in.V.data_ptr<float>(), out.data_ptr<float>(),
                               static_cast<int>(B), static_cast<int>(Nq), static_cast<int>(Nk), static_cast<int>(d_model),
-                              static_cast<int>(num_heads), variant, flags, nullptr, 0, stream);
+                              static_cast<int>(num_heads), variant, flags, nullptr, 0, on.stream);
     TORCH_CHECK(st == QMHA_OK, what, "(", kernel, "): ", qmha_status_string(st), ": ", qmha_last_error());
     return out;
 }
@@ -158,7 +169,7 @@ public:
                                            static_cast<int>(d_model), static_cast<int>(num_heads), static_cast<int>(*num_kv_heads), variant)
                 : qmha_kv_cache_create(&handle_, mem_.data_ptr(), bytes, static_cast<int>(B), static_cast<int>(cap),
                                        static_cast<int>(d_model), static_cast<int>(num_heads), variant);
-        TORCH_CHECK(st == QMHA_OK, "KVCache(", kernel, "): ", qmha_status_string(st), ": ", qmha_last_error());
+        TORCH_CHECK(st == QMHA_OK, "KVCache", "(", kernel, "): ", qmha_status_string(st), ": ", qmha_last_error());
     }
     ~KVCache() { qmha_kv_cache_destroy(handle_); }
     KVCache(const KVCache&) = delete;
@@ -171,20 +182,18 @@ public:
     void append(const Tensor& K, const Tensor& V) {
         auto Kc = rows(K, "K", kv_model_), Vc = rows(V, "V", kv_model_);
         TORCH_CHECK(Kc.sizes() == Vc.sizes(), "K and V must have the same shape");
-        const c10::hip::HIPGuardMasqueradingAsCUDA guard(mem_.device());
-        const hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(mem_.device().index()).stream();
-        const int st = qmha_kv_cache_append(handle_, Kc.data_ptr<float>(), Vc.data_ptr<float>(), static_cast<int>(Kc.size(1)), stream);
-        TORCH_CHECK(st == QMHA_OK, "KVCache.append(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+        const OnStream on = current_stream(mem_.device());
+        const int st = qmha_kv_cache_append(handle_, Kc.data_ptr<float>(), Vc.data_ptr<float>(), static_cast<int>(Kc.size(1)), on.stream);
+        TORCH_CHECK(st == QMHA_OK, "KVCache.append", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
     }
 
     Tensor attend(const Tensor& Q, bool causal) {
         auto Qc = rows(Q, "Q", d_model_);
         auto out = torch::empty_like(Qc);
-        const c10::hip::HIPGuardMasqueradingAsCUDA guard(mem_.device());
-        const hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(mem_.device().index()).stream();
+        const OnStream on = current_stream(mem_.device());
         const int st = qmha_attend_cached(handle_, Qc.data_ptr<float>(), out.data_ptr<float>(), static_cast<int>(Qc.size(1)),
-                                          causal ? QMHA_FLAG_CAUSAL : 0u, stream);
-        TORCH_CHECK(st == QMHA_OK, "KVCache.attend(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+                                          causal ? QMHA_FLAG_CAUSAL : 0u, on.stream);
+        TORCH_CHECK(st == QMHA_OK, "KVCache.attend", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
         return out.view(Q.sizes());
     }
 
@@ -198,31 +207,21 @@ public:
         auto Kc = rows(K, "K", kv_model_), Vc = rows(V, "V", kv_model_);
         TORCH_CHECK(Kc.sizes() == Vc.sizes(), "K and V must have the same shape");
         per_seq(pos, "pos");
-        const c10::hip::HIPGuardMasqueradingAsCUDA guard(mem_.device());
-        const hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(mem_.device().index()).stream();
+        const OnStream on = current_stream(mem_.device());
         const int st = qmha_kv_cache_append_at(handle_, Kc.data_ptr<float>(), Vc.data_ptr<float>(), static_cast<int>(Kc.size(1)),
-                                               pos.data_ptr<int32_t>(), stream);
-        TORCH_CHECK(st == QMHA_OK, "KVCache.append_at(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+                                               pos.data_ptr<int32_t>(), on.stream);
+        TORCH_CHECK(st == QMHA_OK, "KVCache.append_at", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
     }
 
     // attend with a length per sequence (qmha_attend_cached_varlen): lens is int32 [B] on the device, read by the kernel
     Tensor attend_varlen(const Tensor& Q, const Tensor& lens, bool causal, std::optional<Tensor> out_opt) {
         auto Qc = rows(Q, "Q", d_model_);
         per_seq(lens, "lens");
-        Tensor out;
-        if (out_opt) {
-            out = *out_opt;
-            TORCH_CHECK(out.numel() == Qc.numel() && out.dtype() == torch::kFloat32 && out.device() == Qc.device() &&
-                            out.is_contiguous(),
-                        "out must be a contiguous float32 tensor of Q's size on Q's device");
-        } else {
-            out = torch::empty_like(Qc);
-        }
-        const c10::hip::HIPGuardMasqueradingAsCUDA guard(mem_.device());
-        const hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(mem_.device().index()).stream();
+        Tensor out = out_for(out_opt, Qc);
+        const OnStream on = current_stream(mem_.device());
         const int st = qmha_attend_cached_varlen(handle_, Qc.data_ptr<float>(), out.data_ptr<float>(), static_cast<int>(Qc.size(1)),
-                                                 lens.data_ptr<int32_t>(), causal ? QMHA_FLAG_CAUSAL : 0u, stream);
-        TORCH_CHECK(st == QMHA_OK, "KVCache.attend_varlen(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+                                                 lens.data_ptr<int32_t>(), causal ? QMHA_FLAG_CAUSAL : 0u, on.stream);
+        TORCH_CHECK(st == QMHA_OK, "KVCache.attend_varlen", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
         return out_opt ? out : out.view(Q.sizes());
     }
 

@@ -20,6 +20,7 @@ Both take num_kv_heads (additive, default None = num_heads): grouped-query atten
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import warnings
 from typing import Optional
@@ -40,6 +41,42 @@ def _shape(Q: torch.Tensor, d_model: int):
     return 1, n // d_model
 
 
+def _fp32_inputs(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor):
+    """Q, K, V made contiguous; all on the GPU and float32, or the reference's errors (torch_ext.cpp:14-17)."""
+    if not (Q.is_cuda and K.is_cuda and V.is_cuda):
+        raise RuntimeError("Inputs must be CUDA tensors")
+    for name, t in (("Q", Q), ("K", K), ("V", V)):
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{name} must be float32")
+    return Q.contiguous(), K.contiguous(), V.contiguous()
+
+
+def _known_kernel(kernel: str) -> str:
+    """An unknown kernel name warns and routes to the default (torch_ext.cpp:32-34)."""
+    if kernel in _lib.VARIANTS:
+        return kernel
+    warnings.warn(f"Kernel selection supports {sorted(_lib.VARIANTS)}; '{kernel}' routing to default "
+                  f"'{_lib.DEFAULT_KERNEL}'")
+    return _lib.DEFAULT_KERNEL
+
+
+def _out_for(out: Optional[torch.Tensor], Qc: torch.Tensor, same: str) -> torch.Tensor:
+    """The caller's `out`, checked against Qc by shape or by size (numel), or a new tensor like Qc."""
+    if out is None:
+        return torch.empty_like(Qc)
+    fits = out.shape == Qc.shape if same == "shape" else out.numel() == Qc.numel()
+    if not fits or out.dtype != torch.float32 or out.device != Qc.device or not out.is_contiguous():
+        raise RuntimeError(f"out must be a contiguous float32 tensor of Q's {same} on Q's device")
+    return out
+
+
+@contextlib.contextmanager
+def _current_stream(device):
+    """`device` made current; yields the handle of torch's current stream there."""
+    with torch.cuda.device(device):
+        yield torch.cuda.current_stream(device).cuda_stream
+
+
 def flash_solve(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, d_model: int, num_heads: int,
                 kernel: str = _lib.DEFAULT_KERNEL, out: Optional[torch.Tensor] = None,
                 causal: bool = False) -> torch.Tensor:
@@ -48,28 +85,15 @@ def flash_solve(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, d_model: int,
     (the batch-shard path writes each rank's rows straight into the gathered result).
     causal (additive): query row r attends keys j <= r of its own sequence (fa_tc_int8_b at
     d = 32 / 64 / 128, fa_tc_v1a at d = 64 / 128; anything else raises)."""
-    if not (Q.is_cuda and K.is_cuda and V.is_cuda):
-        raise RuntimeError("Inputs must be CUDA tensors")
-    for name, t in (("Q", Q), ("K", K), ("V", V)):
-        if t.dtype != torch.float32:
-            raise RuntimeError(f"{name} must be float32")
-    Qc, Kc, Vc = Q.contiguous(), K.contiguous(), V.contiguous()
+    Qc, Kc, Vc = _fp32_inputs(Q, K, V)
     d_model, num_heads = int(d_model), int(num_heads)
     B, N = _shape(Qc, d_model)
     if Kc.shape != Qc.shape or Vc.shape != Qc.shape:
         raise RuntimeError("Q, K and V must have the same shape")
-    if kernel not in _lib.VARIANTS:
-        warnings.warn(f"Kernel selection supports {sorted(_lib.VARIANTS)}; '{kernel}' routing to default "
-                      f"'{_lib.DEFAULT_KERNEL}'")
-        kernel = _lib.DEFAULT_KERNEL
-    if out is None:
-        out = torch.empty_like(Qc)
-    elif (out.shape != Qc.shape or out.dtype != torch.float32 or out.device != Qc.device
-          or not out.is_contiguous()):
-        raise RuntimeError("out must be a contiguous float32 tensor of Q's shape on Q's device")
+    kernel = _known_kernel(kernel)
+    out = _out_for(out, Qc, "shape")
     lib = _lib.load()
-    with torch.cuda.device(Qc.device):
-        stream = torch.cuda.current_stream(Qc.device).cuda_stream
+    with _current_stream(Qc.device) as stream:
         if causal:
             st = lib.qmha_solve_opts(Qc.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), out.data_ptr(), B, N, d_model,
                                      num_heads, _lib.variant_id(kernel), _lib.QMHA_FLAG_CAUSAL, None, 0, stream)
@@ -103,12 +127,7 @@ def flash_solve_gqa(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, d_model: 
 
 
 def _solve_rect(Q, K, V, d_model, num_heads, num_kv_heads, kernel, out, causal, what):
-    if not (Q.is_cuda and K.is_cuda and V.is_cuda):
-        raise RuntimeError("Inputs must be CUDA tensors")
-    for name, t in (("Q", Q), ("K", K), ("V", V)):
-        if t.dtype != torch.float32:
-            raise RuntimeError(f"{name} must be float32")
-    Qc, Kc, Vc = Q.contiguous(), K.contiguous(), V.contiguous()
+    Qc, Kc, Vc = _fp32_inputs(Q, K, V)
     d_model, num_heads = int(d_model), int(num_heads)
     B, Nq = _shape(Qc, d_model)
     if Kc.shape != Vc.shape:
@@ -125,18 +144,10 @@ def _solve_rect(Q, K, V, d_model, num_heads, num_kv_heads, kernel, out, causal, 
     Bk, Nk = _shape(Kc, kv_model)
     if Bk != B:
         raise RuntimeError("Q and K must have the same batch count")
-    if kernel not in _lib.VARIANTS:
-        warnings.warn(f"Kernel selection supports {sorted(_lib.VARIANTS)}; '{kernel}' routing to default "
-                      f"'{_lib.DEFAULT_KERNEL}'")
-        kernel = _lib.DEFAULT_KERNEL
-    if out is None:
-        out = torch.empty_like(Qc)
-    elif (out.shape != Qc.shape or out.dtype != torch.float32 or out.device != Qc.device
-          or not out.is_contiguous()):
-        raise RuntimeError("out must be a contiguous float32 tensor of Q's shape on Q's device")
+    kernel = _known_kernel(kernel)
+    out = _out_for(out, Qc, "shape")
     lib = _lib.load()
-    with torch.cuda.device(Qc.device):
-        stream = torch.cuda.current_stream(Qc.device).cuda_stream
+    with _current_stream(Qc.device) as stream:
         flags = _lib.QMHA_FLAG_CAUSAL if causal else 0
         if num_kv_heads is None:
             st = lib.qmha_solve_rect(Qc.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), out.data_ptr(), B, Nq, Nk, d_model,
@@ -228,20 +239,14 @@ class KVCache:
         Kc, Vc = self._rows(K, "K", self.kv_model), self._rows(V, "V", self.kv_model)
         if Kc.shape != Vc.shape:
             raise RuntimeError("K and V must have the same shape")
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+        with _current_stream(self.device) as stream:
             st = _lib.load().qmha_kv_cache_append(self._handle, Kc.data_ptr(), Vc.data_ptr(), Kc.shape[1], stream)
         _lib.check(st, f"KVCache.append({self.kernel})")
 
     def attend(self, Q: torch.Tensor, causal: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         Qc = self._rows(Q, "Q")
-        if out is None:
-            out = torch.empty_like(Qc)
-        elif (out.numel() != Qc.numel() or out.dtype != torch.float32 or out.device != Qc.device
-              or not out.is_contiguous()):
-            raise RuntimeError("out must be a contiguous float32 tensor of Q's size on Q's device")
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+        out = _out_for(out, Qc, "size")
+        with _current_stream(self.device) as stream:
             st = _lib.load().qmha_attend_cached(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[1],
                                                 _lib.QMHA_FLAG_CAUSAL if causal else 0, stream)
         _lib.check(st, f"KVCache.attend({self.kernel})")
@@ -271,8 +276,7 @@ class KVCache:
         if Kc.shape != Vc.shape:
             raise RuntimeError("K and V must have the same shape")
         pos = self._per_seq(pos, "pos")
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+        with _current_stream(self.device) as stream:
             st = _lib.load().qmha_kv_cache_append_at(self._handle, Kc.data_ptr(), Vc.data_ptr(), Kc.shape[1], pos.data_ptr(),
                                                      stream)
         _lib.check(st, f"KVCache.append_at({self.kernel})")
@@ -285,13 +289,8 @@ class KVCache:
         sequence whose lens[b] is no multiple of 32, above cap, or below Nq (causal) / 32 (not) gets zeros."""
         Qc = self._rows(Q, "Q")
         lens = self._per_seq(lens, "lens")
-        if out is None:
-            out = torch.empty_like(Qc)
-        elif (out.numel() != Qc.numel() or out.dtype != torch.float32 or out.device != Qc.device
-              or not out.is_contiguous()):
-            raise RuntimeError("out must be a contiguous float32 tensor of Q's size on Q's device")
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+        out = _out_for(out, Qc, "size")
+        with _current_stream(self.device) as stream:
             st = _lib.load().qmha_attend_cached_varlen(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[1],
                                                        lens.data_ptr(), _lib.QMHA_FLAG_CAUSAL if causal else 0, stream)
         _lib.check(st, f"KVCache.attend_varlen({self.kernel})")
@@ -325,8 +324,7 @@ def quantize_int8(X: torch.Tensor, d_model: int, num_heads: int, layout: int = 0
     else:
         Xi = torch.empty((B, num_heads, N // 32, d, 32), dtype=torch.int8, device=X.device)
     sc = torch.empty((B, num_heads) if layout == 2 else (B, num_heads, N // 32), dtype=torch.float32, device=X.device)
-    with torch.cuda.device(Xc.device):
-        stream = torch.cuda.current_stream(Xc.device).cuda_stream
+    with _current_stream(Xc.device) as stream:
         st = _lib.load().qmha_quantize_int8(Xc.data_ptr(), B, N, d_model, num_heads, Xi.data_ptr(), sc.data_ptr(),
                                             layout, stream)
     _lib.check(st, "quantize_int8")

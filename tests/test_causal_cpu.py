@@ -369,18 +369,13 @@ def test_torch_bindings_take_causal_and_still_work_without_it(built):
     """Both torch bindings reach their own argument checks with and without `causal` (a binding that did
     not know the keyword would raise TypeError instead)."""
     torch = pytest.importorskip("torch")
-    import importlib.util
-    import os
-    import sysconfig
-    from quantizedmha_amd import _lib, torch_ext
+    from quantizedmha_amd import torch_ext
+    from tests.gpu_support import compiled_module
     q = torch.zeros(32, 32)
     for kw in ({}, {"causal": True}, {"causal": False}):
         with pytest.raises(RuntimeError, match="Inputs must be CUDA tensors"):
             torch_ext.flash_solve(q, q, q, 32, 1, **kw)
-    path = os.path.join(_lib.LIB_DIR, "torch_ext" + sysconfig.get_config_var("EXT_SUFFIX"))
-    spec = importlib.util.spec_from_file_location("torch_ext", path)
-    compiled = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(compiled)
+    compiled = compiled_module()
     assert "causal" in compiled.flash_solve.__doc__
     for kw in ({}, {"causal": True}, {"kernel": "fa_tc_v1a", "causal": True}):
         with pytest.raises(RuntimeError, match="Inputs must be CUDA tensors"):

@@ -13,37 +13,19 @@ unless stated, so that b > 0 and kvh > 0 occur in the K/V slice index.
 """
 import ctypes
 import functools
-import importlib.util
-import os
-import sysconfig
 
 import numpy as np
 import pytest
 
 from tests import causal_ref as cr
 from tests import rect_ref as rr
+from tests.gpu_support import (BUILT, CAUSAL, F16, GUARD, INT8, assert_bits, attend, c_solve, cache_array,  # noqa: F401
+                               compiled_module, dev, overlap_chunks, to_dev)
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-INT8, F16 = "fa_tc_int8_b", "fa_tc_v1a"
-BUILT = [(INT8, 32), (INT8, 64), (INT8, 128), (F16, 64), (F16, 128)]
 B, HKV = 2, 2
-CAUSAL = 1
-GUARD = 7.25
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from quantizedmha_amd import _lib
-    _lib.load()  # raises if the HIP library is missing: no silent fallback
-    return torch.device("cuda:0")
-
-
-def to_dev(dev, *xs):
-    return [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in xs]
 
 
 @functools.lru_cache(maxsize=None)
@@ -62,38 +44,10 @@ def expand(X, h_kv, G):
     return X.view(b, n, h_kv, d).repeat_interleave(G, dim=2).reshape(b, n, h_kv * G * d).contiguous()
 
 
-def guarded(Q, d_model):
-    buf = torch.full((Q.numel() + 32 * d_model,), GUARD, dtype=torch.float32, device=Q.device)
-    torch.cuda.synchronize()  # the fill is done before a call on another stream may write O
-    return buf
-
-
-def unguard(buf, Q):
-    torch.cuda.synchronize()
-    got = buf.cpu().numpy()
-    assert (got[Q.numel():] == GUARD).all(), "O written past its last row"
-    return got[:Q.numel()].reshape(Q.shape)
-
-
-def solve_gqa(variant, t, d, h, h_kv, flags, ws=None, ws_bytes=None, stream=None, expect=0):
-    """qmha_solve_gqa on device tensors t = [Q [B, Nq, h d], K, V [B, Nk, h_kv d]]; O (numpy) after a sync."""
-    from quantizedmha_amd import _lib
-    lib = _lib.load()
-    Q, K, V = t
-    assert K.shape[2] == h_kv * d and Q.shape[2] == h * d
-    buf = guarded(Q, h * d)
-    st = lib.qmha_solve_gqa(Q.data_ptr(), K.data_ptr(), V.data_ptr(), buf.data_ptr(), Q.shape[0], Q.shape[1], K.shape[1],
-                            h * d, h, h_kv, _lib.VARIANTS[variant], flags, ws.data_ptr() if ws is not None else None,
-                            (ws.numel() if ws_bytes is None else ws_bytes) if ws is not None else 0, stream)
-    got = unguard(buf, Q)
-    assert st == expect, (st, lib.qmha_last_error().decode())
-    return got
-
-
-def attend(cache, Q, causal=True):
-    buf = guarded(Q, cache.d_model)
-    cache.attend(Q, causal=causal, out=buf[:Q.numel()])
-    return unguard(buf, Q)
+def solve_gqa(variant, t, d, h, h_kv, flags, **kw):
+    """qmha_solve_gqa on device tensors t = [Q [B, Nq, h d], K, V [B, Nk, h_kv d]]; O (numpy) through the guard."""
+    assert t[1].shape[2] == h_kv * d and t[0].shape[2] == h * d
+    return c_solve("gqa", variant, t, h, flags, h_kv=h_kv, **kw)
 
 
 def grouped_cached(dev, variant, d, h, h_kv, t, causal, cap=None, stale=False, cls=None):
@@ -128,11 +82,6 @@ def oracle_cached(dev, variant, d, h, h_kv, t, causal, cap=None):
     cache = torch_ext.KVCache(Q.shape[0], cap, h * d, h, variant, device=dev)
     cache.append(expand(K, h_kv, h // h_kv), expand(V, h_kv, h // h_kv))
     return attend(cache, Q, causal)
-
-
-def assert_bits(label, got, want):
-    assert np.isfinite(want).all(), label
-    assert np.array_equal(got, want), (label, float(np.abs(got - want).max()), int((got != want).sum()))
 
 
 # ---- 1. shapes: every comparison bit for bit against the expanded multi-head cache -------------------------------
@@ -262,13 +211,9 @@ def test_grouped_cache_bytes_are_the_prepass_bytes_at_h_kv_heads(dev, variant, d
     torch.cuda.synchronize()
     assert cache.len == n and cache.mem.numel() == plain.mem.numel() > 1
     assert torch.equal(cache.mem, plain.mem)
-    e = -(-B * HKV * cap * d // 256) * 256
     if variant == INT8:
-        s = -(-B * HKV * (cap // 32) * 4 // 256) * 256
-        assert cache.mem.numel() == 3 * e + 2 * s
-        Ki = cache.mem[:B * HKV * cap * d].view(torch.int8).view(B * HKV, cap, d)
-        sK = cache.mem[3 * e:3 * e + B * HKV * (cap // 32) * 4].view(torch.int32).view(B * HKV, cap // 32)
-        sV = cache.mem[3 * e + s:3 * e + s + B * HKV * (cap // 32) * 4].view(torch.int32).view(B * HKV, cap // 32)
+        Ki = cache_array(cache, "Ki", torch.int8).view(B * HKV, cap, d)
+        sK, sV = cache_array(cache, "sK", torch.int32), cache_array(cache, "sV", torch.int32)
         Xi, sc = torch_ext.quantize_int8(K, HKV * d, HKV, layout=0)
         _, scv = torch_ext.quantize_int8(V, HKV * d, HKV, layout=1)
         torch.cuda.synchronize()
@@ -276,8 +221,7 @@ def test_grouped_cache_bytes_are_the_prepass_bytes_at_h_kv_heads(dev, variant, d
         assert torch.equal(sK[:, :n // 32], sc.view(B * HKV, n // 32).view(torch.int32))
         assert torch.equal(sV[:, :n // 32], scv.view(B * HKV, n // 32).view(torch.int32))
     else:
-        assert cache.mem.numel() == 2 * (-(-2 * B * HKV * cap * d // 256) * 256)
-        Kh = cache.mem[:2 * B * HKV * cap * d].view(torch.int16).view(B * HKV, cap, d)
+        Kh = cache_array(cache, "Kh", torch.int16).view(B * HKV, cap, d)
         want = K.cpu().reshape(B, n, HKV, d).permute(0, 2, 1, 3).half().contiguous().view(B * HKV, n, d)
         assert torch.equal(Kh[:, :n].cpu(), want.view(torch.int16))
 
@@ -288,16 +232,9 @@ def test_grouped_cache_bytes_are_the_prepass_bytes_at_h_kv_heads(dev, variant, d
                                                  (INT8, 96, 96, CAUSAL), (F16, 96, 96, CAUSAL),
                                                  (INT8, 96, 160, CAUSAL), (F16, 96, 160, 0)])
 def test_equal_head_counts_are_qmha_solve_rect(dev, variant, Nq, Nk, flags):
-    from quantizedmha_amd import _lib
-    lib = _lib.load()
     d, h = 64, 2
     t = to_dev(dev, *rr.inputs(Nq, Nk, h * d, B, "normal", 850))
-    out = torch.empty_like(t[0])
-    st = lib.qmha_solve_rect(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), out.data_ptr(), B, Nq, Nk, h * d, h,
-                             _lib.VARIANTS[variant], flags, None, 0, None)
-    torch.cuda.synchronize()
-    assert st == 0, lib.qmha_last_error().decode()
-    assert_bits("h_kv == h", solve_gqa(variant, t, d, h, h, flags), out.cpu().numpy())
+    assert_bits("h_kv == h", solve_gqa(variant, t, d, h, h, flags), c_solve("rect", variant, t, h, flags))
 
 
 @pytest.mark.parametrize("variant,d", BUILT)
@@ -329,17 +266,12 @@ def test_equal_head_counts_keep_the_cache_unbuilt_for_other_variants(dev, varian
 # ---- 5. host layer ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("variant", [INT8, F16])
 def test_overlap_chunks_are_bit_identical(dev, variant):
-    from quantizedmha_amd import _lib
-    lib = _lib.load()
     G, d = 2, 64
     h = HKV * G
     t = to_dev(dev, *host_inputs(96, 160, d, h, HKV, 3, "normal", 870))
     want = solve_gqa(variant, t, d, h, HKV, CAUSAL)
-    prev = lib.qmha_set_overlap_chunks(2)
-    try:
+    with overlap_chunks(2):
         got = solve_gqa(variant, t, d, h, HKV, CAUSAL)
-    finally:
-        lib.qmha_set_overlap_chunks(prev)
     assert_bits("two chunks of B = 3", got, want)
 
 
@@ -406,11 +338,8 @@ def test_unsupported_grouped_call_touches_nothing(dev, variant):
 # ---- 6. both bindings -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("variant,d", BUILT)
 def test_bindings_give_the_same_bytes(dev, variant, d):
-    from quantizedmha_amd import _lib, torch_ext
-    spec = importlib.util.spec_from_file_location(
-        "torch_ext", os.path.join(_lib.LIB_DIR, "torch_ext" + sysconfig.get_config_var("EXT_SUFFIX")))
-    compiled = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(compiled)
+    from quantizedmha_amd import torch_ext
+    compiled = compiled_module()
     G = 2
     h = HKV * G
     t = to_dev(dev, *host_inputs(96, 160, d, h, HKV, B, "normal", 900))

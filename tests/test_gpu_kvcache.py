@@ -18,53 +18,26 @@ Shapes: at most 512 rows, B = 2 (the chunk's and the cache's batch strides diffe
 """
 import ctypes
 import functools
-import importlib.util
-import os
-import sysconfig
 import threading
 
 import numpy as np
 import pytest
 
 from tests import causal_ref as cr
-from tests import parity_log
+from tests import gpu_support as gs
 from tests import rect_ref as rr
+from tests.gpu_support import (BUILT, CAUSAL, F16, INT8, assert_bits, assert_f16, assert_int8, attend, c_solve,  # noqa: F401
+                               cache_array, compiled_module, dev, to_dev)
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-INT8, F16 = "fa_tc_int8_b", "fa_tc_v1a"
-BUILT = [(INT8, 32), (INT8, 64), (INT8, 128), (F16, 64), (F16, 128)]
 B, H = 2, 2
-GUARD = 7.25
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from quantizedmha_amd import _lib
-    _lib.load()  # raises if the HIP library is missing: no silent fallback
-    return torch.device("cuda:0")
-
-
-def to_dev(dev, *xs):
-    return [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in xs]
+TAG = "+kv"  # this file's mark on its parity_log records
 
 
 def new_cache(dev, variant, d, cap, batch=B):
-    from quantizedmha_amd import torch_ext
-    return torch_ext.KVCache(batch, cap, H * d, H, variant, device=dev)
-
-
-def attend(cache, Q, causal=True):
-    """cache.attend into the head of a guarded buffer; O (numpy) after a sync."""
-    buf = torch.full((Q.numel() + 32 * cache.d_model,), GUARD, dtype=torch.float32, device=Q.device)
-    cache.attend(Q, causal=causal, out=buf[:Q.numel()])
-    torch.cuda.synchronize()
-    got = buf.cpu().numpy()
-    assert (got[Q.numel():] == GUARD).all(), "O written past its last row"
-    return got[:Q.numel()].reshape(Q.shape)
+    return gs.new_cache(dev, variant, batch, cap, d, H)
 
 
 def rect(variant, d, Q, K, V, causal=True):
@@ -75,29 +48,6 @@ def rect(variant, d, Q, K, V, causal=True):
     return out.cpu().numpy()
 
 
-def assert_bits(label, got, want):
-    same = np.array_equal(got, want)
-    assert same, (label, float(np.abs(got - want).max()), int((got != want).sum()))
-
-
-def assert_int8(label, got, ref, unit):
-    assert np.isfinite(got).all()
-    err = np.abs(got.astype(np.float64) - ref)
-    units = cr.flip_units(err, unit)
-    parity_log.record(f"{label} [max error beyond 5e-5, in one-flip units]", INT8 + "+kv", units,
-                      float((err > 5e-5).mean()), 2.0)
-    print(f"{label}: max|gpu - ref| = {err.max():.3e}, worst (err - 5e-5) / u_r = {units:.3f} (bound 2)")
-    assert (err <= 2.0 * unit + 5e-5).all(), (label, float(err.max()), units)
-
-
-def assert_f16(label, got, contract, tol):
-    assert np.isfinite(got).all()
-    err = float(np.abs(got.astype(np.float64) - contract).max())
-    parity_log.record(f"{label} (vs lazy contract)", F16 + "+kv", err, float((np.abs(got - contract) > 5e-5).mean()), tol)
-    print(f"{label}: max|gpu - lazy contract| = {err:.3e} (bound {tol:.2e})")
-    assert err <= tol, (label, err, tol)
-
-
 def assert_square_causal(label, variant, d, got, Q, K, V, oracle_rect=None):
     """len == Nq with the mask: the variant's bound against tests/causal_ref.py on host arrays Q, K, V [B, N, H d];
     oracle_rect (the SquareCausal instance's result) only for the record."""
@@ -105,9 +55,9 @@ def assert_square_causal(label, variant, d, got, Q, K, V, oracle_rect=None):
     N = Q.shape[1]
     if variant == INT8:
         ref, unit, _ = cr.fa_int8(oracle, Q, K, V, H * d, H, causal=True, base2=True)
-        assert_int8(label, got, ref, cr.per_element(unit, d))
+        assert_int8(label, got, ref, cr.per_element(unit, d), TAG)
     else:
-        assert_f16(label, got, cr.fa_fp16_lazy(None, Q, K, V, H * d, H, causal=True)[0], cr.fp16_lazy_tol(N))
+        assert_f16(label, got, cr.fa_fp16_lazy(None, Q, K, V, H * d, H, causal=True)[0], cr.fp16_lazy_tol(N), TAG)
     if oracle_rect is not None:
         same = np.array_equal(got, oracle_rect)
         print(f"{label}: Rect with diag_off = 0 {'is' if same else 'is NOT'} bit-identical to the SquareCausal instance"
@@ -117,15 +67,9 @@ def assert_square_causal(label, variant, d, got, Q, K, V, oracle_rect=None):
 # ---- 1. the cache's bytes ------------------------------------------------------------------------------------
 def carve(cache, d):
     """Views of the cache tensor by the workspace carve at N = cap: (K rows [B*H, cap, d], K scales or None)."""
-    e = -(-B * H * cache.cap * d // 256) * 256
     if cache.kernel == INT8:
-        s = -(-B * H * (cache.cap // 32) * 4 // 256) * 256
-        Ki = cache.mem[:B * H * cache.cap * d].view(torch.int8).view(B * H, cache.cap, d)
-        sK = cache.mem[3 * e:3 * e + B * H * (cache.cap // 32) * 4].view(torch.float32).view(B * H, cache.cap // 32)
-        assert cache.mem.numel() == 3 * e + 2 * s
-        return Ki, sK
-    assert cache.mem.numel() == 2 * (-(-2 * B * H * cache.cap * d // 256) * 256)
-    return cache.mem[:2 * B * H * cache.cap * d].view(torch.float16).view(B * H, cache.cap, d), None
+        return cache_array(cache, "Ki", torch.int8).view(B * H, cache.cap, d), cache_array(cache, "sK", torch.float32)
+    return cache_array(cache, "Kh", torch.float16).view(B * H, cache.cap, d), None
 
 
 @pytest.mark.parametrize("variant,d", BUILT)
@@ -195,22 +139,16 @@ def test_chunked_prefill(dev, variant, d, dist):
             assert_bits(f"chunk {c + 1}", got, want)
         parts.append(got)
     got = np.concatenate(parts, axis=1)
-    out = torch.empty_like(t[0])
-    from quantizedmha_amd import _lib
-    st = _lib.load().qmha_solve_opts(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), out.data_ptr(), B, N, H * d, H,
-                                     _lib.VARIANTS[variant], 1, None, 0, None)
-    torch.cuda.synchronize()
-    assert st == 0
-    square = out.cpu().numpy()
+    square = c_solve("opts", variant, t, H, CAUSAL)
     label = f"kv prefill {variant} d{d} {dist}"
     if variant == INT8:
         ref, unit, _ = cr.fa_int8(oracle, Q, K, V, H * d, H, causal=True, base2=True)
         pe = cr.per_element(unit, d)
-        assert_int8(label, got, ref, pe)
-        assert_int8(label + " (vs the square GPU call)", got, square.astype(np.float64), pe)
+        assert_int8(label, got, ref, pe, TAG)
+        assert_int8(label + " (vs the square GPU call)", got, square.astype(np.float64), pe, TAG)
     else:
-        assert_f16(label, got, cr.fa_fp16_lazy(None, Q, K, V, H * d, H, causal=True)[0], cr.fp16_lazy_tol(N))
-        assert_f16(label + " (vs the square GPU call)", got, square, cr.fp16_lazy_tol(N))
+        assert_f16(label, got, cr.fa_fp16_lazy(None, Q, K, V, H * d, H, causal=True)[0], cr.fp16_lazy_tol(N), TAG)
+        assert_f16(label + " (vs the square GPU call)", got, square, cr.fp16_lazy_tol(N), TAG)
         assert oracle.verify_results(got, cr.attention_f64(Q, K, V, H * d, H, causal=True).astype(np.float32), 1e-3, 1e-3) == -1
 
 
@@ -359,11 +297,7 @@ def test_two_threads_with_their_own_caches(dev, variant, d):
 # ---- 10. both bindings --------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("variant,d", BUILT)
 def test_compiled_binding_gives_the_same_bytes(dev, variant, d):
-    from quantizedmha_amd import _lib
-    spec = importlib.util.spec_from_file_location(
-        "torch_ext", os.path.join(_lib.LIB_DIR, "torch_ext" + sysconfig.get_config_var("EXT_SUFFIX")))
-    compiled = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(compiled)
+    compiled = compiled_module()
     t = to_dev(dev, *prefill_inputs(d, "normal"))
     want = chunked_prefill(dev, variant, d, t)
     got = chunked_prefill(dev, variant, d, t, cls=compiled.KVCache)

@@ -24,6 +24,7 @@ import pytest
 
 from tests import parity_log
 from tests.golden_io import load_case
+from tests.gpu_support import dev, overlap_chunks  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -56,15 +57,6 @@ def int8_tol(N):
     if N < 2048:
         return 5e-4
     return 1e-4
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from quantizedmha_amd import _lib
-    _lib.load()  # raises if the HIP library is missing: no silent fallback
-    return torch.device("cuda:0")
 
 
 def oracle_for(oracle_mod, variant):
@@ -922,18 +914,14 @@ def test_solve_ws_caller_scratch_and_graph_capture(dev, variant):
 def test_overlap_chunks_bit_identical(dev, variant):
     """Batch-chunked pre-pass/main overlap (qmha_set_overlap_chunks) must not change a bit, and
     two calls in a row on the same workspace must agree (catches LDS-DMA / stream races)."""
-    from quantizedmha_amd import _lib, torch_ext
-    lib = _lib.load()
+    from quantizedmha_amd import torch_ext
     B, N, H, d = 8, 1024, 16, 64
     g = torch.Generator(device=dev).manual_seed(3)
     Q, K, V = (torch.randn(B, N, H * d, device=dev, generator=g) * 0.5 for _ in range(3))
-    prev = lib.qmha_set_overlap_chunks(1)
-    try:
+    with overlap_chunks(1) as lib:
         ref = torch_ext.flash_solve(Q, K, V, H * d, H, kernel=variant)
         for chunks in (2, 4):
             lib.qmha_set_overlap_chunks(chunks)
             for _ in range(2):
                 out = torch_ext.flash_solve(Q, K, V, H * d, H, kernel=variant)
                 assert torch.equal(out, ref), (variant, chunks)
-    finally:
-        lib.qmha_set_overlap_chunks(prev)

@@ -13,20 +13,11 @@ import pytest
 from oracle import oracle
 from tests import parity_log
 from tests import pstage_ref as ps
+from tests.gpu_support import INT8, dev, to_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-INT8 = "fa_tc_int8_b"
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from quantizedmha_amd import _lib
-    _lib.load()  # raises if the HIP library is missing: no silent fallback
-    return torch.device("cuda:0")
 
 
 @pytest.mark.parametrize("case", ps.CASES, ids=lambda c: c.label)
@@ -35,7 +26,7 @@ def test_pstage(dev, case):
     Q, K, V = case.build()
     d_model, h = case.d_model, case.h
     assert ps.kind_of(Q.shape[1], K.shape[1], d_model // h, case.causal) == case.kind, "the case no longer reaches its kernel"
-    t = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (Q, K, V)]
+    t = to_dev(dev, Q, K, V)
     O, dump = torch_ext.debug_fa_int8_pstage(t[0], t[1], t[2], d_model, h, causal=case.causal)
     shipped = torch_ext.flash_solve_rect(t[0], t[1], t[2], d_model, h, INT8, causal=case.causal)
     torch.cuda.synchronize()

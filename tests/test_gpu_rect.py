@@ -17,9 +17,6 @@ The observed maxima are printed in pytest's terminal summary (tests/parity_log.p
 """
 import ctypes
 import functools
-import importlib.util
-import os
-import sysconfig
 
 import numpy as np
 import pytest
@@ -27,82 +24,25 @@ import pytest
 from tests import causal_ref as cr
 from tests import parity_log
 from tests import rect_ref as rr
+from tests.gpu_support import (CAUSAL, F16, GUARD, INT8, assert_f16, assert_int8, c_solve, compiled_module, dev,  # noqa: F401
+                               overlap_chunks, to_dev)
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-INT8, F16 = "fa_tc_int8_b", "fa_tc_v1a"
-CAUSAL = 1
-GUARD = 7.25
+TAG = "+r"  # this file's mark on its parity_log records
 _ids = lambda v: rr.case_id(v) if isinstance(v, tuple) and len(v) == 6 else str(v)  # noqa: E731
 
 
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from quantizedmha_amd import _lib
-    _lib.load()  # raises if the HIP library is missing: no silent fallback
-    return torch.device("cuda:0")
-
-
-def to_dev(dev, *xs):
-    return [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in xs]
-
-
-def solve_rect(variant, t, d_model, h, flags, ws=None, ws_bytes=None, stream=None, expect=0):
-    """qmha_solve_rect on device tensors t = [Q [B, Nq, d_model], K, V [B, Nk, d_model]]; returns O (numpy) after a
-    sync.  O is the head of a buffer whose tail (32 rows) holds a sentinel that must survive the call."""
-    from quantizedmha_amd import _lib
-    lib = _lib.load()
-    Q, K, V = t
-    B, Nq, Nk = Q.shape[0], Q.shape[1], K.shape[1]
-    buf = torch.full((Q.numel() + 32 * d_model,), GUARD, dtype=torch.float32, device=Q.device)
-    torch.cuda.synchronize()  # the fill is done before a call on another stream may write O
-    st = lib.qmha_solve_rect(Q.data_ptr(), K.data_ptr(), V.data_ptr(), buf.data_ptr(), B, Nq, Nk, d_model, h,
-                             _lib.VARIANTS[variant], flags, ws.data_ptr() if ws is not None else None,
-                             (ws.numel() if ws_bytes is None else ws_bytes) if ws is not None else 0, stream)
-    torch.cuda.synchronize()
-    assert st == expect, (st, lib.qmha_last_error().decode())
-    got = buf.cpu().numpy()
-    assert (got[Q.numel():] == GUARD).all(), "O written past its last row"
-    return got[:Q.numel()].reshape(Q.shape)
+def solve_rect(variant, t, d_model, h, flags, **kw):
+    """qmha_solve_rect on device tensors t = [Q [B, Nq, d_model], K, V [B, Nk, d_model]]; O (numpy) through the guard."""
+    assert t[0].shape[-1] == d_model
+    return c_solve("rect", variant, t, h, flags, **kw)
 
 
 def solve_opts(variant, t, d_model, h, flags):
-    from quantizedmha_amd import _lib
-    lib = _lib.load()
-    out = torch.empty_like(t[0])
-    st = lib.qmha_solve_opts(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), out.data_ptr(), t[0].shape[0],
-                             t[0].shape[1], d_model, h, _lib.VARIANTS[variant], flags, None, 0, None)
-    torch.cuda.synchronize()
-    assert st == 0, (st, lib.qmha_last_error().decode())
-    return out.cpu().numpy()
-
-
-def assert_int8(label, got, ref, unit):
-    assert np.isfinite(got).all()
-    err = np.abs(got.astype(np.float64) - ref)
-    units = cr.flip_units(err, unit)
-    parity_log.record(f"{label} [max error beyond 5e-5, in one-flip units]", INT8 + "+r", units,
-                      float((err > 5e-5).mean()), 2.0)
-    print(f"{label}: max|gpu - ref| = {err.max():.3e}, worst (err - 5e-5) / u_r = {units:.3f} (bound 2)")
-    assert (err <= 2.0 * unit + 5e-5).all(), (label, float(err.max()), units)
-
-
-def assert_f16(label, got, contract, tol, exact=None):
-    """Within tol of the kernel's contract; with `exact`, also within max(1e-3, 1e-3 |ref|) of float64."""
-    from oracle import oracle
-    assert np.isfinite(got).all()
-    err = float(np.abs(got.astype(np.float64) - contract).max())
-    parity_log.record(f"{label} (vs lazy contract)", F16 + "+r", err, float((np.abs(got - contract) > 5e-5).mean()), tol)
-    print(f"{label}: max|gpu - lazy contract| = {err:.3e} (bound {tol:.2e})")
-    assert err <= tol, (label, err, tol)
-    if exact is not None:
-        far = float(np.abs(got - exact).max())
-        parity_log.record(f"{label} (vs float64)", F16 + "+r", far, float((np.abs(got - exact) > 5e-5).mean()), 1e-3)
-        print(f"{label}: max|gpu - float64| = {far:.3e} (bound max(1e-3, 1e-3 |ref|))")
-        assert oracle.verify_results(got, exact.astype(np.float32), 1e-3, 1e-3) == -1, (label, far)
+    assert t[0].shape[-1] == d_model
+    return c_solve("opts", variant, t, h, flags)
 
 
 # ---- parity ------------------------------------------------------------------------------------------
@@ -130,7 +70,7 @@ def test_int8_rect_vs_base2_restatement(dev, case, dist):
     Nq, Nk, d_model, h, B, causal = case
     Q, K, V, ref, unit = int8_reference(case, dist)
     got = solve_rect(INT8, to_dev(dev, Q, K, V), d_model, h, CAUSAL if causal else 0)
-    assert_int8(f"{rr.case_id(case)} {dist}", got, ref, unit)
+    assert_int8(f"{rr.case_id(case)} {dist}", got, ref, unit, TAG)
 
 
 @pytest.mark.parametrize("dist", rr.DISTS)
@@ -139,7 +79,7 @@ def test_fp16_rect_vs_lazy_contract_and_float64(dev, case, dist):
     Nq, Nk, d_model, h, B, causal = case
     Q, K, V, contract, exact = f16_reference(case, dist)
     got = solve_rect(F16, to_dev(dev, Q, K, V), d_model, h, CAUSAL if causal else 0)
-    assert_f16(f"{rr.case_id(case)} {dist}", got, contract, cr.fp16_lazy_tol(Nk), exact)
+    assert_f16(f"{rr.case_id(case)} {dist}", got, contract, cr.fp16_lazy_tol(Nk), TAG, exact)
 
 
 # ---- the mask: every row's strongest key is its first masked one ----------------------------------------------
@@ -150,7 +90,7 @@ def test_int8_shifted_superdiagonal(dev, shape):
     Q, K, V = rr.superdiag_inputs(Nq, Nk, d_model, B)
     ref, unit = rr.fa_int8(oracle, Q, K, V, d_model, h, causal=True, base2=True)
     got = solve_rect(INT8, to_dev(dev, Q, K, V), d_model, h, CAUSAL)
-    assert_int8(f"superdiag {shape}", got, ref, cr.per_element(unit, d_model // h))
+    assert_int8(f"superdiag {shape}", got, ref, cr.per_element(unit, d_model // h), TAG)
 
 
 @pytest.mark.parametrize("shape", [s for s in rr.SUPERDIAG if s[2] // s[3] in (64, 128)], ids=str)
@@ -161,7 +101,7 @@ def test_fp16_shifted_superdiagonal(dev, shape):
     Q, K, V = rr.superdiag_inputs(Nq, Nk, d_model, B)
     ref = rr.fa_fp16_lazy(None, Q, K, V, d_model, h, causal=True)
     got = solve_rect(F16, to_dev(dev, Q, K, V), d_model, h, CAUSAL)
-    assert_f16(f"superdiag {shape}", got, ref, 2.0 ** -10 * float(np.abs(V).max()))
+    assert_f16(f"superdiag {shape}", got, ref, 2.0 ** -10 * float(np.abs(V).max()), TAG)
 
 
 # ---- chunked prefill -------------------------------------------------------------------------------------
@@ -188,12 +128,12 @@ def test_chunked_prefill_reproduces_full_prefill(dev, variant, d):
     if variant == INT8:
         ref, unit, _ = cr.fa_int8(oracle, Q, K, V, d_model, h, causal=True, base2=True)
         pe = cr.per_element(unit, d)
-        assert_int8(f"chunked prefill d{d}", got, ref, pe)
-        assert_int8(f"chunked prefill d{d} (vs the square GPU call)", got, square.astype(np.float64), pe)
+        assert_int8(f"chunked prefill d{d}", got, ref, pe, TAG)
+        assert_int8(f"chunked prefill d{d} (vs the square GPU call)", got, square.astype(np.float64), pe, TAG)
     else:
         ref = cr.fa_fp16_lazy(None, Q, K, V, d_model, h, causal=True)[0]
-        assert_f16(f"chunked prefill d{d}", got, ref, cr.fp16_lazy_tol(N), cr.attention_f64(Q, K, V, d_model, h, causal=True))
-        assert_f16(f"chunked prefill d{d} (vs the square GPU call)", got, square, cr.fp16_lazy_tol(N))
+        assert_f16(f"chunked prefill d{d}", got, ref, cr.fp16_lazy_tol(N), TAG, cr.attention_f64(Q, K, V, d_model, h, causal=True))
+        assert_f16(f"chunked prefill d{d} (vs the square GPU call)", got, square, cr.fp16_lazy_tol(N), TAG)
 
 
 # ---- routing -----------------------------------------------------------------------------------------
@@ -263,13 +203,10 @@ def test_unsupported_rect_touches_nothing(dev, variant, d_model, h, flags):
 def test_bindings_route_to_qmha_solve_rect(dev):
     """torch_ext.flash_solve_rect (the Python mirror, with out=, and the compiled module) gives the C-ABI's result
     bit for bit; mismatched K / V and batch counts raise; flash_solve still wants one shape."""
-    from quantizedmha_amd import _lib, torch_ext
+    from quantizedmha_amd import torch_ext
     Nq, Nk, d_model, h, B = 96, 160, 128, 2, 2
     t = to_dev(dev, *rr.inputs(Nq, Nk, d_model, B, "normal", 550))
-    spec = importlib.util.spec_from_file_location(
-        "torch_ext", os.path.join(_lib.LIB_DIR, "torch_ext" + sysconfig.get_config_var("EXT_SUFFIX")))
-    compiled = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(compiled)
+    compiled = compiled_module()
     for variant in (INT8, F16):
         for causal in (False, True):
             want = solve_rect(variant, t, d_model, h, CAUSAL if causal else 0)
@@ -330,7 +267,7 @@ def test_int8_hard_shapes_vs_base2_restatement(dev, shape, d):
     flags = CAUSAL if shape.causal else 0
     Q, K, V, ref, unit = hard_int8_reference(shape, d)
     got = solve_rect(INT8, to_dev(dev, Q, K, V), c.h * d, c.h, flags)
-    assert_int8(f"hard {rr.hard_id(shape)} d{d}", got, ref, unit)
+    assert_int8(f"hard {rr.hard_id(shape)} d{d}", got, ref, unit, TAG)
     if shape.name == "underflow":
         assert not ref.any() and not got.any()
         assert not solve_rect(INT8, to_dev(dev, *rr.zero_v_hard_inputs(d, shape.Nq, shape.Nk)), c.h * d, c.h, flags).any()
@@ -345,13 +282,13 @@ def test_fp16_hard_shapes_vs_lazy_contract(dev, shape, d):
     Q, K, V, ref = hard_f16_reference(shape, d)
     got = solve_rect(F16, to_dev(dev, Q, K, V), c.h * d, c.h, flags)
     label = f"hard {rr.hard_id(shape)} d{d}"
-    assert_f16(label, got, ref, hard_flip_tol(V))
+    assert_f16(label, got, ref, hard_flip_tol(V), TAG)
     if shape.name == "underflow":  # float64 has no m0 = 0 guard
         assert not ref.any() and not got.any()
         assert not solve_rect(F16, to_dev(dev, *rr.zero_v_hard_inputs(d, shape.Nq, shape.Nk)), c.h * d, c.h, flags).any()
     else:
         far = float(np.abs(got - rr.attention_f64(Q, K, V, c.h * d, c.h, shape.causal)).max())
-        parity_log.record(f"{label} (vs float64, recorded only)", F16 + "+r", far, 0.0, float("inf"))
+        parity_log.record(f"{label} (vs float64, recorded only)", F16 + TAG, far, 0.0, float("inf"))
         print(f"{label}: max|gpu - float64| = {far:.2e} (recorded only)")
 
 
@@ -372,9 +309,9 @@ def test_hard_last_chunk_equals_the_square_causal_call(dev, variant, shape, d):
           f" (max difference {np.abs(got - square).max():.3e})")
     assert np.isfinite(square).all()
     if variant == INT8:
-        assert_int8(label, got, square.astype(np.float64), hard_int8_reference(shape, d)[4])
+        assert_int8(label, got, square.astype(np.float64), hard_int8_reference(shape, d)[4], TAG)
     else:
-        assert_f16(label, got, square, hard_flip_tol(V))
+        assert_f16(label, got, square, hard_flip_tol(V), TAG)
 
 
 @pytest.mark.parametrize("variant,d", [(INT8, 32), (INT8, 64), (INT8, 128), (F16, 64), (F16, 128)])
@@ -410,18 +347,13 @@ def test_overlap_chunks_with_rectangular_slabs_are_bit_identical(dev, variant, N
     """qmha_set_overlap_chunks(2 and 3) with B = 3 and Nq != Nk: every chunk boundary has b0 > 0, chunk c reads Q and
     writes O at b0 Nq d_model and reads K, V and its workspace slice at b0 Nk ..., and the two slabs differ in both
     directions over the two shapes.  Each run equals the unchunked call bit for bit, with the guard behind O intact."""
-    from quantizedmha_amd import _lib
-    lib = _lib.load()
     B, d_model, h = 3, 128, 2
     flags = CAUSAL if causal else 0
     t = to_dev(dev, *rr.inputs(Nq, Nk, d_model, B, "normal", 560 + Nq))
-    prev = lib.qmha_set_overlap_chunks(1)
-    try:
+    with overlap_chunks(1) as lib:
         want = solve_rect(variant, t, d_model, h, flags)
         assert len({want[b].tobytes() for b in range(B)}) == B  # three different sequences: a mixed-up slab shows
         for chunks in (2, 3):
             lib.qmha_set_overlap_chunks(chunks)
             for _ in range(2):
                 assert np.array_equal(solve_rect(variant, t, d_model, h, flags), want), (variant, chunks)
-    finally:
-        lib.qmha_set_overlap_chunks(prev)

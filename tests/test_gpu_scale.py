@@ -26,52 +26,19 @@ from tests import causal_ref as cr
 from tests import parity_log
 from tests import rect_ref as rr
 from tests import test_scale_cpu as sc
+from tests.gpu_support import (BUILT, F16, INT8, Guarded, assert_bits, assert_f16, assert_int8, assert_zeros, attend,
+                               dev, i32, new_cache, seq_slices, to_dev)  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-INT8, F16, BUILT = sc.INT8, sc.F16, sc.BUILT
-GUARD = 7.25
+TAG = "+s"  # this file's mark on its parity_log records
 _vd = lambda v: "-".join(str(x) for x in v) if isinstance(v, tuple) else str(v)  # noqa: E731
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from quantizedmha_amd import _lib
-    _lib.load()  # raises if the HIP library is missing: no silent fallback
-    return torch.device("cuda:0")
-
-
-def to_dev(dev, *xs):
-    return [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in xs]
-
-
-def i32(dev, xs):
-    return torch.tensor(xs, dtype=torch.int32, device=dev)
 
 
 def cols(X, k, w):
     """Columns [k w, (k + 1) w) of a device tensor, contiguous."""
     return X[..., k * w:(k + 1) * w].contiguous()
-
-
-class Guarded:
-    """O as the head of a buffer whose 32-row tail holds a sentinel; `out` is what a call writes into."""
-
-    def __init__(self, Q):
-        self.n, self.shape = Q.numel(), tuple(Q.shape)
-        self.buf = torch.full((self.n + 32 * Q.shape[-1],), GUARD, dtype=torch.float32, device=Q.device)
-        self.out = self.buf[:self.n].view(self.shape)
-
-    def device_result(self):
-        torch.cuda.synchronize()
-        assert bool((self.buf[self.n:] == GUARD).all()), "O written past its last row"
-        return self.out
-
-    def result(self):
-        return self.device_result().cpu().numpy()
 
 
 def solve(variant, t, h, causal, h_kv=None, device_result=False):
@@ -86,59 +53,6 @@ def solve(variant, t, h, causal, h_kv=None, device_result=False):
     else:
         torch_ext.flash_solve_rect(Q, K, V, Q.shape[-1], h, variant, out=g.out, causal=causal)
     return g.device_result() if device_result else g.result()
-
-
-def attend(cache, Q, causal=True, lens=None):
-    g = Guarded(Q)
-    if lens is None:
-        cache.attend(Q, causal=causal, out=g.buf[:g.n])
-    else:
-        cache.attend_varlen(Q, lens, causal=causal, out=g.buf[:g.n])
-    return g.result()
-
-
-def new_cache(dev, variant, B, cap, d, h, h_kv=None):
-    from quantizedmha_amd import torch_ext
-    if h_kv is None:
-        return torch_ext.KVCache(B, cap, h * d, h, variant, str(dev))
-    return torch_ext.GroupedKVCache(B, cap, h * d, h, h_kv, variant, str(dev))
-
-
-def assert_bits(label, got, want):
-    assert np.isfinite(want).all(), label
-    assert np.array_equal(got, want), (label, float(np.abs(got - want).max()), int((got != want).sum()))
-
-
-def assert_zeros(label, got):
-    assert (got == 0.0).all() and not np.signbit(got).any(), label
-
-
-def assert_int8(label, got, ref, unit):
-    """Every element within 2 u_r + 5e-5 of the base-2 restatement (tests/test_gpu_rect.py)."""
-    assert np.isfinite(got).all()
-    err = np.abs(got.astype(np.float64) - ref)
-    units = cr.flip_units(err, unit)
-    frac = float((err > 5e-5).mean())
-    parity_log.record(f"{label} [max error beyond 5e-5, in one-flip units]", INT8 + "+s", units, frac, 2.0)
-    print(f"{label}: max|gpu - ref| = {err.max():.3e}, worst (err - 5e-5) / u_r = {units:.3f} (bound 2), "
-          f"frac > 5e-5 = {frac:.2e}, largest u_r = {float(unit.max()):.2e}")
-    assert (err <= 2.0 * unit + 5e-5).all(), (label, float(err.max()), units)
-
-
-def assert_f16(label, got, contract, tol, exact=None, got_all=None):
-    """Within tol of the lazy contract; with `exact`, got_all (default got) within max(1e-3, 1e-3 |ref|) of float64."""
-    from oracle import oracle
-    assert np.isfinite(got).all()
-    err = float(np.abs(got.astype(np.float64) - contract).max())
-    parity_log.record(f"{label} (vs lazy contract)", F16 + "+s", err, float((np.abs(got - contract) > 5e-5).mean()), tol)
-    print(f"{label}: max|gpu - lazy contract| = {err:.3e} (bound {tol:.2e})")
-    assert err <= tol, (label, err, tol)
-    if exact is not None:
-        got_all = got if got_all is None else got_all
-        far = float(np.abs(got_all - exact).max())
-        parity_log.record(f"{label} (vs float64)", F16 + "+s", far, float((np.abs(got_all - exact) > 5e-5).mean()), 1e-3)
-        print(f"{label}: max|gpu - float64| = {far:.3e} (bound max(1e-3, 1e-3 |ref|))")
-        assert oracle.verify_results(np.ascontiguousarray(got_all), np.ascontiguousarray(exact, dtype=np.float32), 1e-3, 1e-3) == -1, (label, far)
 
 
 # ==== 1. the launch map on ragged, wide grids ============================================================================
@@ -220,21 +134,6 @@ def test_wide_varlen_call_equals_uniform_narrow_caches(dev, variant, d, causal):
             assert_bits(f"varlen slice ({b}, {kvh}) at {L}", got[b:b + 1, :, kvh * G * d:(kvh + 1) * G * d], want)
 
 
-def seq_slices(cache, B, d, b):
-    """Byte ranges of sequence b in the tensor of a cache of B sequences (tests/test_gpu_varlen.py's seq_slices)."""
-    hk, cap = cache.num_kv_heads, cache.cap
-    al = lambda x: -(-x // 256) * 256  # noqa: E731
-    if cache.kernel == INT8:
-        e, s = al(B * hk * cap * d), al(B * hk * (cap // 32) * 4)
-        arrays = [(0, cap * d), (e, 2 * cap * d), (3 * e, (cap // 32) * 4), (3 * e + s, (cap // 32) * 4)]  # Ki Vh sK sV
-        assert cache.mem.numel() == 3 * e + 2 * s
-    else:
-        e = al(2 * B * hk * cap * d)
-        arrays = [(0, 2 * cap * d), (e, 2 * cap * d)]  # Kh Vt
-        assert cache.mem.numel() == 2 * e
-    return [slice(off + b * hk * per, off + (b + 1) * hk * per) for off, per in arrays]
-
-
 @pytest.mark.parametrize("variant,d", BUILT)
 def test_wide_append_at_places_what_narrow_appends_place(dev, variant, d):
     """append_at(n = 64, pos = [0, 64, -32, 128, 48, 160, 224]) on the B7 grouped cache, prefilled with a byte pattern:
@@ -255,14 +154,14 @@ def test_wide_append_at_places_what_narrow_appends_place(dev, variant, d):
         u = new_cache(dev, variant, 1, w.Nk, d, w.h, w.h_kv)
         if p:
             u.append(K[b:b + 1, :p], V[b:b + 1, :p])  # only to move len to pos[b]
-        mine, theirs = seq_slices(a, w.B, d, b), seq_slices(u, 1, d, 0)
+        mine, theirs = seq_slices(a, b), seq_slices(u, 0)
         for sa, su in zip(mine, theirs):
             u.mem[su] = pattern[sa]
         u.append(new_k[b:b + 1], new_v[b:b + 1])
         for sa, su in zip(mine, theirs):
             want[sa] = u.mem[su]
     torch.cuda.synchronize()
-    changed = [bool((want[s] != pattern[s]).any()) for b in range(w.B) for s in seq_slices(a, w.B, d, b)[:1]]
+    changed = [bool((want[s] != pattern[s]).any()) for b in range(w.B) for s in seq_slices(a, b)[:1]]
     assert changed == [True, True, False, True, False, True, True]
     assert torch.equal(a.mem, want)
 
@@ -289,10 +188,10 @@ def test_wide_causal_calls_vs_the_restatements(dev, variant, name):
         mine = np.ascontiguousarray(got[b:b + 1, :, k * 64:(k + 1) * 64])
         label = f"wide {name} B{w.B} h{w.h} slice ({b}, {k})"
         if variant == INT8:
-            assert_int8(label, mine, *wide_reference(name, variant, b, k))
+            assert_int8(label, mine, *wide_reference(name, variant, b, k), TAG)
         else:
             contract, exact = wide_reference(name, variant, b, k)
-            assert_f16(label, mine, contract, cr.fp16_lazy_tol(w.Nk), exact)
+            assert_f16(label, mine, contract, cr.fp16_lazy_tol(w.Nk), TAG, exact)
 
 
 # ==== 2. long key loops: 128 tiles =========================================================================================
@@ -325,7 +224,7 @@ def test_long_int8_vs_base2_restatement(dev, d, dist, call):
     _, Nq, causal = call
     ref, unit, exact = sc.long_int8_reference(d, dist, causal)
     got = long_base(dev, INT8, d, dist, call)
-    assert_int8(f"Nk4096 {call[0]} d{d} {dist}", got, ref[:, -Nq:], unit[:, -Nq:])
+    assert_int8(f"Nk4096 {call[0]} d{d} {dist}", got, ref[:, -Nq:], unit[:, -Nq:], TAG)
     far = float(np.abs(got - exact[:, -Nq:]).max())
     print(f"Nk4096 {call[0]} d{d} {dist}: max|gpu - float64| = {far:.3e} (bound 5e-3)")
     assert far <= 5e-3, far
@@ -341,7 +240,7 @@ def test_long_fp16_vs_lazy_contract_and_float64(dev, d, dist, call):
     contract, exact = sc.long_f16_reference(d, dist, causal)
     got = long_base(dev, F16, d, dist, call)
     assert_f16(f"Nk4096 {call[0]} d{d} {dist}", np.ascontiguousarray(got[..., :d]), contract[:, -Nq:],
-               cr.fp16_lazy_tol(sc.LONG_NK), exact[:, -Nq:], got_all=got)
+               cr.fp16_lazy_tol(sc.LONG_NK), TAG, exact[:, -Nq:], got_all=got)
 
 
 @pytest.mark.parametrize("call", sc.LONG_CALLS, ids=lambda c: c[0])
@@ -439,7 +338,7 @@ def test_more_workgroups_than_the_device_holds(dev, variant):
                 exact = rows_f64(q, kk, v, r0, r0 + 32)
                 far = float(np.abs(mine[0, r0:r0 + 32] - exact).max())
                 print(f"{variant} B16 h16 N2048 slice ({b}, {k}) rows {r0}..{r0 + 31}: max|gpu - float64| = {far:.3e}")
-                parity_log.record(f"B16 h16 N2048 slice ({b}, {k}) rows {r0}.. (vs float64)", variant + "+s", far, 0.0,
+                parity_log.record(f"B16 h16 N2048 slice ({b}, {k}) rows {r0}.. (vs float64)", variant + TAG, far, 0.0,
                                   5e-3 if variant == INT8 else 1e-3)
                 if variant == INT8:
                     assert far <= 5e-3, far
@@ -468,7 +367,6 @@ def test_result_does_not_depend_on_the_previous_launch(dev, variant, d, Nq, Nk, 
     Q, K, V = to_dev(dev, *rr.inputs(Nq, Nk, h * d, B, "normal", 8800 + Nq + d))
     runs = [(K, V), (poisoned(K, 1.0), poisoned(V, -1.0)), (K, V)]
     outs = [Guarded(Q) for _ in runs]
-    torch.cuda.synchronize()
     for g, (k, v) in zip(outs, runs):
         torch_ext.flash_solve_rect(Q, k, v, h * d, h, variant, out=g.out, causal=causal)
     first, _, again = [g.result() for g in outs]
@@ -489,7 +387,6 @@ def test_varlen_result_does_not_depend_on_the_previous_launch(dev, variant, d, N
     dirty.append(poisoned(K, 1.0), poisoned(V, -1.0))
     lens = i32(dev, [Nk, Nk])
     outs = [Guarded(Q) for _ in range(3)]
-    torch.cuda.synchronize()
     for g, cache in zip(outs, (clean, dirty, clean)):
         cache.attend_varlen(Q, lens, causal=causal, out=g.buf[:g.n])
     first, _, again = [g.result() for g in outs]

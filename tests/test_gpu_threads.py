@@ -17,20 +17,13 @@ import threading
 
 import pytest
 
+from tests.gpu_support import dev, overlap_chunks  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from quantizedmha_amd import _lib
-    _lib.load()  # raises if the HIP library is missing: no silent fallback
-    return torch.device("cuda:0")
 
 
 THREADS, CALLS = 4, 25
@@ -201,15 +194,12 @@ def _references(dev, lib, calls, stream_of):
     """The same calls made one at a time with overlap chunks = 1."""
     ws = torch.empty(max(max(_ws_bytes(lib, c) for c in calls.values()), 256), dtype=torch.uint8, device=dev)
     torch.cuda.synchronize(dev)  # the inputs were made on the default stream
-    prev = lib.qmha_set_overlap_chunks(1)
-    try:
-        refs = {}
+    refs = {}
+    with overlap_chunks(1):
         for key, call in calls.items():
             refs[key] = torch.full_like(call[4], float("nan"))
             _enqueue(lib, call, refs[key], stream_of(key), ws)
             torch.cuda.synchronize(dev)
-    finally:
-        lib.qmha_set_overlap_chunks(prev)
     return refs
 
 
@@ -277,13 +267,10 @@ def test_concurrent_callers_with_overlap_chunks(dev):
                 _enqueue(lib, calls[t, j], calls[t, j][7], sptr, wss[t])
         return fn
 
-    prev = lib.qmha_set_overlap_chunks(2)
-    try:
+    with overlap_chunks(2):
         errors = _run_threads(dev, [worker(t) for t in range(nthreads)])
         shared.synchronize()
         torch.cuda.synchronize(dev)
-    finally:
-        lib.qmha_set_overlap_chunks(prev)
     assert not errors, errors
     _assert_bit_identical(calls, refs)
 
@@ -316,12 +303,9 @@ def test_release_beside_callers_with_overlap_chunks(dev):
             lib.qmha_release_workspaces()
             time.sleep(0.02)
 
-    prev = lib.qmha_set_overlap_chunks(2)
-    try:
+    with overlap_chunks(2):
         errors = _run_threads(dev, [caller(t) for t in range(ncallers)] + [releaser])
         torch.cuda.synchronize(dev)
-    finally:
-        lib.qmha_set_overlap_chunks(prev)
     assert not errors, errors
     _assert_bit_identical(calls, refs)
 
@@ -345,11 +329,8 @@ def test_stream_per_thread_slots(dev):
                 _enqueue(lib, calls[t, j], calls[t, j][7], per_thread)
         return fn
 
-    prev = lib.qmha_set_overlap_chunks(2)
-    try:
+    with overlap_chunks(2):
         errors = _run_threads(dev, [worker(t) for t in range(nthreads)])
         torch.cuda.synchronize(dev)  # device-wide: the per-thread streams are not reachable from here
-    finally:
-        lib.qmha_set_overlap_chunks(prev)
     assert not errors, errors
     _assert_bit_identical(calls, refs)

@@ -15,67 +15,28 @@ Shapes: B = 3, cap = 224 (Gk = 7: the last stage is partial), h = 2 (grouped: h 
 (variant, d).  A wrong per-sequence offset, tile count or slice stride moves whole tiles and fails these comparisons.
 """
 import functools
-import importlib.util
-import os
-import sysconfig
 
 import numpy as np
 import pytest
 
+from tests import gpu_support as gs
 from tests import rect_ref as rr
+from tests.gpu_support import (BUILT, F16, GUARD, INT8, assert_bits, assert_zeros, attend, compiled_module, dev, i32,  # noqa: F401
+                               seq_slices, to_dev)
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-INT8, F16 = "fa_tc_int8_b", "fa_tc_v1a"
-BUILT = [(INT8, 32), (INT8, 64), (INT8, 128), (F16, 64), (F16, 128)]
 B, CAP, NQ = 3, 224, 96
 HEADS = [(2, None), (4, 2), (4, 1)]  # (h, h_kv); None: a multi-head KVCache
-GUARD = 7.25
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from quantizedmha_amd import _lib
-    _lib.load()  # raises if the HIP library is missing: no silent fallback
-    return torch.device("cuda:0")
 
 
 def new_cache(dev, variant, d, heads=HEADS[0], cap=CAP, mod=None):
-    from quantizedmha_amd import torch_ext
-    mod = mod or torch_ext
-    h, h_kv = heads
-    if h_kv is None:
-        return mod.KVCache(B, cap, h * d, h, variant, str(dev))
-    return mod.GroupedKVCache(B, cap, h * d, h, h_kv, variant, str(dev))
-
-
-def i32(dev, xs):
-    return torch.tensor(xs, dtype=torch.int32, device=dev)
-
-
-def guarded(call, Q):
-    """call(out) with out the head of a guarded buffer; O (numpy, shaped like Q) after a sync."""
-    buf = torch.full((Q.numel() + 32 * Q.shape[-1],), GUARD, dtype=torch.float32, device=Q.device)
-    call(buf[:Q.numel()])
-    torch.cuda.synchronize()
-    got = buf.cpu().numpy()
-    assert (got[Q.numel():] == GUARD).all(), "O written past its last row"
-    return got[:Q.numel()].reshape(Q.shape)
+    return gs.new_cache(dev, variant, B, cap, d, *heads, mod=mod)
 
 
 def attend_varlen(cache, Q, lens, causal=True):
-    return guarded(lambda out: cache.attend_varlen(Q, lens, causal=causal, out=out), Q)
-
-
-def attend(cache, Q, causal=True):
-    return guarded(lambda out: cache.attend(Q, causal=causal, out=out), Q)
-
-
-def assert_bits(label, got, want):
-    assert np.array_equal(got, want), (label, float(np.abs(got - want).max()), int((got != want).sum()))
+    return attend(cache, Q, causal, lens)
 
 
 # ---- inputs and the uniform path's results, computed once per (variant, d, heads, dist) and left unchanged ----------
@@ -102,7 +63,7 @@ _DEV = {}
 def dev_inputs(dev, d, heads, dist):
     key = (d, heads, dist)
     if key not in _DEV:
-        _DEV[key] = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in host_inputs(d, heads, dist)]
+        _DEV[key] = to_dev(dev, *host_inputs(d, heads, dist))
     return _DEV[key]
 
 
@@ -130,21 +91,6 @@ def filled(dev, variant, d, heads, dist):
 
 
 # ---- 1. placement ---------------------------------------------------------------------------------------------------
-def seq_slices(cache, d, b):
-    """Byte ranges of sequence b in the cache tensor: its h_kv slices of every array of the carve at N = cap."""
-    hk, cap = cache.num_kv_heads, cache.cap
-    al = lambda x: -(-x // 256) * 256  # noqa: E731
-    if cache.kernel == INT8:
-        e, s = al(B * hk * cap * d), al(B * hk * (cap // 32) * 4)
-        arrays = [(0, cap * d), (e, 2 * cap * d), (3 * e, (cap // 32) * 4), (3 * e + s, (cap // 32) * 4)]  # Ki Vh sK sV
-        assert cache.mem.numel() == 3 * e + 2 * s
-    else:
-        e = al(2 * B * hk * cap * d)
-        arrays = [(0, 2 * cap * d), (e, 2 * cap * d)]  # Kh Vt
-        assert cache.mem.numel() == 2 * e
-    return [slice(off + b * hk * per, off + (b + 1) * hk * per) for off, per in arrays]
-
-
 def pattern_of(cache):
     return (torch.arange(cache.mem.numel(), device=cache.mem.device) % 251).to(torch.uint8)
 
@@ -179,7 +125,7 @@ def test_placement(dev, variant, d, heads):
             u.append(K[:, :pb], V[:, :pb])  # only to move len to pos[b]
         u.mem.copy_(pattern)
         u.append(new_k, new_v)
-        for s in seq_slices(u, d, b):
+        for s in seq_slices(u, b):
             want[s] = u.mem[s]
     torch.cuda.synchronize()
     assert not torch.equal(want, pattern)
@@ -262,7 +208,7 @@ def test_invalid_and_empty_sequences(dev, variant, d, heads):
             if L == 224:
                 assert_bits(f"lens {lens}: the valid sequence {b}", got[b], uniform(dev, variant, d, heads, "normal", L, NQ)[b])
             else:
-                assert (got[b] == 0.0).all() and not np.signbit(got[b]).any(), (lens, b)
+                assert_zeros(f"lens {lens}: sequence {b}", got[b])
 
 
 # ---- 7. graph replay with advancing lengths ---------------------------------------------------------------------------
@@ -326,14 +272,9 @@ def test_graph_replay_follows_the_lengths(dev, variant, d):
 @pytest.mark.parametrize("heads", [HEADS[0], HEADS[1]], ids=["mha", "gqa2"])
 @pytest.mark.parametrize("variant,d", [(INT8, 64), (F16, 64)])
 def test_compiled_binding_gives_the_same_bytes(dev, variant, d, heads):
-    from quantizedmha_amd import _lib
-    spec = importlib.util.spec_from_file_location(
-        "torch_ext", os.path.join(_lib.LIB_DIR, "torch_ext" + sysconfig.get_config_var("EXT_SUFFIX")))
-    compiled = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(compiled)
     Q, K, V = dev_inputs(dev, d, heads, "normal")
     pos, lens = i32(dev, [0, 64, -32]), i32(dev, [96, 160, 0])
-    caches = [new_cache(dev, variant, d, heads), new_cache(dev, variant, d, heads, mod=compiled)]
+    caches = [new_cache(dev, variant, d, heads), new_cache(dev, variant, d, heads, mod=compiled_module())]
     outs = []
     for c in caches:
         c.append(K[:, :64], V[:, :64])

@@ -12,11 +12,13 @@ import subprocess
 
 import pytest
 
+from tests import gpu_support as gs
+from tests.gpu_support import CAUSAL
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CAUSAL = 1
-V1A, INT8 = 1, 2
+V1A, INT8 = 1, 2  # the C-ABI's variant ids, not gpu_support's names
 MEM = 0x10000  # 256-byte aligned, never dereferenced: checks run first
-BUILT = [(INT8, 32), (INT8, 64), (INT8, 128), (V1A, 64), (V1A, 128)]
+BUILT = [({gs.INT8: INT8, gs.F16: V1A}[v], d) for v, d in gs.BUILT]
 
 
 @pytest.fixture(scope="module")

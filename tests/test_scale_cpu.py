@@ -22,10 +22,9 @@ import pytest
 
 from tests import causal_ref as cr
 from tests import rect_ref as rr
+from tests.gpu_support import F16, INT8
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INT8, F16 = "fa_tc_int8_b", "fa_tc_v1a"
-BUILT = [(INT8, 32), (INT8, 64), (INT8, 128), (F16, 64), (F16, 128)]
 GROUP, WAVES, STAGE, XCDS = 32, 4, 2, 8  # QMHA_GROUP, kWaves, kSG, the XCDs xcd_remap deals over
 
 

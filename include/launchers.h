@@ -215,6 +215,53 @@ int qmha_kv_cache_append_at(qmha_kv_cache_t *c, const float *K, const float *V, 
 int qmha_attend_cached_varlen(qmha_kv_cache_t *c, const float *Q, float *O, int Nq, const int32_t *lens, unsigned flags,
                               void *stream);
 
+/*
+ * Token-granular lengths -- append and attend at any length: a prompt of 1000 tokens, a decode step of one.  Device
+ * lengths only, as above: pos and lens are DEVICE int32[B] arrays read by the kernels, the host `len` is neither read
+ * nor changed, multi-head and grouped caches alike.  Absolute row positions of a sequence keep their 32-row groups, and
+ * a ragged call is DEFINED as the call above on zero-padded operands, which it matches bit for bit:
+ *
+ *   keys / values  a cache that holds L rows of a sequence holds the bytes append_at writes for those rows zero-padded
+ *                  to L' = ceil32(L).  For int8 the open (last, partial) group's scale comes from the rows present --
+ *                  zero rows do not move an absmax -- and the group is quantised again from its raw rows every time
+ *                  rows are added; it is final once it is full.
+ *   queries        Nq rows attend a sequence of L rows, causal and bottom-right aligned: row r sees keys j <= r + L - Nq.
+ *                  With s = (L - Nq) mod 32 and Nq' = ceil32(s + Nq) the result is rows [s, s + Nq) of attend_varlen's
+ *                  causal call on a zero [Nq', d_model] block that holds Q at rows [s, s + Nq), against L' rows (L' - Nq'
+ *                  is a multiple of 32, and the diagonal mask hides exactly the zero key rows >= L from every real row).
+ *                  A single-token decode step: s = (L - 1) mod 32, Nq' = 32.  int8: the zero query rows have p = 1 on the
+ *                  keys they see and enter the P tile's absmax, so a tile shared with pad rows is quantised with
+ *                  sP = 1/127, the per-tensor mode's static scale (DESIGN.md 17 has the measured accuracy).
+ *
+ *   tail_bytes     the bytes of caller-owned device memory for the raw fp32 rows of each sequence's open group: int8, K and
+ *                  V of 32 rows x h_kv * d per sequence; fp16, 0 (a row converts on its own).
+ *   attach_tail    attaches that memory (256-byte aligned, >= tail_bytes, otherwise QMHA_ERR_INVALID) to the cache.  A
+ *                  buffer of its own: the cache memory and qmha_kv_cache_bytes stay as they are.  The library never
+ *                  allocates or frees it.  fp16: nothing to attach, QMHA_OK.
+ *   append_tokens  K, V: [B, n, h_kv * d], any 1 <= n <= cap (host check).  On the device, pos[b] is valid when
+ *                  pos[b] >= 0 and pos[b] + n <= cap: the 32-row groups that rows [pos[b], pos[b] + n) touch get the bytes
+ *                  of the contract above, no other group is written, and the tail is updated.  An invalid pos[b]: nothing
+ *                  is written, the tail included.  An int8 cache without a tail: QMHA_ERR_INVALID.
+ *                  An append that starts inside a group (pos[b] % 32 != 0) RELIES on the tail holding that group's earlier
+ *                  rows (int8), and on the group's rows behind them being zero (fp16), from the append_tokens calls that
+ *                  wrote them: build a partial group with append_tokens from its first row on.  append / append_at at a
+ *                  multiple of 32 start a fresh group and need no tail; so does append_tokens there.
+ *   attend_tokens  Q, O: [B, Nq, d_model], any 1 <= Nq <= cap; flags must be QMHA_FLAG_CAUSAL (the kernels have no mask but
+ *                  the diagonal: unmasked ragged attention is not built), anything else QMHA_ERR_INVALID; host checks.
+ *                  On the device, L = lens[b] is valid when Nq <= L <= cap: the contract above.  Rows at and beyond
+ *                  ceil32(L) are never read; Q and O are touched at their Nq rows only.  An invalid L: the sequence's Nq
+ *                  rows of O are positive zeros and none of its K/V is read.
+ *
+ * Null pos / lens: QMHA_ERR_INVALID.  Every host check runs before any HIP call; no allocation, no synchronisation (both
+ * calls can be captured in a hipGraph); the cache's mutex is held across the enqueue; qmha_profile records are those of
+ * append / attend.
+ */
+size_t qmha_kv_cache_tail_bytes(const qmha_kv_cache_t *c);
+int qmha_kv_cache_attach_tail(qmha_kv_cache_t *c, void *mem, size_t bytes);
+int qmha_kv_cache_append_tokens(qmha_kv_cache_t *c, const float *K, const float *V, int n, const int32_t *pos, void *stream);
+int qmha_attend_cached_tokens(qmha_kv_cache_t *c, const float *Q, float *O, int Nq, const int32_t *lens, unsigned flags,
+                              void *stream);
+
 /* Blocking convenience used by the per-variant `solve` shims and the JAX raw-pointer
  * binding (extensions/jax/jax_ext.cpp:12-28): batch 1, synchronises the device stream. */
 int qmha_solve_variant(const float *Q, const float *K, const float *V, float *O, int N, int d_model, int h,

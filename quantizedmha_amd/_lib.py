@@ -38,6 +38,11 @@ SIGNATURES = {
     # per-sequence rows / lengths: device int32[B] pointers
     "qmha_kv_cache_append_at": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "qmha_attend_cached_varlen": (_i, [_vp, _vp, _vp, _i, _vp, ctypes.c_uint, _vp]),
+    # token-granular lengths: the int8 cache's tail of raw rows, and append / attend at any length
+    "qmha_kv_cache_tail_bytes": (_sz, [_vp]),
+    "qmha_kv_cache_attach_tail": (_i, [_vp, _vp, _sz]),
+    "qmha_kv_cache_append_tokens": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "qmha_attend_cached_tokens": (_i, [_vp, _vp, _vp, _i, _vp, ctypes.c_uint, _vp]),
     "qmha_solve_ws": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "qmha_solve_variant": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     "qmha_quantize_int8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),

@@ -526,6 +526,8 @@ struct qmha_kv_cache {
     int B, cap, d_model, h, D, variant;
     int h_kv;  // K/V heads: the memory is the variant's carve at H = h_kv (== h unless created by _create_gqa)
     int len;   // valid rows of every head slice
+    // the raw rows of each sequence's open group (qmha_kv_cache_attach_tail; int8 only), caller-owned like `mem`
+    void* tail = nullptr;
 };
 
 namespace {
@@ -738,6 +740,60 @@ int qmha_attend_cached_varlen(qmha_kv_cache_t* c, const float* Q, float* O, int 
                                           ", cap = " + std::to_string(c->cap) + ")");
     return cache_enqueue(c, &ProfRec::main, stream, "kv_cache attend_varlen launch", kNoLenCheck, [&](const auto& w, int) {
         return qmha::launch_fa_masked(w, Q, O, {c->B, Nq, c->cap, c->h, c->h_kv, c->D, c->d_model, causal, -1, lens},
+                                      (hipStream_t)stream);
+    });
+}
+
+// ---- token-granular lengths: device lengths only, the host `len` is neither read nor changed ----
+size_t qmha_kv_cache_tail_bytes(const qmha_kv_cache_t* c) {
+    if (!c || c->variant != QMHA_FA_TC_INT8_B) return 0;  // fp16: a row converts on its own
+    return qmha::kv_tail_bytes(c->B, c->h_kv, c->D);
+}
+
+int qmha_kv_cache_attach_tail(qmha_kv_cache_t* c, void* mem, size_t bytes) {
+    if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+    const size_t need = qmha_kv_cache_tail_bytes(c);
+    if (need == 0) return QMHA_OK;  // nothing to hold
+    if (!mem) return fail(QMHA_ERR_INVALID, "attach_tail: null tail memory");
+    if (reinterpret_cast<uintptr_t>(mem) % 256 != 0) return fail(QMHA_ERR_INVALID, "attach_tail: tail memory must be 256-byte aligned");
+    if (bytes < need)
+        return fail(QMHA_ERR_INVALID, "attach_tail: tail memory too small: " + std::to_string(bytes) +
+                                          " bytes, qmha_kv_cache_tail_bytes is " + std::to_string(need));
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->tail = mem;
+    return QMHA_OK;
+}
+
+int qmha_kv_cache_append_tokens(qmha_kv_cache_t* c, const float* K, const float* V, int n, const int32_t* pos, void* stream) {
+    if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+    if (!K || !V) return fail(QMHA_ERR_INVALID, "null tensor pointer");
+    if (!pos) return fail(QMHA_ERR_INVALID, "append_tokens: null pos (a device int32[B])");
+    if (n < 1 || n > c->cap)
+        return fail(QMHA_ERR_INVALID, "append_tokens: n = " + std::to_string(n) + " rows, needs 1 <= n <= cap = " + std::to_string(c->cap));
+    return cache_enqueue(
+        c, &ProfRec::pre, stream, "kv_cache append_tokens launch",
+        [&](int) {  // under the mutex: attach_tail writes `tail` under it
+            if (c->variant == QMHA_FA_TC_INT8_B && !c->tail)
+                return fail(QMHA_ERR_INVALID, "append_tokens: an int8 cache needs its tail (qmha_kv_cache_attach_tail)");
+            return (int)QMHA_OK;
+        },
+        [&](const auto& w, int) {
+            return qmha::launch_kv_tokens(K, V, w, static_cast<float*>(c->tail), c->B, n, c->cap, pos, c->h_kv, c->D, c->h_kv * c->D,
+                                          (hipStream_t)stream);
+        });
+}
+
+int qmha_attend_cached_tokens(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, const int32_t* lens, unsigned flags,
+                              void* stream) {
+    if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+    if (!Q || !O) return fail(QMHA_ERR_INVALID, "null tensor pointer");
+    if (!lens) return fail(QMHA_ERR_INVALID, "attend_tokens: null lens (a device int32[B])");
+    if (flags != QMHA_FLAG_CAUSAL)
+        return fail(QMHA_ERR_INVALID, "attend_tokens: flags must be QMHA_FLAG_CAUSAL (the kernels have no mask but the diagonal)");
+    if (Nq < 1 || Nq > c->cap)
+        return fail(QMHA_ERR_INVALID, "attend_tokens: Nq = " + std::to_string(Nq) + " rows, needs 1 <= Nq <= cap = " + std::to_string(c->cap));
+    return cache_enqueue(c, &ProfRec::main, stream, "kv_cache attend_tokens launch", kNoLenCheck, [&](const auto& w, int) {
+        return qmha::launch_fa_masked(w, Q, O, {c->B, Nq, c->cap, c->h, c->h_kv, c->D, c->d_model, true, -1, lens, true},
                                       (hipStream_t)stream);
     });
 }

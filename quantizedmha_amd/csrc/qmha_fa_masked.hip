@@ -5,7 +5,8 @@
 // geometry type (SquareCausal, Rect, Grouped: below) supplies what differs.  And the varlen kernels of a K/V cache
 // whose sequences differ in length: the same body -- it is the text of
 // qmha_fa_masked_{int8,f16}.inc, included by every __global__ here -- over a geometry (Varlen) formed from a length
-// the kernel reads from device memory.
+// the kernel reads from device memory.  And the ragged kernels: that body once more, over
+// lengths and query counts that are no multiple of 32 (Ragged).
 //
 // Square causal: query row r attends keys j <= r of its own sequence (Nq = Nk = N).  Both kernels keep the
 // geometry of the non-causal main kernels, so they consume the unchanged pre-pass outputs (qmha_prepass.hip):
@@ -150,6 +151,44 @@ struct Varlen : Grouped {
     __device__ int last(int g) const { return min(g + diag_off, GL - 1); }
 };
 
+// Token-granular lengths: Nq query rows (any 1 <= Nq <= cap) attend the first L = lens[b] rows of a
+// causal cache, bottom-right aligned, for any Nq <= L <= cap.  Absolute row positions keep their 32-row groups: with
+// s = (L - Nq) mod 32 the call is Varlen's causal one on a zero [Nq', d_model] block, Nq' = ceil32(s + Nq), that holds Q
+// at rows [s, s + Nq), against L' = ceil32(L) rows -- L' - Nq' = L - Nq - s is a multiple of 32, so the diagonal tile
+// and its in-tile mask are the existing ones, and the mask hides exactly the key rows >= L from every real query row.
+// Nq stays the caller's row count (the batch stride of Q and O); the padded block exists in registers only: a lane
+// whose memory row 32 qg + col - s lies outside [0, Nq) holds zeros without a load and stores nothing (row_real,
+// row_shift below).  The grid cannot follow s: the host sizes it for ceil((Nq + 31) / 32) query groups per head
+// (max_units), of which a sequence has Ga = Nq' / 32 active -- the body's U --, and a workgroup with no active unit
+// leaves before its first barrier.
+struct Ragged : Varlen {
+    int s;   // rows of padding ahead of Q in its first group
+    int Ga;  // active query groups of this sequence
+    Ragged(int nq, int cap, int g) : Varlen(nq, cap, g, true), s(0), Ga(0) {}
+    __host__ __device__ int max_units() const { return G * ((Nq + 2 * QMHA_GROUP - 2) / QMHA_GROUP); }
+    __device__ bool valid(int L) const { return L >= Nq && L <= Nk; }
+    __device__ Ragged of(int L) const {
+        Ragged v = *this;
+        v.s = (L - Nq) & (QMHA_GROUP - 1);
+        const int Lp = (L + QMHA_GROUP - 1) & ~(QMHA_GROUP - 1), Nqp = (v.s + Nq + QMHA_GROUP - 1) & ~(QMHA_GROUP - 1);
+        v.GL = Lp / QMHA_GROUP;  // <= Gk: cap is a multiple of 32
+        v.Ga = Nqp / QMHA_GROUP;
+        v.diag_off = (Lp - Nqp) / QMHA_GROUP;
+        return v;
+    }
+    __host__ __device__ int units() const { return G * Ga; }
+};
+// A lane's row of Q / O in memory is its row of the (padded) block less row_shift; row_real: that row exists.
+// Constants for every geometry but Ragged, so the other instances carry no trace of them.
+template <class Geo>
+constexpr bool kRaggedGeo = std::is_same<std::remove_cv_t<Geo>, Ragged>::value;
+template <class Geo>
+__device__ __forceinline__ constexpr int row_shift(const Geo&) { return 0; }
+template <class Geo>
+__device__ __forceinline__ constexpr bool row_real(const Geo&, int) { return true; }
+__device__ __forceinline__ int row_shift(const Ragged& g) { return g.s; }
+__device__ __forceinline__ bool row_real(const Ragged& g, int row) { return (unsigned)(row - g.s) < (unsigned)g.Nq; }
+
 // A geometry that also carries the buffers of a dumping instance (int8 kernel; QkDump and PDump in
 // qmha_kernels.hpp): the debug hook's twin of a shipped instance, whose own arguments stay as they are.
 template <class Geo>
@@ -279,6 +318,51 @@ __global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_f16_varle
 }
 
 // ---------------------------------------------------------------------------------------
+// Token-granular lengths (Ragged, above): the varlen prologue over the same bodies.  An invalid length has the
+// sequence's Nq real rows of O zeroed by the first workgroup of each of its K/V slices -- the G heads' columns of
+// those rows --, and nothing read.
+// ---------------------------------------------------------------------------------------
+template <int D>
+__device__ __forceinline__ void zero_real_rows(float* __restrict__ O, const Ragged& geo, int bh, int H, int d_model) {
+    const int W4 = geo.G * D / 4;  // 16-byte pieces of a row's G heads
+    float* o = O + (size_t)(bh / H) * geo.Nq * d_model + (size_t)(bh % H) * geo.G * D;
+    for (int i = threadIdx.x; i < geo.Nq * W4; i += kWaves * 64) *reinterpret_cast<v4f*>(o + (size_t)(i / W4) * d_model + 4 * (i % W4)) = v4f{};
+}
+
+// (d = 32 asks for the seven waves per SIMD its varlen sibling has: under the shared bound of four the row shift
+// took it from 68 to 75 VGPRs, one occupancy step; with seven it needs 70 and no scratch.)
+template <int D, class Geo = Ragged>
+__global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : D > 32 ? 4 : 7) void qmha_fa_int8_ragged_kernel(
+    const float* __restrict__ Qf, const int8_t* __restrict__ Ki, const _Float16* __restrict__ Vh,
+    const float* __restrict__ sK, const float* __restrict__ sV, float* __restrict__ O, Geo any,
+    const int32_t* __restrict__ lens, int H, int d_model, int nqb, float c_log2) {
+    int bh_, pi_;
+    masked_wg(nqb, bh_, pi_);  // the body forms the same pair again
+    const int L = lens[bh_ / H];
+    if (!any.valid(L)) {  // workgroup-uniform, before the body's first barrier
+        if (pi_ == 0) zero_real_rows<D>(O, any, bh_, H, d_model);
+        return;
+    }
+    const Geo geo = any.of(L);
+#include "qmha_fa_masked_int8.inc"
+}
+
+template <int D, class Geo = Ragged>
+__global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_f16_ragged_kernel(
+    const float* __restrict__ Qf, const _Float16* __restrict__ Kh, const _Float16* __restrict__ Vt,
+    float* __restrict__ O, Geo any, const int32_t* __restrict__ lens, int H, int d_model, int nqb, float c_log2) {
+    int bh_, qb_;
+    masked_wg_single(nqb, bh_, qb_);  // the body forms the same pair again
+    const int L = lens[bh_ / H];
+    if (!any.valid(L)) {
+        if (qb_ == 0) zero_real_rows<D>(O, any, bh_, H, d_model);
+        return;
+    }
+    const Geo geo = any.of(L);
+#include "qmha_fa_masked_f16.inc"
+}
+
+// ---------------------------------------------------------------------------------------
 // host launchers (MaskedCall in qmha_kernels.hpp): per-sequence lengths take the varlen kernels, grouped calls
 // (Hkv < H) the Grouped instances, square causal calls of their own the SquareCausal ones, everything else Rect
 // ---------------------------------------------------------------------------------------
@@ -292,12 +376,22 @@ static bool cached_shape_ok(int Nq, int cap, int len, bool causal) {
     return causal ? Nq <= len && len <= cap : len == cap;
 }
 static int masked_nqb(int units) { return (units + kWaves - 1) / kWaves; }  // unit blocks per K/V slice
+// the units a grid is sized for: the geometry's own, or, where they follow a length on the device (Ragged), their most
+template <class Geo>
+static int grid_units(const Geo& geo) {
+    if constexpr (std::is_same<Geo, Ragged>::value) return geo.max_units();
+    else return geo.units();
+}
 
 // The geometry of a call, checked, handed to `launch`.  The varlen grid follows Nq, B, Hkv and G only; what lens
 // holds is the kernels' business.
 template <class Launch>
 static hipError_t masked_geo(const MaskedCall& c, Launch&& launch) {
     if (c.B < 1 || c.Hkv < 1 || c.Hkv > c.H || c.H % c.Hkv != 0 || c.d_model != c.H * c.D) return hipErrorInvalidValue;
+    if (c.ragged) {  // token-granular lengths: any 1 <= Nq <= cap, causal, lengths on the device
+        if (!c.lens || !c.causal || c.Nq < 1 || c.Nk < QMHA_GROUP || c.Nk % QMHA_GROUP != 0 || c.Nq > c.Nk) return hipErrorInvalidValue;
+        return launch(Ragged(c.Nq, c.Nk, c.H / c.Hkv));
+    }
     const bool cached = !c.lens && c.len >= 0;
     if (!(cached ? cached_shape_ok(c.Nq, c.Nk, c.len, c.causal) : masked_shape_ok(c.Nq, c.Nk, c.causal))) return hipErrorInvalidValue;
     const int G = c.H / c.Hkv;
@@ -310,10 +404,13 @@ static hipError_t masked_geo(const MaskedCall& c, Launch&& launch) {
 // Launch the instance of `geo` over the call's B * Hkv K/V slices (the kernels' H argument); stream: the dump's is null
 template <class Geo>
 static hipError_t fa_masked_launch(const Int8Workspace& w, const float* Qf, float* O, const MaskedCall& c, hipStream_t stream, Geo geo) {
-    const int nqb = masked_nqb(geo.units());
+    const int nqb = masked_nqb(grid_units(geo));
     const dim3 grid(c.B * c.Hkv * masked_pairs(nqb)), block(kWaves * 64);
     return int8_masked_d(c.D, [&](auto d) {
-        if constexpr (std::is_same<Geo, Varlen>::value)
+        if constexpr (std::is_same<Geo, Ragged>::value)
+            hipLaunchKernelGGL((qmha_fa_int8_ragged_kernel<decltype(d)::value>), grid, block, 0, stream, Qf, w.Ki, w.Vh, w.sK, w.sV, O,
+                               geo, c.lens, c.Hkv, c.d_model, nqb, softmax_scale_log2(c.D));
+        else if constexpr (std::is_same<Geo, Varlen>::value)
             hipLaunchKernelGGL((qmha_fa_int8_varlen_kernel<decltype(d)::value>), grid, block, 0, stream, Qf, w.Ki, w.Vh, w.sK, w.sV, O,
                                geo, c.lens, c.Hkv, c.d_model, nqb, softmax_scale_log2(c.D));
         else
@@ -325,10 +422,13 @@ static hipError_t fa_masked_launch(const Int8Workspace& w, const float* Qf, floa
 
 template <class Geo>
 static hipError_t fa_masked_launch(const F16Workspace& w, const float* Qf, float* O, const MaskedCall& c, hipStream_t stream, Geo geo) {
-    const int nqb = masked_nqb(geo.units());
+    const int nqb = masked_nqb(grid_units(geo));
     const dim3 grid(c.B * c.Hkv * nqb), block(kWaves * 64);
     return f16_masked_d(c.D, [&](auto d) {
-        if constexpr (std::is_same<Geo, Varlen>::value)
+        if constexpr (std::is_same<Geo, Ragged>::value)
+            hipLaunchKernelGGL((qmha_fa_f16_ragged_kernel<decltype(d)::value>), grid, block, 0, stream, Qf, w.Kh, w.Vt, O, geo, c.lens,
+                               c.Hkv, c.d_model, nqb, softmax_scale_log2(c.D));
+        else if constexpr (std::is_same<Geo, Varlen>::value)
             hipLaunchKernelGGL((qmha_fa_f16_varlen_kernel<decltype(d)::value>), grid, block, 0, stream, Qf, w.Kh, w.Vt, O, geo, c.lens,
                                c.Hkv, c.d_model, nqb, softmax_scale_log2(c.D));
         else
@@ -353,6 +453,8 @@ QMHA_INSTANCE(Int8Workspace, Grouped)
 QMHA_INSTANCE(F16Workspace, Grouped)
 QMHA_INSTANCE(Int8Workspace, Varlen)
 QMHA_INSTANCE(F16Workspace, Varlen)
+QMHA_INSTANCE(Int8Workspace, Ragged)
+QMHA_INSTANCE(F16Workspace, Ragged)
 #undef QMHA_INSTANCE
 
 hipError_t launch_fa_masked(const Int8Workspace& w, const float* Qf, float* O, const MaskedCall& c, hipStream_t stream) {

@@ -1,6 +1,7 @@
     // qmha_fa_masked_f16.inc -- the body of every fp16 kernel of qmha_fa_masked.hip, included inside the __global__
     // (why a text include and no __device__ function: DESIGN.md 15.3).  In scope: D, the geometry `geo`, and the
-    // arguments Qf, Kh, Vt, O, H, d_model, nqb, c_log2.
+    // arguments Qf, Kh, Vt, O, H, d_model, nqb, c_log2.  row_shift(geo) / row_real(geo, row) (qmha_fa_masked.hip) are
+    // 0 / true for every geometry but Ragged, whose query rows sit `s` rows into their 32-row groups.
     QMHA_ENABLE_AGPR_MFMA();
     asm volatile("" : "+v"(c_log2));  // a VOP3 fma reading an SGPR issues at the slow rate
     constexpr int WAVES = kWaves, SG = kSG;
@@ -21,6 +22,9 @@
     const int b = bh / H, kvh = bh % H;  // bh: the K/V slice (H K/V heads)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if constexpr (kRaggedGeo<decltype(geo)>) {  // its grid follows the host's Nq, U the sequence's length: a workgroup with
+        if (qb0 * WAVES >= U) return;           // no active unit leaves before any barrier or DMA issue
+    }
     const int u = qb0 * WAVES + wave;
     const bool active = u < U;
     const int qg = geo.group(u), k = geo.head(kvh, u);  // query group, query head
@@ -36,8 +40,8 @@
     for (int qb = 0; qb < 2; ++qb)
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            if (active) {
-                const float* qp = Qf + ((size_t)b * Nq + (size_t)qg * QMHA_GROUP + 16 * qb + r16) * d_model + (size_t)k * D +
+            if (active && row_real(geo, qg * QMHA_GROUP + 16 * qb + r16)) {  // a pad lane (Ragged) loads nothing
+                const float* qp = Qf + ((size_t)b * Nq + (size_t)qg * QMHA_GROUP + 16 * qb + r16 - row_shift(geo)) * d_model + (size_t)k * D +
                                   32 * ks + 8 * grp;
                 const v4f a = *reinterpret_cast<const v4f*>(qp), c = *reinterpret_cast<const v4f*>(qp + 4);
 #pragma unroll
@@ -192,13 +196,15 @@
             l += __shfl_xor(l, 16);
             l += __shfl_xor(l, 32);
             const bool ok = l > 1e-10f;  // fa_tc_v1a.cu:384-388
-            float* orow = O + ((size_t)b * Nq + (size_t)qg * QMHA_GROUP + 16 * qb + r16) * d_model + (size_t)k * D + 4 * grp;
+            float* orow = O + ((size_t)b * Nq + (size_t)qg * QMHA_GROUP + 16 * qb + r16 - row_shift(geo)) * d_model + (size_t)k * D + 4 * grp;
+            if (row_real(geo, qg * QMHA_GROUP + 16 * qb + r16)) {  // a pad lane stores nothing
 #pragma unroll
             for (int m = 0; m < DB; ++m) {
                 v4f w;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) w[j] = ok ? o[m][qb][j] / l : 0.0f;
                 *reinterpret_cast<v4f*>(orow + 16 * m) = w;
+            }
             }
         }
     }

@@ -1,6 +1,7 @@
     // qmha_fa_masked_int8.inc -- the body of every int8 kernel of qmha_fa_masked.hip, included inside the __global__
     // (why a text include and no __device__ function: DESIGN.md 15.3).  In scope: D, Geo, the geometry `geo`, and the
-    // arguments Qf, Ki, Vh, sK, sV, O, H, d_model, nqb, c_log2.
+    // arguments Qf, Ki, Vh, sK, sV, O, H, d_model, nqb, c_log2.  row_shift(geo) / row_real(geo, row) (qmha_fa_masked.hip)
+    // are 0 / true for every geometry but Ragged, whose query rows sit `s` rows into their 32-row groups.
     constexpr int WAVES = kWaves, SG = kSG;
     constexpr int KS = D / 32;               // i8 MFMA k-steps (QK) and d-blocks (PV)
     constexpr int KBYTES = SG * 32 * D;      // K int8 per stage
@@ -23,6 +24,9 @@
     for (int pass = 0; pass < 2; ++pass) {  // the pair's large q-block, then its mirror (uniform)
     const int qb = pass == 0 ? nqb - 1 - pi : pi;
     if (pass == 1 && pi == nqb - 1 - pi) break;  // odd nqb: the middle q-block has no partner
+    if constexpr (kRaggedGeo<decltype(geo)>) {  // its grid follows the host's Nq, U the sequence's length: a pass with no
+        if (qb * WAVES >= U) continue;          // active unit leaves before any barrier or DMA issue (workgroup-uniform)
+    }
     const int u = qb * WAVES + wave;
     const bool active = u < U;  // wave-uniform; an inactive wave still stages and syncs
     const int qg = geo.group(u), k = geo.head(kvh, u);  // query group, query head
@@ -38,12 +42,17 @@
     float cq = 0.0f;
     if (active) {
         const float* qrow = Qf + ((size_t)b * Nq + (size_t)qg * QMHA_GROUP + col) * d_model + (size_t)k * D;
+        if constexpr (kRaggedGeo<decltype(geo)>) qrow -= (size_t)row_shift(geo) * d_model;
         v4f x[KS][4];
         float amax = 0.0f;
 #pragma unroll
         for (int s = 0; s < KS; ++s)
 #pragma unroll
             for (int c4 = 0; c4 < 4; ++c4) {
+                if constexpr (kRaggedGeo<decltype(geo)>) {  // a pad lane holds a zero row and loads nothing
+                    x[s][c4] = v4f{};
+                    if (row_real(geo, qg * QMHA_GROUP + col)) x[s][c4] = *reinterpret_cast<const v4f*>(qrow + 32 * s + 16 * half + 4 * c4);
+                } else
                 x[s][c4] = *reinterpret_cast<const v4f*>(qrow + 32 * s + 16 * half + 4 * c4);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -230,6 +239,8 @@
         }
         const bool ok = l > 1e-20f;
         float* orow = O + ((size_t)b * Nq + (size_t)qg * QMHA_GROUP + col) * d_model + (size_t)k * D + 4 * half;
+        if constexpr (kRaggedGeo<decltype(geo)>) orow -= (size_t)row_shift(geo) * d_model;
+        if (kRaggedGeo<decltype(geo)> ? row_real(geo, qg * QMHA_GROUP + col) : true)  // a pad lane (Ragged) stores nothing
 #pragma unroll
         for (int m = 0; m < KS; ++m)
 #pragma unroll

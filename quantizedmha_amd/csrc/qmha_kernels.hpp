@@ -192,6 +192,9 @@ hipError_t f16_masked_d(int D, F&& f) {
 //     varlen kernels, Hkv == H included.  Sequence b computes what the cache mode computes at len = lens[b] -- without
 //     the mask over rows [0, lens[b]), whatever cap is --; lens[b] % 32 != 0, > cap, < Nq (causal) or < 32 (not): its O
 //     rows are zeros and none of its K/V is read.
+//   token-granular lengths (ragged, with lens and causal): the ragged kernels.  Any 1 <= Nq <= Nk; sequence
+//     b, Nq <= lens[b] <= Nk, computes rows [s, s + Nq), s = (lens[b] - Nq) mod 32, of the per-sequence-length mode on a
+//     zero block of ceil32(s + Nq) rows holding Q there, at ceil32(lens[b]); any other lens[b]: its Nq rows of O are zeros.
 // B * Hkv K/V slices per grid.  int8: d in {32, 64, 128}; fp16: d in {64, 128} (qmha_api.cpp's variant table).  A shape
 // or head count outside the above, d_model != H * D, an unbuilt d: hipErrorInvalidValue, nothing launched.
 struct MaskedCall {
@@ -199,6 +202,7 @@ struct MaskedCall {
     bool causal;
     int len;
     const int32_t* lens;
+    bool ragged = false;  // lens at token granularity (the ragged kernels): any 1 <= Nq <= Nk, causal only
 };
 hipError_t launch_fa_masked(const Int8Workspace& w, const float* Qf, float* O, const MaskedCall& c, hipStream_t stream);
 hipError_t launch_fa_masked(const F16Workspace& w, const float* Qf, float* O, const MaskedCall& c, hipStream_t stream);
@@ -215,6 +219,17 @@ hipError_t launch_fa_int8_masked_pstage_dump(const Int8Workspace& w, const float
 hipError_t launch_kv_append(const float* K, const float* V, const Int8Workspace& w, int B, int n, int cap, int len,
                             const int32_t* pos, int H, int D, int d_model, hipStream_t stream);
 hipError_t launch_kv_append(const float* K, const float* V, const F16Workspace& w, int B, int n, int cap, int len,
+                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream);
+
+// Token-granular append: any 1 <= n <= cap rows per sequence at any row pos[b] (DEVICE int32[B], non-null);
+// every 32-row group that rows [pos[b], pos[b] + n) touch is written as the append kernels write that group's rows so
+// far, zero-padded.  tail: the int8 cache's raw fp32 rows of each sequence's open group, [2][B][32][d_model] (K, then V),
+// read for the rows ahead of pos[b] in its group and rewritten while the last group stays open; fp16 has none (ignored).
+// pos[b] < 0 or pos[b] + n > cap: that sequence writes nothing.  Bad host arguments: hipErrorInvalidValue.
+inline size_t kv_tail_bytes(int B, int H, int D) { return align_up((size_t)2 * B * 32 * H * D * sizeof(float), 256); }
+hipError_t launch_kv_tokens(const float* K, const float* V, const Int8Workspace& w, float* tail, int B, int n, int cap,
+                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream);
+hipError_t launch_kv_tokens(const float* K, const float* V, const F16Workspace& w, float* tail, int B, int n, int cap,
                             const int32_t* pos, int H, int D, int d_model, hipStream_t stream);
 
 // ---- FP32 (fa: scalar VALU kernel; fa_mfma: the same contract on v_mfma_f32_32x32x2_f32) -----

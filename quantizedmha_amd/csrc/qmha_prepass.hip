@@ -9,6 +9,8 @@
 //                           (qmha_kv_cache_append), written behind the cache's valid rows
 //   qmha_kv_place_{int8,f16}_kernel   the append kernels' body with a row per sequence, read from device memory
 //                           (qmha_kv_cache_append_at)
+//   qmha_kv_token_{int8,f16}_kernel   any number of rows at any row of a sequence: the open 32-row group is written
+//                           again from its raw rows (qmha_kv_cache_append_tokens)
 #include <atomic>
 
 #include "qmha_common.hpp"
@@ -223,6 +225,172 @@ __global__ __launch_bounds__(256) void qmha_kv_place_f16_kernel(
     const int len = place_row(pos, n, cap, H, total_groups);
     if (len < 0) return;
 #include "qmha_kv_append_f16.inc"
+}
+
+// ---------------------------------------------------------------------------------------
+// Token-granular append (qmha_kv_cache_append_tokens): any 1 <= n <= cap rows per sequence at any
+// row pos[b].  A cache that holds L rows of a sequence holds the bytes the append kernels write for those rows
+// zero-padded to ceil32(L), so a touched 32-row group is written whole from its 32 assembled rows.
+// One wave per (tensor, K/V slice, touched group): rows [pos[b], pos[b] + n) touch groups g0 = pos[b] / 32 ..
+// g1 = (pos[b] + n - 1) / 32, at most (n + 30) / 32 + 1 of them.  Item j of a slice: j == 0 runs group g0 and then, if
+// it is another one, group g1; 0 < j < g1 - g0 runs group g0 + j; any other item returns -- so a slice has
+// `maxg` = max(1, (n + 30) / 32) items.  pos[b] < 0 or pos[b] + n > cap: every item of the sequence returns, nothing is written.
+// ---------------------------------------------------------------------------------------
+// This wave's item: the slice bh, the sequence's first row p (-1: nothing to do) and the groups g0, g1
+struct TokenItem {
+    int bh, j, p, g0, g1;
+};
+__device__ __forceinline__ TokenItem token_item(const int32_t* __restrict__ pos, int n, int cap, int H, int maxg, int total) {
+    TokenItem it{0, 0, -1, 0, 0};
+    const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= total) return it;
+    it.bh = item / maxg, it.j = item % maxg;
+    const int p = pos[it.bh / H];
+    if (p < 0 || p > cap - n) return it;
+    it.g0 = p / QMHA_GROUP, it.g1 = (p + n - 1) / QMHA_GROUP;
+    if (it.j == 0 || it.j < it.g1 - it.g0) it.p = p;
+    return it;
+}
+
+// int8.  The open group's scale comes from the rows present (zero rows do not move an absmax), and the group is
+// quantised again from its raw rows whenever rows are added: `tail` ([2][B][32][H * D] fp32, K then V) keeps the raw
+// rows of each sequence's open group.  Row a of group g comes from the tail (a < p: rows of earlier token appends,
+// group g0 only), from the new rows (p <= a < p + n) or is zero; the arithmetic is quant_row_group's /
+// quant_v_group's, on the lane maps of those functions.  A group that stays open (g1, when (p + n) % 32 != 0) has its
+// new rows written to the tail.  The wave that reads the tail (group g0) is the wave that rewrites it (group g1), and
+// its loads have returned before its first store (the absmax needs them): no other wave touches the (tensor,
+// sequence, head) columns of the tail.
+template <int D, bool ISV>
+__device__ __forceinline__ void token_groups_int8(const float* __restrict__ X, float* __restrict__ T, int8_t* __restrict__ Ki,
+                                                  _Float16* __restrict__ Vh, float* __restrict__ sX, char* vtr,
+                                                  const TokenItem& it, int n, int Gc, int d_model) {
+    constexpr int C4 = D / 4, RPI = 64 / C4, NI = 32 / RPI;
+    const int lane = threadIdx.x & 63, p = it.p;
+    // K: lane (ri, ci) holds rows i * RPI + ri; V: lane (rq, c4) holds the NI consecutive rows NI * rq + i
+    const int r0 = ISV ? (lane / C4) * NI : lane / C4;
+    constexpr int rs = ISV ? 1 : RPI;
+#pragma nounroll
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass == 1 && (it.j != 0 || it.g1 == it.g0)) break;
+        const int g = pass == 0 ? it.g0 + it.j : it.g1;
+        const int lo = p - g * QMHA_GROUP, hi = lo + n;  // the new rows of this group: lo <= r < hi
+        v4f x[NI];
+        float amax = 0.0f;
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int r = r0 + i * rs;
+            x[i] = v4f{};
+            if (r < hi)
+                x[i] = r >= lo ? QMHA_PRE_LOAD(reinterpret_cast<const v4f*>(X + (size_t)(r - lo) * d_model))
+                               : *reinterpret_cast<const v4f*>(T + (size_t)r * d_model);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) amax = fmaxf(amax, fabsf(x[i][c]));
+        }
+        const float sc = qmha_scale_from_absmax(wave_max64(amax));
+        const float inv = 1.0f / sc;
+        const size_t gi = (size_t)it.bh * Gc + g;  // the group's index in the cache's arrays
+        if constexpr (ISV) {
+            vt_group_store<D, true>(vtr, x, inv, lane, reinterpret_cast<char*>(Vh) + gi * (size_t)(64 * D));
+        } else {
+            int8_t* dst = Ki + gi * (size_t)(QMHA_GROUP * D) + 4 * (lane % C4);
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                uint32_t w = 0;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) w |= ((uint32_t)(uint8_t)qmha_quant_i8(x[i][c], inv)) << (8 * c);
+                *reinterpret_cast<uint32_t*>(dst + (size_t)(r0 + i * rs) * D) = w;
+            }
+        }
+        if (lane == 0) sX[gi] = sc;
+        if (g == it.g1 && ((p + n) & (QMHA_GROUP - 1)) != 0) {  // the group stays open: its new raw rows to the tail
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                const int r = r0 + i * rs;
+                if (r >= lo && r < hi) *reinterpret_cast<v4f*>(T + (size_t)r * d_model) = x[i];
+            }
+        }
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void qmha_kv_token_int8_kernel(
+    const float* __restrict__ K, const float* __restrict__ V, int8_t* __restrict__ Ki, _Float16* __restrict__ Vh,
+    float* __restrict__ sK, float* __restrict__ sV, float* __restrict__ tail, int B, int n, int cap,
+    const int32_t* __restrict__ pos, int H, int d_model, int maxg, int total) {
+    __shared__ __attribute__((aligned(16))) char vtr[4][D * QMHA_VT_PITCH];
+    const TokenItem it = token_item(pos, n, cap, H, maxg, total);
+    if (it.p < 0) return;  // wave-uniform; the LDS tile is per wave, no workgroup barrier follows
+    const int b = it.bh / H, k = it.bh % H;
+    const size_t col = (size_t)k * D + 4 * ((threadIdx.x & 63) % (D / 4));  // this lane's columns of a row
+    const size_t src = (size_t)b * n * d_model + col, trow = (size_t)b * QMHA_GROUP * d_model + col;
+    if (blockIdx.y == 1)
+        token_groups_int8<D, true>(V + src, tail + (size_t)B * QMHA_GROUP * d_model + trow, Ki, Vh, sV, vtr[threadIdx.x >> 6], it, n,
+                                   cap / QMHA_GROUP, d_model);
+    else
+        token_groups_int8<D, false>(K + src, tail + trow, Ki, Vh, sK, vtr[threadIdx.x >> 6], it, n, cap / QMHA_GROUP, d_model);
+}
+
+// fp16: a row converts on its own, so there is no tail.  A group this call opens (a group behind g0, or g0 when pos[b]
+// is a multiple of 32) is written whole, the rows behind the new ones as zeros -- masked P entries are 0, and 0 times a
+// stale inf would be NaN --, with the stores of qmha_kv_append_f16_kernel.  A group that earlier rows opened (g0
+// otherwise) gets the new rows only: their Kh rows, and their slots of the V^T block, two bytes each.
+template <int D, bool ISV>
+__device__ __forceinline__ void token_groups_f16(const float* __restrict__ X, _Float16* __restrict__ Kh, _Float16* __restrict__ Vt,
+                                                 char* vtr, const TokenItem& it, int n, int Gc, int d_model) {
+    constexpr int C4 = D / 4, RPI = 64 / C4, NI = 32 / RPI;
+    const int lane = threadIdx.x & 63, p = it.p;
+    const int r0 = ISV ? (lane / C4) * NI : lane / C4, c4 = lane % C4;
+    constexpr int rs = ISV ? 1 : RPI;
+#pragma nounroll
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass == 1 && (it.j != 0 || it.g1 == it.g0)) break;
+        const int g = pass == 0 ? it.g0 + it.j : it.g1;
+        const size_t gi = (size_t)it.bh * Gc + g;
+        const int lo = p - g * QMHA_GROUP, hi = lo + n;  // the new rows of this group: lo <= r < hi
+        const bool opens = lo <= 0;                       // a group behind g0, or g0 at a multiple of 32
+        if (ISV && !opens) {  // the new rows' slots of the block: element (d, slot) of [D][32]
+            const int cnt = min(hi, QMHA_GROUP) - lo;
+            _Float16* blk = Vt + gi * (size_t)(QMHA_GROUP * D);
+            for (int e = lane; e < cnt * D; e += 64) {
+                const int i = e / D, d = e % D;
+                blk[d * QMHA_GROUP + slot_of_kv_f16(lo + i)] = (_Float16)X[(size_t)i * d_model + d];  // RNE
+            }
+            continue;
+        }
+        v4f x[NI];
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int r = r0 + i * rs;
+            x[i] = v4f{};
+            if (r >= lo && r < hi) x[i] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(X + (size_t)(r - lo) * d_model + 4 * c4));
+        }
+        if constexpr (ISV) {
+            vt_group_store<D, false>(vtr, x, 1.0f, lane, reinterpret_cast<char*>(Vt + gi * (size_t)(QMHA_GROUP * D)));
+        } else {
+            _Float16* dst = Kh + gi * (size_t)(QMHA_GROUP * D) + 4 * c4;
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                const int r = r0 + i * rs;
+                if (!opens && (r < lo || r >= hi)) continue;  // rows of earlier appends, and the zeros behind them, stay
+                v4h hv;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) hv[c] = (_Float16)x[i][c];  // RNE (= __float2half)
+                *reinterpret_cast<v4h*>(dst + (size_t)r * D) = hv;
+            }
+        }
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void qmha_kv_token_f16_kernel(
+    const float* __restrict__ K, const float* __restrict__ V, _Float16* __restrict__ Kh, _Float16* __restrict__ Vt,
+    int n, int cap, const int32_t* __restrict__ pos, int H, int d_model, int maxg, int total) {
+    __shared__ __attribute__((aligned(16))) char vtr[4][D * QMHA_VT_PITCH];
+    const TokenItem it = token_item(pos, n, cap, H, maxg, total);
+    if (it.p < 0) return;  // wave-uniform; the LDS tile is per wave, no workgroup barrier follows
+    const size_t src = (size_t)(it.bh / H) * n * d_model + (size_t)(it.bh % H) * D;
+    if (blockIdx.y == 1) token_groups_f16<D, true>(V + src, Kh, Vt, vtr[threadIdx.x >> 6], it, n, cap / QMHA_GROUP, d_model);
+    else token_groups_f16<D, false>(K + src, Kh, Vt, vtr[threadIdx.x >> 6], it, n, cap / QMHA_GROUP, d_model);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -709,6 +877,35 @@ hipError_t launch_kv_append(const float* K, const float* V, const F16Workspace& 
         else
             hipLaunchKernelGGL((qmha_kv_append_f16_kernel<decltype(d)::value>), grid, dim3(256), 0, stream, K, V, w.Kh, w.Vt, n, cap,
                                len, H, d_model, total);
+        return hipGetLastError();
+    });
+}
+
+// ---- token-granular append: rows [pos[b], pos[b] + n) of sequence b, any 1 <= n <= cap ----
+// items of a K/V slice: a wave per touched group, the first wave taking the last group too
+static int token_items(int n) { return n <= 2 ? 1 : (n + QMHA_GROUP - 2) / QMHA_GROUP; }
+static bool kv_tokens_shape_ok(int B, int n, int cap, const int32_t* pos, int H) {
+    return B >= 1 && H >= 1 && pos && n >= 1 && cap >= QMHA_GROUP && cap % QMHA_GROUP == 0 && n <= cap;
+}
+
+hipError_t launch_kv_tokens(const float* K, const float* V, const Int8Workspace& w, float* tail, int B, int n, int cap,
+                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream) {
+    if (!kv_tokens_shape_ok(B, n, cap, pos, H) || !tail) return hipErrorInvalidValue;
+    const int maxg = token_items(n), total = B * H * maxg;
+    return int8_masked_d(D, [&](auto d) {
+        hipLaunchKernelGGL((qmha_kv_token_int8_kernel<decltype(d)::value>), dim3((total + 3) / 4, 2), dim3(256), 0, stream, K, V, w.Ki,
+                           w.Vh, w.sK, w.sV, tail, B, n, cap, pos, H, d_model, maxg, total);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_kv_tokens(const float* K, const float* V, const F16Workspace& w, float*, int B, int n, int cap,
+                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream) {
+    if (!kv_tokens_shape_ok(B, n, cap, pos, H)) return hipErrorInvalidValue;
+    const int maxg = token_items(n), total = B * H * maxg;
+    return f16_masked_d(D, [&](auto d) {
+        hipLaunchKernelGGL((qmha_kv_token_f16_kernel<decltype(d)::value>), dim3((total + 3) / 4, 2), dim3(256), 0, stream, K, V, w.Kh,
+                           w.Vt, n, cap, pos, H, d_model, maxg, total);
         return hipGetLastError();
     });
 }

@@ -18,6 +18,8 @@
 //     (grouped-query attention, qmha_solve_gqa / qmha_kv_cache_create_gqa); None is the multi-head form;
 //   * both caches' `append_at` / `attend_varlen`: a row / a length per sequence in int32 [B] device tensors that the
 //     kernels read (qmha_kv_cache_append_at / qmha_attend_cached_varlen);
+//   * both caches' `enable_tokens` / `append_tokens` / `attend_tokens`: the same at any length -- any number of rows at any
+//     row, any Nq, causal (qmha_kv_cache_attach_tail / qmha_kv_cache_append_tokens / qmha_attend_cached_tokens);
 //   * a rejected shape raises (TORCH_CHECK on the C-ABI status) instead of a device assert.
 #include <torch/extension.h>
 // ROCm PyTorch reports HIP devices as device type "cuda": the guard / current-stream
@@ -225,6 +227,39 @@ public:
         return out_opt ? out : out.view(Q.sizes());
     }
 
+    // allocate and attach the tail of raw rows append_tokens needs (qmha_kv_cache_attach_tail); once, outside a capture
+    void enable_tokens() {
+        if (tail_.defined()) return;
+        const size_t bytes = qmha_kv_cache_tail_bytes(handle_);
+        tail_ = torch::zeros({static_cast<int64_t>(bytes > 0 ? bytes : 1)}, torch::TensorOptions().dtype(torch::kUInt8).device(mem_.device()));
+        const int st = qmha_kv_cache_attach_tail(handle_, tail_.data_ptr(), bytes);
+        TORCH_CHECK(st == QMHA_OK, "KVCache.enable_tokens", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+    }
+    std::optional<Tensor> tail() const { return tail_.defined() ? std::optional<Tensor>(tail_) : std::nullopt; }
+
+    // append_at for any number of rows at any row (qmha_kv_cache_append_tokens)
+    void append_tokens(const Tensor& K, const Tensor& V, const Tensor& pos) {
+        auto Kc = rows(K, "K", kv_model_), Vc = rows(V, "V", kv_model_);
+        TORCH_CHECK(Kc.sizes() == Vc.sizes(), "K and V must have the same shape");
+        per_seq(pos, "pos");
+        const OnStream on = current_stream(mem_.device());
+        const int st = qmha_kv_cache_append_tokens(handle_, Kc.data_ptr<float>(), Vc.data_ptr<float>(), static_cast<int>(Kc.size(1)),
+                                                   pos.data_ptr<int32_t>(), on.stream);
+        TORCH_CHECK(st == QMHA_OK, "KVCache.append_tokens", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+    }
+
+    // causal attend_varlen for any Nq and any lengths (qmha_attend_cached_tokens)
+    Tensor attend_tokens(const Tensor& Q, const Tensor& lens, std::optional<Tensor> out_opt) {
+        auto Qc = rows(Q, "Q", d_model_);
+        per_seq(lens, "lens");
+        Tensor out = out_for(out_opt, Qc);
+        const OnStream on = current_stream(mem_.device());
+        const int st = qmha_attend_cached_tokens(handle_, Qc.data_ptr<float>(), out.data_ptr<float>(), static_cast<int>(Qc.size(1)),
+                                                 lens.data_ptr<int32_t>(), QMHA_FLAG_CAUSAL, on.stream);
+        TORCH_CHECK(st == QMHA_OK, "KVCache.attend_tokens", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+        return out_opt ? out : out.view(Q.sizes());
+    }
+
 private:
     // a per-sequence int32 [B] tensor on the cache's device, contiguous: the kernel reads it, the host does not
     void per_seq(const Tensor& t, const char* name) const {
@@ -247,7 +282,7 @@ private:
     }
     int64_t B_, cap_, d_model_, kv_model_;
     std::string kernel_;
-    Tensor mem_;
+    Tensor mem_, tail_;
     qmha_kv_cache_t* handle_ = nullptr;
 };
 
@@ -276,6 +311,14 @@ PYBIND11_MODULE(torch_ext, m) {
              pybind11::arg("out") = pybind11::none(),
              "attend with a length per sequence: sequence b attends its first lens[b] cache rows; lens: int32 [B] on the\n"
              "device, read by the kernel; an invalid lens[b] gives zeros for that sequence.")
+        .def("enable_tokens", &KVCache::enable_tokens,
+             "allocate and attach the tail of raw rows append_tokens needs (int8); once, outside a graph capture.")
+        .def("append_tokens", &KVCache::append_tokens, pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("pos"),
+             "append_at for any number of rows n >= 1 at any row pos[b]; the touched 32-row groups hold what append_at writes\n"
+             "for their rows so far, zero-padded; an invalid pos[b] writes nothing for that sequence.")
+        .def("attend_tokens", &KVCache::attend_tokens, pybind11::arg("Q"), pybind11::arg("lens"), pybind11::arg("out") = pybind11::none(),
+             "causal attend_varlen for any Nq >= 1 and any lens[b] in [Nq, cap]; an invalid lens[b] gives zeros.")
+        .def_property_readonly("tail", &KVCache::tail)
         .def_property_readonly("len", &KVCache::len)
         .def_property_readonly("cap", &KVCache::cap)
         .def_property_readonly("mem", &KVCache::mem);

@@ -174,7 +174,9 @@ class KVCache:
     K/V heads than query heads.
     append_at(K, V, pos) / attend_varlen(Q, lens) take a row / a length per sequence from int32 [B] tensors on the
     device, read by the kernels when they run: sequences of different lengths in one cache, and a step that is captured
-    once and replayed while the caller advances pos / lens in device memory.  They leave `len` alone."""
+    once and replayed while the caller advances pos / lens in device memory.  They leave `len` alone.
+    enable_tokens() once, then append_tokens(K, V, pos) / attend_tokens(Q, lens): the same at any length -- a prompt of
+    1000 rows, a decode step of one (qmha_kv_cache_append_tokens / qmha_attend_cached_tokens; causal only)."""
 
     def __init__(self, B: int, cap: int, d_model: int, num_heads: int, kernel: str = _lib.DEFAULT_KERNEL, device="cuda"):
         self._setup(B, cap, d_model, num_heads, None, kernel, device)
@@ -194,6 +196,7 @@ class KVCache:
         lib = _lib.load()
         vid = _lib.variant_id(kernel)
         self._handle = None
+        self.tail = None  # enable_tokens()
         if num_kv_heads is None:
             nbytes = lib.qmha_kv_cache_bytes(self.B, self.cap, self.d_model, self.num_heads, vid)
         else:  # the carve of num_kv_heads heads
@@ -294,6 +297,44 @@ class KVCache:
             st = _lib.load().qmha_attend_cached_varlen(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[1],
                                                        lens.data_ptr(), _lib.QMHA_FLAG_CAUSAL if causal else 0, stream)
         _lib.check(st, f"KVCache.attend_varlen({self.kernel})")
+        return out.view(Q.shape) if out.numel() == Q.numel() and out.dim() != Q.dim() else out
+
+
+    def enable_tokens(self) -> None:
+        """Allocate and attach the tail append_tokens needs (qmha_kv_cache_attach_tail): the raw rows of each sequence's
+        open 32-row group, `.tail` (int8; an fp16 cache needs none).  Once, and outside a graph capture: append_tokens
+        and attend_tokens themselves allocate nothing."""
+        if self.tail is not None:
+            return
+        lib = _lib.load()
+        nbytes = lib.qmha_kv_cache_tail_bytes(self._handle)
+        self.tail = torch.zeros(max(nbytes, 1), dtype=torch.uint8, device=self.device)
+        _lib.check(lib.qmha_kv_cache_attach_tail(self._handle, self.tail.data_ptr(), nbytes), f"KVCache.enable_tokens({self.kernel})")
+
+    def append_tokens(self, K: torch.Tensor, V: torch.Tensor, pos: torch.Tensor) -> None:
+        """append_at for any number of rows at any row (qmha_kv_cache_append_tokens): sequence b's n >= 1 rows go to cache
+        rows [pos[b], pos[b] + n), and every 32-row group they touch holds what append_at writes for the group's rows so
+        far, zero-padded (int8: the open group is quantised again from its raw rows).  A sequence whose pos[b] is
+        negative or beyond cap - n writes nothing.  Needs enable_tokens() on an int8 cache."""
+        Kc, Vc = self._rows(K, "K", self.kv_model), self._rows(V, "V", self.kv_model)
+        if Kc.shape != Vc.shape:
+            raise RuntimeError("K and V must have the same shape")
+        pos = self._per_seq(pos, "pos")
+        with _current_stream(self.device) as stream:
+            st = _lib.load().qmha_kv_cache_append_tokens(self._handle, Kc.data_ptr(), Vc.data_ptr(), Kc.shape[1], pos.data_ptr(),
+                                                         stream)
+        _lib.check(st, f"KVCache.append_tokens({self.kernel})")
+
+    def attend_tokens(self, Q: torch.Tensor, lens: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Causal attend_varlen for any Nq >= 1 and any lengths (qmha_attend_cached_tokens): row r of sequence b attends
+        cache rows j <= r + (lens[b] - Nq).  A sequence whose lens[b] is below Nq or above cap gets zeros."""
+        Qc = self._rows(Q, "Q")
+        lens = self._per_seq(lens, "lens")
+        out = _out_for(out, Qc, "size")
+        with _current_stream(self.device) as stream:
+            st = _lib.load().qmha_attend_cached_tokens(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[1], lens.data_ptr(),
+                                                       _lib.QMHA_FLAG_CAUSAL, stream)
+        _lib.check(st, f"KVCache.attend_tokens({self.kernel})")
         return out.view(Q.shape) if out.numel() == Q.numel() and out.dim() != Q.dim() else out
 
 

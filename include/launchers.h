@@ -262,6 +262,57 @@ int qmha_kv_cache_append_tokens(qmha_kv_cache_t *c, const float *K, const float 
 int qmha_attend_cached_tokens(qmha_kv_cache_t *c, const float *Q, float *O, int Nq, const int32_t *lens, unsigned flags,
                               void *stream);
 
+/*
+ * Paged caches -- a pool of pages and a block table, for a server whose sequences come, grow and go: memory follows the
+ * rows that exist, a finished sequence's pages go to another slot, and sequences with a common prompt share its pages.
+ * A paged call is DEFINED as the token-granular call above with the row address looked up through the table, and
+ * matches it bit for bit.  Multi-head and grouped caches alike; causal only.
+ *
+ *   page           page_rows rows of all h_kv K/V heads of one sequence; page_rows % 64 == 0, page_rows >= 64 (a stage of
+ *                  the kernels is two 32-row key tiles, so it never straddles pages).
+ *   pool           num_pages pages: the variant's workspace carve with B := num_pages, N := page_rows, H := h_kv.  Page p,
+ *                  K/V head kvh is head slice p * h_kv + kvh of every array.  paged_bytes(num_pages, page_rows, d_model, h,
+ *                  h_kv, variant) == qmha_workspace_size(num_pages, page_rows, h_kv * d, h_kv, variant): nothing new is
+ *                  laid out, and 32-row quantisation groups are independent, so a page holds the same bytes wherever it is.
+ *   table          a DEVICE int32 [B][max_pages] array, row-major, caller-owned, passed with every call and read by the
+ *                  kernels when they run, like pos and lens: the host never reads it, so a captured step follows a table
+ *                  that the caller advances in device memory.  Row r of sequence b lives in page table[b][r / page_rows]
+ *                  at row r % page_rows; a sequence's logical capacity is cap = max_pages * page_rows.  The caller owns
+ *                  the allocation policy: the library keeps no free list.
+ *   create_paged   the handle of the calls above, marked paged; B is the number of sequence slots.  page_rows % 64 != 0,
+ *                  num_pages < 1, max_pages < 1, memory not 256-byte aligned or below paged_bytes: QMHA_ERR_INVALID; the
+ *                  head rules and QMHA_ERR_NOSYS of qmha_kv_cache_create_gqa.  qmha_kv_cache_len of a paged cache is 0.
+ *   tail           qmha_kv_cache_tail_bytes / _attach_tail as above.  The tail belongs to the B sequence slots, not to
+ *                  pages: [2][B][32][h_kv * d].
+ *   append_paged   K, V: [B, n, h_kv * d], any 1 <= n <= cap (host check).  On the device, sequence b is valid when
+ *                  pos[b] >= 0, pos[b] + n <= cap and every table entry that rows [pos[b], pos[b] + n) use lies in
+ *                  [0, num_pages).  It leaves, in every page it touches, the bytes append_tokens leaves in those rows of a
+ *                  contiguous cache; other pages, other groups and the rows at and beyond ceil32(pos[b] + n) are neither
+ *                  read nor written.  An invalid sequence writes nothing, the tail included.  The rule on partial groups
+ *                  is append_tokens': build one with append_paged from its first row on.
+ *   attend_paged   Q, O: [B, Nq, d_model], any 1 <= Nq <= cap; flags must be QMHA_FLAG_CAUSAL (host checks).  On the device,
+ *                  sequence b is valid when Nq <= lens[b] <= cap and every table entry of pages 0 .. ceil(lens[b] /
+ *                  page_rows) - 1 lies in [0, num_pages): O holds the bits of attend_tokens on the contiguous cache.  An
+ *                  invalid sequence: its Nq rows of O are positive zeros and none of its K/V is read.  Entries behind the
+ *                  pages a call uses are not looked at (a caller may keep -1 there), and no table content is ever turned
+ *                  into an address outside the pool.
+ *   sharing        two sequences may name the same page in an attend: prefix sharing, read-only.  Two sequences WRITING one
+ *                  page in one append_paged is the caller's error: the result in that page is unspecified and nothing else
+ *                  is affected.  Leave a sequence out of an append with pos[b] = -1.
+ *
+ * The contiguous entry points (append, attend, append_at, attend_varlen, append_tokens, attend_tokens, truncate) on a
+ * paged cache return QMHA_ERR_INVALID, and so do the paged entry points on a contiguous cache.  Null pos / lens / table:
+ * QMHA_ERR_INVALID.  Every host check runs before any HIP call; no allocation, no synchronisation (both calls can be
+ * captured in a hipGraph); the cache's mutex is held across the enqueue; qmha_profile records are those of append / attend.
+ */
+size_t qmha_kv_cache_paged_bytes(int num_pages, int page_rows, int d_model, int h, int h_kv, int variant);
+int qmha_kv_cache_create_paged(qmha_kv_cache_t **out, void *mem, size_t bytes, int B, int num_pages, int page_rows,
+                               int max_pages, int d_model, int h, int h_kv, int variant);
+int qmha_kv_cache_append_paged(qmha_kv_cache_t *c, const float *K, const float *V, int n, const int32_t *pos,
+                               const int32_t *table, void *stream);
+int qmha_attend_cached_paged(qmha_kv_cache_t *c, const float *Q, float *O, int Nq, const int32_t *lens, const int32_t *table,
+                             unsigned flags, void *stream);
+
 /* Blocking convenience used by the per-variant `solve` shims and the JAX raw-pointer
  * binding (extensions/jax/jax_ext.cpp:12-28): batch 1, synchronises the device stream. */
 int qmha_solve_variant(const float *Q, const float *K, const float *V, float *O, int N, int d_model, int h,

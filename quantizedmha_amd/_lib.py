@@ -43,6 +43,11 @@ SIGNATURES = {
     "qmha_kv_cache_attach_tail": (_i, [_vp, _vp, _sz]),
     "qmha_kv_cache_append_tokens": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "qmha_attend_cached_tokens": (_i, [_vp, _vp, _vp, _i, _vp, ctypes.c_uint, _vp]),
+    # paged caches: a pool of pages, and a device int32[B][max_pages] block table beside pos / lens
+    "qmha_kv_cache_paged_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "qmha_kv_cache_create_paged": (_i, [ctypes.POINTER(_vp), _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "qmha_kv_cache_append_paged": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "qmha_attend_cached_paged": (_i, [_vp, _vp, _vp, _i, _vp, _vp, ctypes.c_uint, _vp]),
     "qmha_solve_ws": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "qmha_solve_variant": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     "qmha_quantize_int8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),

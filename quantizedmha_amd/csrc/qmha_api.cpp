@@ -528,6 +528,12 @@ struct qmha_kv_cache {
     int len;   // valid rows of every head slice
     // the raw rows of each sequence's open group (qmha_kv_cache_attach_tail; int8 only), caller-owned like `mem`
     void* tail = nullptr;
+    // a paged cache (qmha_kv_cache_create_paged): `mem` is a pool of num_pages pages of page_rows rows --
+    // the variant's carve at B := num_pages, N := page_rows --, cap the logical capacity max_pages * page_rows of a
+    // sequence, B the sequence slots (the tail's).  num_pages == 0: a contiguous cache.
+    int num_pages = 0, page_rows = 0, max_pages = 0;
+    bool paged() const { return num_pages > 0; }
+    qmha::PageTable pages(const int32_t* table) const { return {table, page_rows, max_pages, num_pages}; }
 };
 
 namespace {
@@ -535,8 +541,9 @@ namespace {
 // f(the cache's memory as its variant's workspace); the one place that knows the precision of a cache
 template <class F>
 hipError_t with_carve(const qmha_kv_cache& c, F&& f) {
-    return c.variant == QMHA_FA_TC_INT8_B ? f(qmha::int8_carve(c.mem, c.B, c.cap, c.h_kv, c.D))
-                                          : f(qmha::f16_carve(c.mem, c.B, c.cap, c.h_kv, c.D));
+    const int slices = c.paged() ? c.num_pages : c.B, rows = c.paged() ? c.page_rows : c.cap;
+    return c.variant == QMHA_FA_TC_INT8_B ? f(qmha::int8_carve(c.mem, slices, rows, c.h_kv, c.D))
+                                          : f(qmha::f16_carve(c.mem, slices, rows, c.h_kv, c.D));
 }
 
 // One operation on a cache, after the checks that need no lock: `mu` held across check(len) -- the checks against the
@@ -555,6 +562,15 @@ int cache_enqueue(qmha_kv_cache* c, Marks ProfRec::*marks, void* stream, const c
     return st;
 }
 const auto kNoLenCheck = [](int) { return QMHA_OK; };
+
+// the entry points of one kind of cache refuse the other kind
+int check_cache_kind(const qmha_kv_cache* c, bool paged_call, const char* what) {
+    if (c->paged() == paged_call) return QMHA_OK;
+    return fail(QMHA_ERR_INVALID, std::string(what) + (paged_call ? ": the cache is contiguous (qmha_kv_cache_create): the paged entry points "
+                                                                    "need a cache of qmha_kv_cache_create_paged"
+                                                                  : ": the cache is paged (qmha_kv_cache_create_paged): use "
+                                                                    "qmha_kv_cache_append_paged / qmha_attend_cached_paged"));
+}
 
 }  // namespace
 
@@ -659,6 +675,7 @@ int qmha_kv_cache_len(const qmha_kv_cache_t* c) {
 
 int qmha_kv_cache_truncate(qmha_kv_cache_t* c, int len) {
     if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+    if (int ck = check_cache_kind(c, false, "truncate")) return ck;
     std::lock_guard<std::mutex> lk(c->mu);
     if (len < 0 || len % 32 != 0) return fail(QMHA_ERR_INVALID, "truncate: len must be a non-negative multiple of 32");
     if (len > c->len)
@@ -670,6 +687,7 @@ int qmha_kv_cache_truncate(qmha_kv_cache_t* c, int len) {
 
 int qmha_kv_cache_append(qmha_kv_cache_t* c, const float* K, const float* V, int n, void* stream) {
     if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+    if (int ck = check_cache_kind(c, false, "append")) return ck;
     if (!K || !V) return fail(QMHA_ERR_INVALID, "null tensor pointer");
     if (n < 32 || n % 32 != 0) return fail(QMHA_ERR_INVALID, "append: n must be a positive multiple of 32");
     return cache_enqueue(
@@ -690,6 +708,7 @@ int qmha_kv_cache_append(qmha_kv_cache_t* c, const float* K, const float* V, int
 
 int qmha_attend_cached(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, unsigned flags, void* stream) {
     if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+    if (int ck = check_cache_kind(c, false, "attend")) return ck;
     int D = 0;
     int st = check_shape(Q, Q, Q, O, c->B, Nq, c->d_model, c->h, c->variant, &D, "Nq");
     if (st == QMHA_OK) st = check_flag_bits(flags);
@@ -716,6 +735,7 @@ int qmha_attend_cached(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, uns
 // ---- per-sequence lengths read on the device: the host `len` is neither read nor changed ----
 int qmha_kv_cache_append_at(qmha_kv_cache_t* c, const float* K, const float* V, int n, const int32_t* pos, void* stream) {
     if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+    if (int ck = check_cache_kind(c, false, "append_at")) return ck;
     if (!K || !V) return fail(QMHA_ERR_INVALID, "null tensor pointer");
     if (!pos) return fail(QMHA_ERR_INVALID, "append_at: null pos (a device int32[B])");
     if (n < 32 || n % 32 != 0) return fail(QMHA_ERR_INVALID, "append_at: n must be a positive multiple of 32");
@@ -729,6 +749,7 @@ int qmha_kv_cache_append_at(qmha_kv_cache_t* c, const float* K, const float* V, 
 int qmha_attend_cached_varlen(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, const int32_t* lens, unsigned flags,
                               void* stream) {
     if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+    if (int ck = check_cache_kind(c, false, "attend_varlen")) return ck;
     int D = 0;
     int st = check_shape(Q, Q, Q, O, c->B, Nq, c->d_model, c->h, c->variant, &D, "Nq");
     if (st == QMHA_OK) st = check_flag_bits(flags);
@@ -766,6 +787,7 @@ int qmha_kv_cache_attach_tail(qmha_kv_cache_t* c, void* mem, size_t bytes) {
 
 int qmha_kv_cache_append_tokens(qmha_kv_cache_t* c, const float* K, const float* V, int n, const int32_t* pos, void* stream) {
     if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+    if (int ck = check_cache_kind(c, false, "append_tokens")) return ck;
     if (!K || !V) return fail(QMHA_ERR_INVALID, "null tensor pointer");
     if (!pos) return fail(QMHA_ERR_INVALID, "append_tokens: null pos (a device int32[B])");
     if (n < 1 || n > c->cap)
@@ -786,6 +808,7 @@ int qmha_kv_cache_append_tokens(qmha_kv_cache_t* c, const float* K, const float*
 int qmha_attend_cached_tokens(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, const int32_t* lens, unsigned flags,
                               void* stream) {
     if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+    if (int ck = check_cache_kind(c, false, "attend_tokens")) return ck;
     if (!Q || !O) return fail(QMHA_ERR_INVALID, "null tensor pointer");
     if (!lens) return fail(QMHA_ERR_INVALID, "attend_tokens: null lens (a device int32[B])");
     if (flags != QMHA_FLAG_CAUSAL)
@@ -794,6 +817,85 @@ int qmha_attend_cached_tokens(qmha_kv_cache_t* c, const float* Q, float* O, int 
         return fail(QMHA_ERR_INVALID, "attend_tokens: Nq = " + std::to_string(Nq) + " rows, needs 1 <= Nq <= cap = " + std::to_string(c->cap));
     return cache_enqueue(c, &ProfRec::main, stream, "kv_cache attend_tokens launch", kNoLenCheck, [&](const auto& w, int) {
         return qmha::launch_fa_masked(w, Q, O, {c->B, Nq, c->cap, c->h, c->h_kv, c->D, c->d_model, true, -1, lens, true},
+                                      (hipStream_t)stream);
+    });
+}
+
+// ---- paged caches: a pool of pages and a block table read on the device --------------------
+size_t qmha_kv_cache_paged_bytes(int num_pages, int page_rows, int d_model, int h, int h_kv, int variant) {
+    if (h < 1 || h_kv < 1 || d_model % h) return 0;
+    return qmha_workspace_size(num_pages, page_rows, h_kv * (d_model / h), h_kv, variant);  // the carve of num_pages slices of page_rows rows
+}
+
+int qmha_kv_cache_create_paged(qmha_kv_cache_t** out, void* mem, size_t bytes, int B, int num_pages, int page_rows, int max_pages,
+                               int d_model, int h, int h_kv, int variant) {
+    if (!out) return fail(QMHA_ERR_INVALID, "null cache handle pointer");
+    *out = nullptr;
+    if (!mem) return fail(QMHA_ERR_INVALID, "null cache memory");
+    if (page_rows < 64 || page_rows % 64 != 0)
+        return fail(QMHA_ERR_INVALID, "create_paged: page_rows = " + std::to_string(page_rows) +
+                                          " must be a positive multiple of 64 (a stage of two 32-row key tiles lies in one page)");
+    if (num_pages < 1) return fail(QMHA_ERR_INVALID, "create_paged: num_pages = " + std::to_string(num_pages) + " must be at least 1");
+    if (max_pages < 1) return fail(QMHA_ERR_INVALID, "create_paged: max_pages = " + std::to_string(max_pages) + " must be at least 1");
+    if ((long long)max_pages * page_rows > (1 << 30))
+        return fail(QMHA_ERR_INVALID, "create_paged: the logical capacity max_pages * page_rows exceeds 2^30 rows");
+    int D = 0;
+    int st = check_shape(mem, mem, mem, mem, B, page_rows, d_model, h, variant, &D, "page_rows");
+    if (st == QMHA_OK) st = check_kv_heads(h, h_kv);
+    if (st == QMHA_OK) st = not_built(h_kv < h ? kGroupedFeature : "the persistent K/V cache", variant, D);
+    if (st != QMHA_OK) return st;
+    if (reinterpret_cast<uintptr_t>(mem) % 256 != 0) return fail(QMHA_ERR_INVALID, "cache memory must be 256-byte aligned");
+    const size_t need = workspace_bytes(num_pages, page_rows, h_kv, D, variant);
+    if (bytes < need)
+        return fail(QMHA_ERR_INVALID, "cache memory too small: " + std::to_string(bytes) + " bytes, qmha_kv_cache_paged_bytes is " +
+                                          std::to_string(need));
+    qmha_kv_cache* c = new qmha_kv_cache;
+    c->mem = mem;
+    c->B = B, c->cap = max_pages * page_rows, c->d_model = d_model, c->h = h, c->D = D, c->variant = variant;
+    c->h_kv = h_kv;
+    c->len = 0;
+    c->num_pages = num_pages, c->page_rows = page_rows, c->max_pages = max_pages;
+    *out = c;
+    return QMHA_OK;
+}
+
+int qmha_kv_cache_append_paged(qmha_kv_cache_t* c, const float* K, const float* V, int n, const int32_t* pos, const int32_t* table,
+                               void* stream) {
+    if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+    if (int ck = check_cache_kind(c, true, "append_paged")) return ck;
+    if (!K || !V) return fail(QMHA_ERR_INVALID, "null tensor pointer");
+    if (!pos) return fail(QMHA_ERR_INVALID, "append_paged: null pos (a device int32[B])");
+    if (!table) return fail(QMHA_ERR_INVALID, "append_paged: null table (a device int32[B][max_pages])");
+    if (n < 1 || n > c->cap)
+        return fail(QMHA_ERR_INVALID, "append_paged: n = " + std::to_string(n) + " rows, needs 1 <= n <= cap = max_pages * page_rows = " +
+                                          std::to_string(c->cap));
+    return cache_enqueue(
+        c, &ProfRec::pre, stream, "kv_cache append_paged launch",
+        [&](int) {  // under the mutex: attach_tail writes `tail` under it
+            if (c->variant == QMHA_FA_TC_INT8_B && !c->tail)
+                return fail(QMHA_ERR_INVALID, "append_paged: an int8 cache needs its tail (qmha_kv_cache_attach_tail)");
+            return (int)QMHA_OK;
+        },
+        [&](const auto& w, int) {
+            return qmha::launch_kv_tokens(K, V, w, static_cast<float*>(c->tail), c->B, n, c->cap, pos, c->h_kv, c->D, c->h_kv * c->D,
+                                          (hipStream_t)stream, c->pages(table));
+        });
+}
+
+int qmha_attend_cached_paged(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, const int32_t* lens, const int32_t* table,
+                             unsigned flags, void* stream) {
+    if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+    if (int ck = check_cache_kind(c, true, "attend_paged")) return ck;
+    if (!Q || !O) return fail(QMHA_ERR_INVALID, "null tensor pointer");
+    if (!lens) return fail(QMHA_ERR_INVALID, "attend_paged: null lens (a device int32[B])");
+    if (!table) return fail(QMHA_ERR_INVALID, "attend_paged: null table (a device int32[B][max_pages])");
+    if (flags != QMHA_FLAG_CAUSAL)
+        return fail(QMHA_ERR_INVALID, "attend_paged: flags must be QMHA_FLAG_CAUSAL (the kernels have no mask but the diagonal)");
+    if (Nq < 1 || Nq > c->cap)
+        return fail(QMHA_ERR_INVALID, "attend_paged: Nq = " + std::to_string(Nq) + " rows, needs 1 <= Nq <= cap = max_pages * page_rows = " +
+                                          std::to_string(c->cap));
+    return cache_enqueue(c, &ProfRec::main, stream, "kv_cache attend_paged launch", kNoLenCheck, [&](const auto& w, int) {
+        return qmha::launch_fa_masked(w, Q, O, {c->B, Nq, c->cap, c->h, c->h_kv, c->D, c->d_model, true, -1, lens, true, c->pages(table)},
                                       (hipStream_t)stream);
     });
 }

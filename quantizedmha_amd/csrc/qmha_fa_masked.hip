@@ -6,7 +6,8 @@
 // whose sequences differ in length: the same body -- it is the text of
 // qmha_fa_masked_{int8,f16}.inc, included by every __global__ here -- over a geometry (Varlen) formed from a length
 // the kernel reads from device memory.  And the ragged kernels: that body once more, over
-// lengths and query counts that are no multiple of 32 (Ragged).
+// lengths and query counts that are no multiple of 32 (Ragged).  And the paged kernels: the ragged
+// call over a pool of pages, each stage's K/V found through a block table on the device (Paged).
 //
 // Square causal: query row r attends keys j <= r of its own sequence (Nq = Nk = N).  Both kernels keep the
 // geometry of the non-causal main kernels, so they consume the unchanged pre-pass outputs (qmha_prepass.hip):
@@ -178,16 +179,79 @@ struct Ragged : Varlen {
     }
     __host__ __device__ int units() const { return G * Ga; }
 };
+// A paged cache: Ragged's rows, queries and diagonal over a logical capacity Nk = max_pages * page_rows
+// whose rows lie in pages of a pool.  Row r of sequence b is row r % page_rows of page table[b][r / page_rows]; page p,
+// K/V head kvh is slice p * H + kvh of a carve at (num_pages, page_rows, H), so a page slice has the layout of a
+// contiguous slice of page_rows rows and the tile arithmetic does not change.  page_rows % 64 == 0: a stage of kSG = 2
+// tiles lies in one page.  The table is read on the device: the used entries are checked by every wave before the
+// workgroup's first barrier or DMA issue (used_pages_ok), and the entry a stage is issued with (entry) is clamped
+// into the pool, so no table content can become an address outside it.
+struct Paged : Ragged {
+    const int32_t* table;  // DEVICE int32 [B][max_pages]
+    int PG;                // 32-row groups of a page (even)
+    int max_pages, num_pages;
+    Paged(Ragged r, const int32_t* t, int page_rows, int mp, int np) : Ragged(r), table(t), PG(page_rows / QMHA_GROUP), max_pages(mp), num_pages(np) {}
+    __device__ Paged of(int L) const {
+        Paged v = *this;
+        static_cast<Ragged&>(v) = Ragged::of(L);
+        return v;
+    }
+    // every entry of the pages that the first L rows of sequence b use lies in [0, num_pages): lanes take the columns,
+    // a ballot joins them -- the same verdict in every wave.  Columns behind the used pages are not loaded.
+    __device__ bool used_pages_ok(int b, int L) const {
+        const int lane = threadIdx.x & 63;
+        bool bad = false;
+        for (int c = lane; c < max_pages; c += 64)
+            if (c * (PG * QMHA_GROUP) < L) bad |= (unsigned)table[(size_t)b * max_pages + c] >= (unsigned)num_pages;
+        return __builtin_amdgcn_ballot_w64(bad) == 0;
+    }
+    // column c of sequence b's table row, wave-uniform; the column and the id are clamped to the row and the pool.  Read
+    // through the constant address space -- no kernel writes a table --, which makes it a scalar load: a vector load
+    // would be waited for with vmcnt(0), together with the stage's DMA that was just issued.
+    __device__ int entry(int b, int c) const {
+        typedef const int32_t __attribute__((address_space(4))) * ConstI32;
+        const int e = *(ConstI32)(uintptr_t)(table + (size_t)b * max_pages + min(c, max_pages - 1));
+        return (int)min((unsigned)e, (unsigned)(num_pages - 1));
+    }
+};
+// The pages of a workgroup's stages in issue order (stage 0, 1, ... of a pass).  take(): page / tile0 / sip become those
+// of the stage about to be issued -- which is the stage computed next, so the id a stage computes with (sK / sV) is the
+// id it was issued with.  advance(), behind the DMA issue: `next`, the entry of the stage to issue after that, is loaded
+// a stage ahead of its use, so the scalar load does not stand in front of a DMA issue.
+struct PageWalk {
+    int col, sip_next, next;  // the next stage to issue: table column, stage within its page, entry
+    int page, tile0, sip;     // the stage issued last: page id, first tile of its page, stage within its page
+    __device__ __forceinline__ void start(const Paged& g, int b) {
+        col = 0, sip_next = 0;
+        next = g.entry(b, 0);
+    }
+    __device__ __forceinline__ void take(const Paged& g) { page = next, tile0 = col * g.PG, sip = sip_next; }
+    __device__ __forceinline__ void advance(const Paged& g, int b) {
+        if (++sip_next == g.PG / kSG) {
+            sip_next = 0;
+            next = g.entry(b, ++col);
+        }
+    }
+};
+struct NoWalk {};
+
 // A lane's row of Q / O in memory is its row of the (padded) block less row_shift; row_real: that row exists.
-// Constants for every geometry but Ragged, so the other instances carry no trace of them.
+// Constants for every geometry but Ragged (and Paged over it), so the other instances carry no trace of them.
 template <class Geo>
-constexpr bool kRaggedGeo = std::is_same<std::remove_cv_t<Geo>, Ragged>::value;
+constexpr bool kRaggedGeo = std::is_base_of<Ragged, std::remove_cv_t<Geo>>::value;
+template <class Geo>
+constexpr bool kPagedGeo = std::is_same<std::remove_cv_t<Geo>, Paged>::value;
+// a value of a type that depends on D: the bodies' `if constexpr` branches over a geometry are discarded unchecked
+template <int D, class T>
+__device__ __forceinline__ T as_dependent(T t) { return t; }
 template <class Geo>
 __device__ __forceinline__ constexpr int row_shift(const Geo&) { return 0; }
 template <class Geo>
 __device__ __forceinline__ constexpr bool row_real(const Geo&, int) { return true; }
 __device__ __forceinline__ int row_shift(const Ragged& g) { return g.s; }
 __device__ __forceinline__ bool row_real(const Ragged& g, int row) { return (unsigned)(row - g.s) < (unsigned)g.Nq; }
+__device__ __forceinline__ int row_shift(const Paged& g) { return g.s; }
+__device__ __forceinline__ bool row_real(const Paged& g, int row) { return (unsigned)(row - g.s) < (unsigned)g.Nq; }
 
 // A geometry that also carries the buffers of a dumping instance (int8 kernel; QkDump and PDump in
 // qmha_kernels.hpp): the debug hook's twin of a shipped instance, whose own arguments stay as they are.
@@ -313,7 +377,7 @@ __global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_f16_varle
         zero_unit_block<D>(O, any, bh_, H, d_model, qb_);
         return;
     }
-    const Varlen geo = any.of(L);
+    const auto geo = as_dependent<D>(any.of(L));
 #include "qmha_fa_masked_f16.inc"
 }
 
@@ -363,6 +427,43 @@ __global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_f16_ragge
 }
 
 // ---------------------------------------------------------------------------------------
+// Paged caches (Paged, above): the ragged prologue, then the scan of the table entries the sequence uses, over the same
+// bodies.  An invalid length or a used entry outside the pool: the sequence's Nq rows of O are zeros and none of its
+// K/V is read -- workgroup-uniform (every wave scans the same entries), before the body's first barrier or DMA issue.
+// The launch bounds are the ragged siblings'.
+// ---------------------------------------------------------------------------------------
+template <int D, class Geo = Paged>
+__global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : D > 32 ? 4 : 7) void qmha_fa_int8_paged_kernel(
+    const float* __restrict__ Qf, const int8_t* __restrict__ Ki, const _Float16* __restrict__ Vh,
+    const float* __restrict__ sK, const float* __restrict__ sV, float* __restrict__ O, Geo any,
+    const int32_t* __restrict__ lens, int H, int d_model, int nqb, float c_log2) {
+    int bh_, pi_;
+    masked_wg(nqb, bh_, pi_);  // the body forms the same pair again
+    const int L = lens[bh_ / H];
+    if (!any.valid(L) || !any.used_pages_ok(bh_ / H, L)) {
+        if (pi_ == 0) zero_real_rows<D>(O, any, bh_, H, d_model);
+        return;
+    }
+    const Geo geo = any.of(L);
+#include "qmha_fa_masked_int8.inc"
+}
+
+template <int D, class Geo = Paged>
+__global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_f16_paged_kernel(
+    const float* __restrict__ Qf, const _Float16* __restrict__ Kh, const _Float16* __restrict__ Vt,
+    float* __restrict__ O, Geo any, const int32_t* __restrict__ lens, int H, int d_model, int nqb, float c_log2) {
+    int bh_, qb_;
+    masked_wg_single(nqb, bh_, qb_);  // the body forms the same pair again
+    const int L = lens[bh_ / H];
+    if (!any.valid(L) || !any.used_pages_ok(bh_ / H, L)) {
+        if (qb_ == 0) zero_real_rows<D>(O, any, bh_, H, d_model);
+        return;
+    }
+    const Geo geo = any.of(L);
+#include "qmha_fa_masked_f16.inc"
+}
+
+// ---------------------------------------------------------------------------------------
 // host launchers (MaskedCall in qmha_kernels.hpp): per-sequence lengths take the varlen kernels, grouped calls
 // (Hkv < H) the Grouped instances, square causal calls of their own the SquareCausal ones, everything else Rect
 // ---------------------------------------------------------------------------------------
@@ -379,7 +480,7 @@ static int masked_nqb(int units) { return (units + kWaves - 1) / kWaves; }  // u
 // the units a grid is sized for: the geometry's own, or, where they follow a length on the device (Ragged), their most
 template <class Geo>
 static int grid_units(const Geo& geo) {
-    if constexpr (std::is_same<Geo, Ragged>::value) return geo.max_units();
+    if constexpr (std::is_base_of<Ragged, Geo>::value) return geo.max_units();
     else return geo.units();
 }
 
@@ -390,7 +491,14 @@ static hipError_t masked_geo(const MaskedCall& c, Launch&& launch) {
     if (c.B < 1 || c.Hkv < 1 || c.Hkv > c.H || c.H % c.Hkv != 0 || c.d_model != c.H * c.D) return hipErrorInvalidValue;
     if (c.ragged) {  // token-granular lengths: any 1 <= Nq <= cap, causal, lengths on the device
         if (!c.lens || !c.causal || c.Nq < 1 || c.Nk < QMHA_GROUP || c.Nk % QMHA_GROUP != 0 || c.Nq > c.Nk) return hipErrorInvalidValue;
-        return launch(Ragged(c.Nq, c.Nk, c.H / c.Hkv));
+        const Ragged r(c.Nq, c.Nk, c.H / c.Hkv);
+        const PageTable& p = c.pages;
+        if (!p.table) return launch(r);
+        // a paged cache: Nk is the logical capacity max_pages * page_rows (an int), w the pool's carve
+        if (p.page_rows < 2 * QMHA_GROUP || p.page_rows % (2 * QMHA_GROUP) != 0 || p.max_pages < 1 || p.num_pages < 1 ||
+            (long long)p.max_pages * p.page_rows != c.Nk)
+            return hipErrorInvalidValue;
+        return launch(Paged(r, p.table, p.page_rows, p.max_pages, p.num_pages));
     }
     const bool cached = !c.lens && c.len >= 0;
     if (!(cached ? cached_shape_ok(c.Nq, c.Nk, c.len, c.causal) : masked_shape_ok(c.Nq, c.Nk, c.causal))) return hipErrorInvalidValue;
@@ -407,7 +515,10 @@ static hipError_t fa_masked_launch(const Int8Workspace& w, const float* Qf, floa
     const int nqb = masked_nqb(grid_units(geo));
     const dim3 grid(c.B * c.Hkv * masked_pairs(nqb)), block(kWaves * 64);
     return int8_masked_d(c.D, [&](auto d) {
-        if constexpr (std::is_same<Geo, Ragged>::value)
+        if constexpr (std::is_same<Geo, Paged>::value)
+            hipLaunchKernelGGL((qmha_fa_int8_paged_kernel<decltype(d)::value>), grid, block, 0, stream, Qf, w.Ki, w.Vh, w.sK, w.sV, O,
+                               geo, c.lens, c.Hkv, c.d_model, nqb, softmax_scale_log2(c.D));
+        else if constexpr (std::is_same<Geo, Ragged>::value)
             hipLaunchKernelGGL((qmha_fa_int8_ragged_kernel<decltype(d)::value>), grid, block, 0, stream, Qf, w.Ki, w.Vh, w.sK, w.sV, O,
                                geo, c.lens, c.Hkv, c.d_model, nqb, softmax_scale_log2(c.D));
         else if constexpr (std::is_same<Geo, Varlen>::value)
@@ -425,7 +536,10 @@ static hipError_t fa_masked_launch(const F16Workspace& w, const float* Qf, float
     const int nqb = masked_nqb(grid_units(geo));
     const dim3 grid(c.B * c.Hkv * nqb), block(kWaves * 64);
     return f16_masked_d(c.D, [&](auto d) {
-        if constexpr (std::is_same<Geo, Ragged>::value)
+        if constexpr (std::is_same<Geo, Paged>::value)
+            hipLaunchKernelGGL((qmha_fa_f16_paged_kernel<decltype(d)::value>), grid, block, 0, stream, Qf, w.Kh, w.Vt, O, geo, c.lens,
+                               c.Hkv, c.d_model, nqb, softmax_scale_log2(c.D));
+        else if constexpr (std::is_same<Geo, Ragged>::value)
             hipLaunchKernelGGL((qmha_fa_f16_ragged_kernel<decltype(d)::value>), grid, block, 0, stream, Qf, w.Kh, w.Vt, O, geo, c.lens,
                                c.Hkv, c.d_model, nqb, softmax_scale_log2(c.D));
         else if constexpr (std::is_same<Geo, Varlen>::value)
@@ -455,6 +569,8 @@ QMHA_INSTANCE(Int8Workspace, Varlen)
 QMHA_INSTANCE(F16Workspace, Varlen)
 QMHA_INSTANCE(Int8Workspace, Ragged)
 QMHA_INSTANCE(F16Workspace, Ragged)
+QMHA_INSTANCE(Int8Workspace, Paged)
+QMHA_INSTANCE(F16Workspace, Paged)
 #undef QMHA_INSTANCE
 
 hipError_t launch_fa_masked(const Int8Workspace& w, const float* Qf, float* O, const MaskedCall& c, hipStream_t stream) {

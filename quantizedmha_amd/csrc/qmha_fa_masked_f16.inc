@@ -76,7 +76,19 @@
         const int d = w >> 2, cv = (w & 3) ^ vswz16(d);
         stg.voff[jj] = gq * 64 * D + d * 64 + 16 * cv;
     }
+    // Paged: the stage's page slice is the buffer (base formed in 64 bits, records of one page slice), the stage offset
+    // the stage's place in its page
+    std::conditional_t<kPagedGeo<decltype(geo)>, PageWalk, NoWalk> walk;
+    if constexpr (kPagedGeo<decltype(geo)>) walk.start(geo, b);
     auto issue = [&](int buf, int st) {
+        if constexpr (kPagedGeo<decltype(geo)>) {
+            walk.take(geo);
+            const size_t slice = (size_t)walk.page * H + kvh, pbytes = (size_t)geo.PG * (QMHA_GROUP * RB);
+            stg.issue(lds[buf], reinterpret_cast<const char*>(Kh) + slice * pbytes, (int)pbytes,
+                      reinterpret_cast<const char*>(Vt) + slice * pbytes, (int)pbytes, walk.sip,
+                      min(SG, wg_last + 1 - st * SG), wave);
+            walk.advance(geo, b);
+        } else
         stg.issue(lds[buf], kbase, Nk * RB, vbase, Nk * D * 2, st, min(SG, wg_last + 1 - st * SG), wave);
     };
     // S^T blocks [kb][qb] of tile gi: rows kap16(kb, .) of the K tile against query block qb

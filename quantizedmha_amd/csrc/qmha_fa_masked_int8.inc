@@ -95,6 +95,7 @@
     const char* vbase = reinterpret_cast<const char*>(Vh + (size_t)bh * Nk * D);
     const float* skb = sK + (size_t)bh * Gk;
     const float* svb = sV + (size_t)bh * Gk;
+    if constexpr (kPagedGeo<decltype(geo)>) skb = sK, svb = sV;  // bh is no slice of a pool: set per stage, below
 
     MaskedStager<WAVES, KCH, VCH, KBYTES, VBYTES, SG> stg;
 #pragma unroll
@@ -110,7 +111,19 @@
         const int d = w >> 2, cv = swz_src<64>(d, w & 3);
         stg.voff[jj] = grp * 64 * D + d * 64 + 16 * cv;
     }
+    // Paged: the stage's page slice is the buffer (base formed in 64 bits, records of one page slice), the stage offset
+    // the stage's place in its page; skb / svb follow the page a stage was issued with (the head of `stage` below)
+    std::conditional_t<kPagedGeo<decltype(geo)>, PageWalk, NoWalk> walk;
+    if constexpr (kPagedGeo<decltype(geo)>) walk.start(geo, b);
     auto issue = [&](int buf, int st) {
+        if constexpr (kPagedGeo<decltype(geo)>) {
+            walk.take(geo);
+            const size_t slice = (size_t)walk.page * H + kvh, pbytes = (size_t)geo.PG * (QMHA_GROUP * D);
+            stg.issue(lds[buf], reinterpret_cast<const char*>(Ki) + slice * pbytes, (int)pbytes,
+                      reinterpret_cast<const char*>(Vh) + slice * (2 * pbytes), (int)(2 * pbytes), walk.sip,
+                      min(SG, wg_last + 1 - st * SG), wave);
+            walk.advance(geo, b);
+        } else
         stg.issue(lds[buf], kbase, Nk * D, vbase, Nk * D * 2, st, min(SG, wg_last + 1 - st * SG), wave);
     };
 
@@ -210,6 +223,10 @@
     qmha_dma_barrier();  // waits vmcnt(0): stage 0 has landed
     auto stage = [&](auto BUF, int st) {
         constexpr int buf = decltype(BUF)::value;
+        if constexpr (kPagedGeo<decltype(geo)>) {  // the scales of the page this stage was issued with: skb[t] is its group t - tile0
+            const ptrdiff_t g0 = ((ptrdiff_t)walk.page * H + kvh) * geo.PG - walk.tile0;
+            skb = sK + g0, svb = sV + g0;
+        }
         if (st + 1 < nst) issue(buf ^ 1, st + 1);  // buf^1 was released by the previous barrier
         const int t0 = st * SG;
         if (t0 <= my_last) {  // wave-uniform

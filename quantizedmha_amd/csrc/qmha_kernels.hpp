@@ -181,7 +181,7 @@ hipError_t f16_masked_d(int D, F&& f) {
 // ---- masked main kernels (qmha_fa_masked.hip) ---------------------
 // One launch of the masked templates.  Q / O: [B, Nq, d_model = H * D].  w: the variant's carve over K / V of Hkv heads
 // and Nk rows -- the workspace of the non-causal paths, whose pre-pass ran unchanged with N = Nk, H = Hkv and
-// d_model = Hkv * D; Hkv < H (H % Hkv == 0) is grouped-query attention.  Nq, Nk multiples of 32.  Three modes:
+// d_model = Hkv * D; Hkv < H (H % Hkv == 0) is grouped-query attention.  Nq, Nk multiples of 32.  The modes:
 //   a call of its own (len < 0, lens null): all Nk rows.  causal: bottom-right aligned, row r attends keys
 //     j <= r + Nk - Nq (Nk >= Nq).  Hkv == H: SquareCausal when causal and Nq == Nk, else Rect; Hkv < H: Grouped.
 //   a K/V cache (len >= 0): Nk = cap, and `len` of the cap rows per slice are valid (len % 32 == 0).  causal: over the
@@ -195,14 +195,25 @@ hipError_t f16_masked_d(int D, F&& f) {
 //   token-granular lengths (ragged, with lens and causal): the ragged kernels.  Any 1 <= Nq <= Nk; sequence
 //     b, Nq <= lens[b] <= Nk, computes rows [s, s + Nq), s = (lens[b] - Nq) mod 32, of the per-sequence-length mode on a
 //     zero block of ceil32(s + Nq) rows holding Q there, at ceil32(lens[b]); any other lens[b]: its Nq rows of O are zeros.
+//   a paged cache (ragged, with a table): the paged kernels.  w is the carve of a pool of num_pages pages
+//     (B := num_pages, N := page_rows, H := Hkv), Nk the logical capacity max_pages * page_rows, and row r of sequence b lies
+//     in page table[b][r / page_rows] (DEVICE int32 [B][max_pages], read by the kernel) at row r % page_rows.  A valid
+//     sequence computes the bits of the token-granular mode on a contiguous cache holding its rows; lens[b] outside
+//     [Nq, Nk], or an entry of a page it uses outside [0, num_pages): its Nq rows of O are zeros, none of its K/V is read.
 // B * Hkv K/V slices per grid.  int8: d in {32, 64, 128}; fp16: d in {64, 128} (qmha_api.cpp's variant table).  A shape
 // or head count outside the above, d_model != H * D, an unbuilt d: hipErrorInvalidValue, nothing launched.
+// The block table of a paged cache (null table: a contiguous cache); page_rows % 64 == 0
+struct PageTable {
+    const int32_t* table = nullptr;
+    int page_rows = 0, max_pages = 0, num_pages = 0;
+};
 struct MaskedCall {
     int B, Nq, Nk, H, Hkv, D, d_model;
     bool causal;
     int len;
     const int32_t* lens;
     bool ragged = false;  // lens at token granularity (the ragged kernels): any 1 <= Nq <= Nk, causal only
+    PageTable pages = {};  // with ragged and a table: a paged cache (the paged kernels), Nk = max_pages * page_rows
 };
 hipError_t launch_fa_masked(const Int8Workspace& w, const float* Qf, float* O, const MaskedCall& c, hipStream_t stream);
 hipError_t launch_fa_masked(const F16Workspace& w, const float* Qf, float* O, const MaskedCall& c, hipStream_t stream);
@@ -226,11 +237,14 @@ hipError_t launch_kv_append(const float* K, const float* V, const F16Workspace& 
 // far, zero-padded.  tail: the int8 cache's raw fp32 rows of each sequence's open group, [2][B][32][d_model] (K, then V),
 // read for the rows ahead of pos[b] in its group and rewritten while the last group stays open; fp16 has none (ignored).
 // pos[b] < 0 or pos[b] + n > cap: that sequence writes nothing.  Bad host arguments: hipErrorInvalidValue.
+// pt with a table: w is the carve of a pool of pages, cap = max_pages * page_rows, and group g of sequence
+// b goes to group g % (page_rows / 32) of page table[b][g / (page_rows / 32)]; an entry of a touched page outside
+// [0, num_pages) is an invalid pos[b].  The tail stays per sequence.
 inline size_t kv_tail_bytes(int B, int H, int D) { return align_up((size_t)2 * B * 32 * H * D * sizeof(float), 256); }
 hipError_t launch_kv_tokens(const float* K, const float* V, const Int8Workspace& w, float* tail, int B, int n, int cap,
-                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream);
+                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream, const PageTable& pt = {});
 hipError_t launch_kv_tokens(const float* K, const float* V, const F16Workspace& w, float* tail, int B, int n, int cap,
-                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream);
+                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream, const PageTable& pt = {});
 
 // ---- FP32 (fa: scalar VALU kernel; fa_mfma: the same contract on v_mfma_f32_32x32x2_f32) -----
 hipError_t launch_fa_f32(const float* Q, const float* K, const float* V, float* O, int B, int N, int H, int D,

@@ -11,6 +11,8 @@
 //                           (qmha_kv_cache_append_at)
 //   qmha_kv_token_{int8,f16}_kernel   any number of rows at any row of a sequence: the open 32-row group is written
 //                           again from its raw rows (qmha_kv_cache_append_tokens)
+//   qmha_kv_paged_{int8,f16}_kernel   the token kernels' groups in the pages of a pool, found through a block table
+//                           on the device (qmha_kv_cache_append_paged)
 #include <atomic>
 
 #include "qmha_common.hpp"
@@ -252,6 +254,12 @@ __device__ __forceinline__ TokenItem token_item(const int32_t* __restrict__ pos,
     return it;
 }
 
+// The index of group g of slice bh in the cache's arrays: the token kernels' contiguous rows, the paged kernels' lookup
+struct ContiguousGroups {
+    int Gc;  // groups of a slice: cap / 32
+    __device__ __forceinline__ size_t operator()(int bh, int g) const { return (size_t)bh * Gc + g; }
+};
+
 // int8.  The open group's scale comes from the rows present (zero rows do not move an absmax), and the group is
 // quantised again from its raw rows whenever rows are added: `tail` ([2][B][32][H * D] fp32, K then V) keeps the raw
 // rows of each sequence's open group.  Row a of group g comes from the tail (a < p: rows of earlier token appends,
@@ -260,10 +268,10 @@ __device__ __forceinline__ TokenItem token_item(const int32_t* __restrict__ pos,
 // new rows written to the tail.  The wave that reads the tail (group g0) is the wave that rewrites it (group g1), and
 // its loads have returned before its first store (the absmax needs them): no other wave touches the (tensor,
 // sequence, head) columns of the tail.
-template <int D, bool ISV>
+template <int D, bool ISV, class Groups>
 __device__ __forceinline__ void token_groups_int8(const float* __restrict__ X, float* __restrict__ T, int8_t* __restrict__ Ki,
                                                   _Float16* __restrict__ Vh, float* __restrict__ sX, char* vtr,
-                                                  const TokenItem& it, int n, int Gc, int d_model) {
+                                                  const TokenItem& it, int n, const Groups& groups, int d_model) {
     constexpr int C4 = D / 4, RPI = 64 / C4, NI = 32 / RPI;
     const int lane = threadIdx.x & 63, p = it.p;
     // K: lane (ri, ci) holds rows i * RPI + ri; V: lane (rq, c4) holds the NI consecutive rows NI * rq + i
@@ -288,7 +296,7 @@ __device__ __forceinline__ void token_groups_int8(const float* __restrict__ X, f
         }
         const float sc = qmha_scale_from_absmax(wave_max64(amax));
         const float inv = 1.0f / sc;
-        const size_t gi = (size_t)it.bh * Gc + g;  // the group's index in the cache's arrays
+        const size_t gi = groups(it.bh, g);  // the group's index in the cache's arrays
         if constexpr (ISV) {
             vt_group_store<D, true>(vtr, x, inv, lane, reinterpret_cast<char*>(Vh) + gi * (size_t)(64 * D));
         } else {
@@ -325,18 +333,19 @@ __global__ __launch_bounds__(256) void qmha_kv_token_int8_kernel(
     const size_t src = (size_t)b * n * d_model + col, trow = (size_t)b * QMHA_GROUP * d_model + col;
     if (blockIdx.y == 1)
         token_groups_int8<D, true>(V + src, tail + (size_t)B * QMHA_GROUP * d_model + trow, Ki, Vh, sV, vtr[threadIdx.x >> 6], it, n,
-                                   cap / QMHA_GROUP, d_model);
+                                   ContiguousGroups{cap / QMHA_GROUP}, d_model);
     else
-        token_groups_int8<D, false>(K + src, tail + trow, Ki, Vh, sK, vtr[threadIdx.x >> 6], it, n, cap / QMHA_GROUP, d_model);
+        token_groups_int8<D, false>(K + src, tail + trow, Ki, Vh, sK, vtr[threadIdx.x >> 6], it, n, ContiguousGroups{cap / QMHA_GROUP},
+                                    d_model);
 }
 
 // fp16: a row converts on its own, so there is no tail.  A group this call opens (a group behind g0, or g0 when pos[b]
 // is a multiple of 32) is written whole, the rows behind the new ones as zeros -- masked P entries are 0, and 0 times a
 // stale inf would be NaN --, with the stores of qmha_kv_append_f16_kernel.  A group that earlier rows opened (g0
 // otherwise) gets the new rows only: their Kh rows, and their slots of the V^T block, two bytes each.
-template <int D, bool ISV>
+template <int D, bool ISV, class Groups>
 __device__ __forceinline__ void token_groups_f16(const float* __restrict__ X, _Float16* __restrict__ Kh, _Float16* __restrict__ Vt,
-                                                 char* vtr, const TokenItem& it, int n, int Gc, int d_model) {
+                                                 char* vtr, const TokenItem& it, int n, const Groups& groups, int d_model) {
     constexpr int C4 = D / 4, RPI = 64 / C4, NI = 32 / RPI;
     const int lane = threadIdx.x & 63, p = it.p;
     const int r0 = ISV ? (lane / C4) * NI : lane / C4, c4 = lane % C4;
@@ -345,7 +354,7 @@ __device__ __forceinline__ void token_groups_f16(const float* __restrict__ X, _F
     for (int pass = 0; pass < 2; ++pass) {
         if (pass == 1 && (it.j != 0 || it.g1 == it.g0)) break;
         const int g = pass == 0 ? it.g0 + it.j : it.g1;
-        const size_t gi = (size_t)it.bh * Gc + g;
+        const size_t gi = groups(it.bh, g);
         const int lo = p - g * QMHA_GROUP, hi = lo + n;  // the new rows of this group: lo <= r < hi
         const bool opens = lo <= 0;                       // a group behind g0, or g0 at a multiple of 32
         if (ISV && !opens) {  // the new rows' slots of the block: element (d, slot) of [D][32]
@@ -389,8 +398,85 @@ __global__ __launch_bounds__(256) void qmha_kv_token_f16_kernel(
     const TokenItem it = token_item(pos, n, cap, H, maxg, total);
     if (it.p < 0) return;  // wave-uniform; the LDS tile is per wave, no workgroup barrier follows
     const size_t src = (size_t)(it.bh / H) * n * d_model + (size_t)(it.bh % H) * D;
-    if (blockIdx.y == 1) token_groups_f16<D, true>(V + src, Kh, Vt, vtr[threadIdx.x >> 6], it, n, cap / QMHA_GROUP, d_model);
-    else token_groups_f16<D, false>(K + src, Kh, Vt, vtr[threadIdx.x >> 6], it, n, cap / QMHA_GROUP, d_model);
+    if (blockIdx.y == 1) token_groups_f16<D, true>(V + src, Kh, Vt, vtr[threadIdx.x >> 6], it, n, ContiguousGroups{cap / QMHA_GROUP}, d_model);
+    else token_groups_f16<D, false>(K + src, Kh, Vt, vtr[threadIdx.x >> 6], it, n, ContiguousGroups{cap / QMHA_GROUP}, d_model);
+}
+
+// ---------------------------------------------------------------------------------------
+// Paged append (qmha_kv_cache_append_paged): the token kernels' items, groups and tail protocol over a
+// pool of pages.  cap = max_pages * page_rows is the logical capacity; group g of sequence b, K/V head k is group
+// g % PG of slice page * H + k, page = table[b][g / PG], PG = page_rows / 32 -- the one thing that differs (PagedGroups).
+// A wave's item is decided as token_item decides it, and then the table entries of the pages that rows
+// [pos[b], pos[b] + n) touch are looked at by the wave's lanes: one outside [0, num_pages) and every item of the sequence
+// returns with nothing written, the tail included (each of them scans the same entries).  The tail belongs to the
+// sequence slot b, not to a page.
+// ---------------------------------------------------------------------------------------
+struct PagedTable {
+    const int32_t* table;  // DEVICE int32 [B][max_pages]
+    int PG, max_pages, num_pages;
+};
+// The pool indices of the (at most two) groups a wave's item runs, looked up once, ahead of the group loop: scalar
+// arithmetic (the item is per wave) that is over before a group's rows are held in registers.
+struct PagedGroups {
+    int g_last;             // it.g1: the group of the second pass, or of the only one
+    size_t first, last;     // the index of group it.g0 + it.j, and of group it.g1
+    __device__ __forceinline__ size_t operator()(int, int g) const { return g == g_last ? last : first; }
+};
+__device__ __forceinline__ TokenItem paged_item(const int32_t* __restrict__ pos, const PagedTable& t, int n, int H, int maxg, int total) {
+    TokenItem it = token_item(pos, n, t.max_pages * t.PG * QMHA_GROUP, H, maxg, total);
+    if (it.p < 0) return it;
+    const int32_t* row = t.table + (size_t)(it.bh / H) * t.max_pages;
+    const int c0 = (unsigned)it.g0 / (unsigned)t.PG, c1 = (unsigned)it.g1 / (unsigned)t.PG;  // <= max_pages - 1: p + n <= cap
+    bool bad = false;
+    for (int c = c0 + (threadIdx.x & 63); c <= c1; c += 64) bad |= (unsigned)row[c] >= (unsigned)t.num_pages;
+    if (__builtin_amdgcn_ballot_w64(bad)) it.p = -1;
+    // the item is per wave: in scalar registers the page arithmetic costs the int8 d = 32 kernel no occupancy step
+    it.bh = __builtin_amdgcn_readfirstlane(it.bh), it.j = __builtin_amdgcn_readfirstlane(it.j), it.p = __builtin_amdgcn_readfirstlane(it.p);
+    it.g0 = __builtin_amdgcn_readfirstlane(it.g0), it.g1 = __builtin_amdgcn_readfirstlane(it.g1);
+    return it;
+}
+
+__device__ __forceinline__ PagedGroups paged_groups(const PagedTable& t, const TokenItem& it, int H) {
+    const int32_t* row = t.table + (size_t)(it.bh / H) * t.max_pages;
+    auto index = [&](int g) {
+        const unsigned c = (unsigned)g / (unsigned)t.PG;
+        // valid (paged_item); clamped all the same, so that no table content leaves the pool
+        const unsigned page = min((unsigned)__builtin_amdgcn_readfirstlane(row[c]), (unsigned)(t.num_pages - 1));
+        return ((size_t)page * H + (unsigned)(it.bh % H)) * t.PG + ((unsigned)g - c * (unsigned)t.PG);
+    };
+    return {it.g1, index(it.g0 + it.j), index(it.g1)};
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void qmha_kv_paged_int8_kernel(
+    const float* __restrict__ K, const float* __restrict__ V, int8_t* __restrict__ Ki, _Float16* __restrict__ Vh,
+    float* __restrict__ sK, float* __restrict__ sV, float* __restrict__ tail, int B, int n, const int32_t* __restrict__ pos,
+    PagedTable t, int H, int d_model, int maxg, int total) {
+    __shared__ __attribute__((aligned(16))) char vtr[4][D * QMHA_VT_PITCH];
+    const TokenItem it = paged_item(pos, t, n, H, maxg, total);
+    if (it.p < 0) return;  // wave-uniform; the LDS tile is per wave, no workgroup barrier follows
+    const int b = it.bh / H, k = it.bh % H;
+    const PagedGroups groups = paged_groups(t, it, H);
+    const size_t col = (size_t)k * D + 4 * ((threadIdx.x & 63) % (D / 4));  // this lane's columns of a row
+    const size_t src = (size_t)b * n * d_model + col, trow = (size_t)b * QMHA_GROUP * d_model + col;
+    if (blockIdx.y == 1)
+        token_groups_int8<D, true>(V + src, tail + (size_t)B * QMHA_GROUP * d_model + trow, Ki, Vh, sV, vtr[threadIdx.x >> 6], it, n,
+                                   groups, d_model);
+    else
+        token_groups_int8<D, false>(K + src, tail + trow, Ki, Vh, sK, vtr[threadIdx.x >> 6], it, n, groups, d_model);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void qmha_kv_paged_f16_kernel(
+    const float* __restrict__ K, const float* __restrict__ V, _Float16* __restrict__ Kh, _Float16* __restrict__ Vt,
+    int n, const int32_t* __restrict__ pos, PagedTable t, int H, int d_model, int maxg, int total) {
+    __shared__ __attribute__((aligned(16))) char vtr[4][D * QMHA_VT_PITCH];
+    const TokenItem it = paged_item(pos, t, n, H, maxg, total);
+    if (it.p < 0) return;  // wave-uniform; the LDS tile is per wave, no workgroup barrier follows
+    const PagedGroups groups = paged_groups(t, it, H);
+    const size_t src = (size_t)(it.bh / H) * n * d_model + (size_t)(it.bh % H) * D;
+    if (blockIdx.y == 1) token_groups_f16<D, true>(V + src, Kh, Vt, vtr[threadIdx.x >> 6], it, n, groups, d_model);
+    else token_groups_f16<D, false>(K + src, Kh, Vt, vtr[threadIdx.x >> 6], it, n, groups, d_model);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -888,11 +974,23 @@ static bool kv_tokens_shape_ok(int B, int n, int cap, const int32_t* pos, int H)
     return B >= 1 && H >= 1 && pos && n >= 1 && cap >= QMHA_GROUP && cap % QMHA_GROUP == 0 && n <= cap;
 }
 
+// a paged call: cap is the table's logical capacity and w the pool's carve at (num_pages, page_rows)
+static bool kv_pages_ok(const PageTable& pt, int cap) {
+    return !pt.table || (pt.page_rows >= 2 * QMHA_GROUP && pt.page_rows % (2 * QMHA_GROUP) == 0 && pt.max_pages >= 1 && pt.num_pages >= 1 &&
+                         (long long)pt.max_pages * pt.page_rows == cap);
+}
+
 hipError_t launch_kv_tokens(const float* K, const float* V, const Int8Workspace& w, float* tail, int B, int n, int cap,
-                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream) {
-    if (!kv_tokens_shape_ok(B, n, cap, pos, H) || !tail) return hipErrorInvalidValue;
+                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream, const PageTable& pt) {
+    if (!kv_tokens_shape_ok(B, n, cap, pos, H) || !tail || !kv_pages_ok(pt, cap)) return hipErrorInvalidValue;
     const int maxg = token_items(n), total = B * H * maxg;
     return int8_masked_d(D, [&](auto d) {
+        if (pt.table) {
+            hipLaunchKernelGGL((qmha_kv_paged_int8_kernel<decltype(d)::value>), dim3((total + 3) / 4, 2), dim3(256), 0, stream, K, V, w.Ki,
+                               w.Vh, w.sK, w.sV, tail, B, n, pos, PagedTable{pt.table, pt.page_rows / QMHA_GROUP, pt.max_pages, pt.num_pages},
+                               H, d_model, maxg, total);
+            return hipGetLastError();
+        }
         hipLaunchKernelGGL((qmha_kv_token_int8_kernel<decltype(d)::value>), dim3((total + 3) / 4, 2), dim3(256), 0, stream, K, V, w.Ki,
                            w.Vh, w.sK, w.sV, tail, B, n, cap, pos, H, d_model, maxg, total);
         return hipGetLastError();
@@ -900,10 +998,16 @@ hipError_t launch_kv_tokens(const float* K, const float* V, const Int8Workspace&
 }
 
 hipError_t launch_kv_tokens(const float* K, const float* V, const F16Workspace& w, float*, int B, int n, int cap,
-                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream) {
-    if (!kv_tokens_shape_ok(B, n, cap, pos, H)) return hipErrorInvalidValue;
+                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream, const PageTable& pt) {
+    if (!kv_tokens_shape_ok(B, n, cap, pos, H) || !kv_pages_ok(pt, cap)) return hipErrorInvalidValue;
     const int maxg = token_items(n), total = B * H * maxg;
     return f16_masked_d(D, [&](auto d) {
+        if (pt.table) {
+            hipLaunchKernelGGL((qmha_kv_paged_f16_kernel<decltype(d)::value>), dim3((total + 3) / 4, 2), dim3(256), 0, stream, K, V, w.Kh,
+                               w.Vt, n, pos, PagedTable{pt.table, pt.page_rows / QMHA_GROUP, pt.max_pages, pt.num_pages}, H, d_model, maxg,
+                               total);
+            return hipGetLastError();
+        }
         hipLaunchKernelGGL((qmha_kv_token_f16_kernel<decltype(d)::value>), dim3((total + 3) / 4, 2), dim3(256), 0, stream, K, V, w.Kh,
                            w.Vt, n, cap, pos, H, d_model, maxg, total);
         return hipGetLastError();

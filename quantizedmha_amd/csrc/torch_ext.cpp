@@ -20,6 +20,8 @@
 //     kernels read (qmha_kv_cache_append_at / qmha_attend_cached_varlen);
 //   * both caches' `enable_tokens` / `append_tokens` / `attend_tokens`: the same at any length -- any number of rows at any
 //     row, any Nq, causal (qmha_kv_cache_attach_tail / qmha_kv_cache_append_tokens / qmha_attend_cached_tokens);
+//   * `PagedKVCache`: a pool of pages and a caller-owned block table on the device, `append_paged` / `attend_paged`
+//     (qmha_kv_cache_create_paged / qmha_kv_cache_append_paged / qmha_attend_cached_paged);
 //   * a rejected shape raises (TORCH_CHECK on the C-ABI status) instead of a device assert.
 #include <torch/extension.h>
 // ROCm PyTorch reports HIP devices as device type "cuda": the guard / current-stream
@@ -144,6 +146,26 @@ static Tensor flash_solve_gqa(const Tensor& Q, const Tensor& K, const Tensor& V,
     return solve_rect(Q, K, V, d_model, num_heads, num_kv_heads, kernel, causal, "flash_solve_gqa");
 }
 
+// What the cache classes ask of their tensors.
+// a per-sequence int32 [B] tensor on the cache's device, contiguous: the kernel reads it, the host does not
+static void cache_per_seq(const Tensor& t, const char* name, int64_t B, const c10::Device& device) {
+    TORCH_CHECK(t.is_cuda(), name, " must be a CUDA tensor");
+    TORCH_CHECK(t.dtype() == torch::kInt32, name, " must be int32");
+    TORCH_CHECK(t.device() == device, name, " must be on the cache's device");
+    TORCH_CHECK(t.dim() == 1 && t.size(0) == B && t.is_contiguous(), name, " must be a contiguous tensor of shape [B = ", B, "]");
+}
+// [B, n, d_model] fp32 on the cache's device, contiguous; [n, d_model] for B = 1
+static Tensor cache_rows(const Tensor& X, const char* name, int64_t width, int64_t B, const c10::Device& device) {
+    TORCH_CHECK(X.is_cuda(), "Inputs must be CUDA tensors");
+    TORCH_CHECK(X.dtype() == torch::kFloat32, name, " must be float32");
+    TORCH_CHECK(X.device() == device, name, " must be on the cache's device");
+    auto Xc = X.contiguous();
+    if (Xc.dim() == 2 && B == 1) Xc = Xc.unsqueeze(0);
+    TORCH_CHECK(Xc.dim() == 3 && Xc.size(0) == B && Xc.size(2) == width, name, " must be [B = ", B, ", n, d_model = ", width, "]",
+                B == 1 ? " or [n, d_model]" : "");
+    return Xc;
+}
+
 // A persistent quantised K/V cache (qmha_kv_cache_*): the compiled form of quantizedmha_amd/torch_ext.py's KVCache.
 // Owns a uint8 tensor of qmha_kv_cache_bytes and the host handle; append / attend run on PyTorch's current stream.
 class KVCache {
@@ -261,25 +283,8 @@ public:
     }
 
 private:
-    // a per-sequence int32 [B] tensor on the cache's device, contiguous: the kernel reads it, the host does not
-    void per_seq(const Tensor& t, const char* name) const {
-        TORCH_CHECK(t.is_cuda(), name, " must be a CUDA tensor");
-        TORCH_CHECK(t.dtype() == torch::kInt32, name, " must be int32");
-        TORCH_CHECK(t.device() == mem_.device(), name, " must be on the cache's device");
-        TORCH_CHECK(t.dim() == 1 && t.size(0) == B_ && t.is_contiguous(), name, " must be a contiguous tensor of shape [B = ", B_,
-                    "]");
-    }
-    // [B, n, d_model] fp32 on the cache's device, contiguous; [n, d_model] for B = 1
-    Tensor rows(const Tensor& X, const char* name, int64_t width) const {
-        TORCH_CHECK(X.is_cuda(), "Inputs must be CUDA tensors");
-        TORCH_CHECK(X.dtype() == torch::kFloat32, name, " must be float32");
-        TORCH_CHECK(X.device() == mem_.device(), name, " must be on the cache's device");
-        auto Xc = X.contiguous();
-        if (Xc.dim() == 2 && B_ == 1) Xc = Xc.unsqueeze(0);
-        TORCH_CHECK(Xc.dim() == 3 && Xc.size(0) == B_ && Xc.size(2) == width, name, " must be [B = ", B_, ", n, d_model = ",
-                    width, "]", B_ == 1 ? " or [n, d_model]" : "");
-        return Xc;
-    }
+    void per_seq(const Tensor& t, const char* name) const { cache_per_seq(t, name, B_, mem_.device()); }
+    Tensor rows(const Tensor& X, const char* name, int64_t width) const { return cache_rows(X, name, width, B_, mem_.device()); }
     int64_t B_, cap_, d_model_, kv_model_;
     std::string kernel_;
     Tensor mem_, tail_;
@@ -294,7 +299,106 @@ public:
         : KVCache(B, cap, d_model, num_heads, kernel, device, num_kv_heads) {}
 };
 
+// A paged K/V cache (qmha_kv_cache_create_paged): the compiled form of quantizedmha_amd/torch_ext.py's PagedKVCache.  Owns
+// the pool (a uint8 tensor of qmha_kv_cache_paged_bytes) and the host handle; the block table is the caller's tensor.
+class PagedKVCache {
+public:
+    PagedKVCache(int64_t B, int64_t num_pages, int64_t page_rows, int64_t max_pages, int64_t d_model, int64_t num_heads,
+                 std::optional<int64_t> num_kv_heads, const std::string& kernel, const std::string& device)
+        : B_(B), max_pages_(max_pages), cap_(max_pages * page_rows), d_model_(d_model), kv_model_(d_model), kernel_(kernel) {
+        const int variant = qmha_variant_from_name(kernel.c_str());
+        TORCH_CHECK(variant >= 0, "PagedKVCache: unknown kernel '", kernel, "'");
+        c10::Device dev(device);
+        TORCH_CHECK(dev.is_cuda(), "PagedKVCache needs a CUDA device");
+        const int64_t h_kv = num_kv_heads ? *num_kv_heads : num_heads;
+        if (num_heads > 0 && d_model % num_heads == 0) kv_model_ = h_kv * (d_model / num_heads);  // a bad head count: the library's checks
+        const size_t bytes = qmha_kv_cache_paged_bytes(static_cast<int>(num_pages), static_cast<int>(page_rows), static_cast<int>(d_model),
+                                                       static_cast<int>(num_heads), static_cast<int>(h_kv), variant);
+        mem_ = torch::zeros({static_cast<int64_t>(bytes > 0 ? bytes : 1)}, torch::TensorOptions().dtype(torch::kUInt8).device(dev));
+        const int st = qmha_kv_cache_create_paged(&handle_, mem_.data_ptr(), bytes, static_cast<int>(B), static_cast<int>(num_pages),
+                                                  static_cast<int>(page_rows), static_cast<int>(max_pages), static_cast<int>(d_model),
+                                                  static_cast<int>(num_heads), static_cast<int>(h_kv), variant);
+        TORCH_CHECK(st == QMHA_OK, "PagedKVCache", "(", kernel, "): ", qmha_status_string(st), ": ", qmha_last_error());
+    }
+    ~PagedKVCache() { qmha_kv_cache_destroy(handle_); }
+    PagedKVCache(const PagedKVCache&) = delete;
+    PagedKVCache& operator=(const PagedKVCache&) = delete;
+
+    int64_t cap() const { return cap_; }
+    Tensor mem() const { return mem_; }
+    std::optional<Tensor> tail() const { return tail_.defined() ? std::optional<Tensor>(tail_) : std::nullopt; }
+
+    // allocate and attach the tail of raw rows append_paged needs (int8); once, outside a capture
+    void enable_tokens() {
+        if (tail_.defined()) return;
+        const size_t bytes = qmha_kv_cache_tail_bytes(handle_);
+        tail_ = torch::zeros({static_cast<int64_t>(bytes > 0 ? bytes : 1)}, torch::TensorOptions().dtype(torch::kUInt8).device(mem_.device()));
+        const int st = qmha_kv_cache_attach_tail(handle_, tail_.data_ptr(), bytes);
+        TORCH_CHECK(st == QMHA_OK, "PagedKVCache.enable_tokens", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+    }
+
+    // append_tokens through the block table (qmha_kv_cache_append_paged)
+    void append_paged(const Tensor& K, const Tensor& V, const Tensor& pos, const Tensor& table) {
+        auto Kc = cache_rows(K, "K", kv_model_, B_, mem_.device()), Vc = cache_rows(V, "V", kv_model_, B_, mem_.device());
+        TORCH_CHECK(Kc.sizes() == Vc.sizes(), "K and V must have the same shape");
+        cache_per_seq(pos, "pos", B_, mem_.device());
+        check_table(table);
+        const OnStream on = current_stream(mem_.device());
+        const int st = qmha_kv_cache_append_paged(handle_, Kc.data_ptr<float>(), Vc.data_ptr<float>(), static_cast<int>(Kc.size(1)),
+                                                  pos.data_ptr<int32_t>(), table.data_ptr<int32_t>(), on.stream);
+        TORCH_CHECK(st == QMHA_OK, "PagedKVCache.append_paged", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+    }
+
+    // attend_tokens through the block table (qmha_attend_cached_paged)
+    Tensor attend_paged(const Tensor& Q, const Tensor& lens, const Tensor& table, std::optional<Tensor> out_opt) {
+        auto Qc = cache_rows(Q, "Q", d_model_, B_, mem_.device());
+        cache_per_seq(lens, "lens", B_, mem_.device());
+        check_table(table);
+        Tensor out = out_for(out_opt, Qc);
+        const OnStream on = current_stream(mem_.device());
+        const int st = qmha_attend_cached_paged(handle_, Qc.data_ptr<float>(), out.data_ptr<float>(), static_cast<int>(Qc.size(1)),
+                                                lens.data_ptr<int32_t>(), table.data_ptr<int32_t>(), QMHA_FLAG_CAUSAL, on.stream);
+        TORCH_CHECK(st == QMHA_OK, "PagedKVCache.attend_paged", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+        return out_opt ? out : out.view(Q.sizes());
+    }
+
+private:
+    // the block table: int32 [B, max_pages] on the cache's device, contiguous: the kernel reads it, the host does not
+    void check_table(const Tensor& t) const {
+        TORCH_CHECK(t.is_cuda(), "table must be a CUDA tensor");
+        TORCH_CHECK(t.dtype() == torch::kInt32, "table must be int32");
+        TORCH_CHECK(t.device() == mem_.device(), "table must be on the cache's device");
+        TORCH_CHECK(t.dim() == 2 && t.size(0) == B_ && t.size(1) == max_pages_ && t.is_contiguous(),
+                    "table must be a contiguous tensor of shape [B = ", B_, ", max_pages = ", max_pages_, "]");
+    }
+    int64_t B_, max_pages_, cap_, d_model_, kv_model_;
+    std::string kernel_;
+    Tensor mem_, tail_;
+    qmha_kv_cache_t* handle_ = nullptr;
+};
+
 PYBIND11_MODULE(torch_ext, m) {
+    pybind11::class_<PagedKVCache>(m, "PagedKVCache",
+                                   "Paged K/V cache (HIP, MI355X): a pool of num_pages pages of page_rows rows and a caller-owned int32\n"
+                                   "[B, max_pages] block table on the device; append_paged / attend_paged are append_tokens /\n"
+                                   "attend_tokens with the row looked up through the table.")
+        .def(pybind11::init<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, std::optional<int64_t>, const std::string&,
+                            const std::string&>(),
+             pybind11::arg("B"), pybind11::arg("num_pages"), pybind11::arg("page_rows"), pybind11::arg("max_pages"), pybind11::arg("d_model"),
+             pybind11::arg("num_heads"), pybind11::arg("num_kv_heads") = pybind11::none(), pybind11::arg("kernel") = "fa_tc_int8_b",
+             pybind11::arg("device") = "cuda")
+        .def("enable_tokens", &PagedKVCache::enable_tokens,
+             "allocate and attach the tail of raw rows append_paged needs (int8); once, outside a graph capture.")
+        .def("append_paged", &PagedKVCache::append_paged, pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("pos"),
+             pybind11::arg("table"),
+             "append_tokens through the table: sequence b's n >= 1 rows go to logical rows [pos[b], pos[b] + n); an invalid pos[b]\n"
+             "or a touched table entry outside [0, num_pages) writes nothing for that sequence.")
+        .def("attend_paged", &PagedKVCache::attend_paged, pybind11::arg("Q"), pybind11::arg("lens"), pybind11::arg("table"),
+             pybind11::arg("out") = pybind11::none(),
+             "attend_tokens through the table; an invalid lens[b] or a used table entry outside [0, num_pages) gives zeros.")
+        .def_property_readonly("tail", &PagedKVCache::tail)
+        .def_property_readonly("cap", &PagedKVCache::cap)
+        .def_property_readonly("mem", &PagedKVCache::mem);
     pybind11::class_<KVCache>(m, "KVCache",
                               "Persistent quantised K/V cache (HIP, MI355X): append(K, V) pre-passes new rows into place,\n"
                               "attend(Q, causal=True) attends the last Nq positions over the cached rows.")

@@ -349,6 +349,94 @@ class GroupedKVCache(KVCache):
         self._setup(B, cap, d_model, num_heads, num_kv_heads, kernel, device)
 
 
+class PagedKVCache:
+    """A paged K/V cache (qmha_kv_cache_create_paged): `.mem` is a pool of num_pages pages of page_rows rows of all
+    num_kv_heads K/V heads (page_rows % 64 == 0), and an int32 [B, max_pages] block table on the device -- the caller's,
+    passed with every call and read by the kernels when they run -- says in which page each page_rows rows of a
+    sequence live: row r of sequence b is row r % page_rows of page table[b, r // page_rows].
+
+        cache = PagedKVCache(B, num_pages, page_rows, max_pages, d_model, num_heads)
+        cache.enable_tokens()
+        cache.append_paged(K, V, pos, table)                 # K, V [B, n, num_kv_heads * d], any n >= 1
+        O = cache.attend_paged(Q, lens, table)               # Q [B, Nq, d_model], any Nq >= 1, causal
+
+    The calls are append_tokens / attend_tokens of a contiguous cache with the row looked up, bit for bit.  A sequence
+    whose pos / lens is out of range, or that uses a table entry outside [0, num_pages), writes nothing / gets zeros;
+    entries behind the pages a call uses are not looked at.  Two sequences may name one page in an attend (a shared
+    prefix); two sequences writing one page in one append is the caller's error."""
+
+    def __init__(self, B: int, num_pages: int, page_rows: int, max_pages: int, d_model: int, num_heads: int,
+                 num_kv_heads: Optional[int] = None, kernel: str = _lib.DEFAULT_KERNEL, device="cuda"):
+        self.B, self.num_pages, self.page_rows, self.max_pages = int(B), int(num_pages), int(page_rows), int(max_pages)
+        self.d_model, self.num_heads, self.kernel = int(d_model), int(num_heads), kernel
+        self.num_kv_heads = self.num_heads if num_kv_heads is None else int(num_kv_heads)
+        self.cap = self.max_pages * self.page_rows  # a sequence's logical capacity
+        self.kv_model = self.d_model  # row width of K and V (a bad head count is left to the library's checks)
+        if self.num_heads > 0 and self.d_model % self.num_heads == 0:
+            self.kv_model = self.num_kv_heads * (self.d_model // self.num_heads)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("PagedKVCache needs a CUDA device")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        lib = _lib.load()
+        vid = _lib.variant_id(kernel)
+        self._handle = None
+        self.tail = None  # enable_tokens()
+        nbytes = lib.qmha_kv_cache_paged_bytes(self.num_pages, self.page_rows, self.d_model, self.num_heads, self.num_kv_heads, vid)
+        self.mem = torch.zeros(max(nbytes, 1), dtype=torch.uint8, device=self.device)
+        handle = ctypes.c_void_p()
+        st = lib.qmha_kv_cache_create_paged(ctypes.byref(handle), self.mem.data_ptr(), nbytes, self.B, self.num_pages, self.page_rows,
+                                            self.max_pages, self.d_model, self.num_heads, self.num_kv_heads, vid)
+        _lib.check(st, f"PagedKVCache({kernel})")
+        self._handle = handle
+
+    __del__ = KVCache.__del__
+    _rows = KVCache._rows
+    _per_seq = KVCache._per_seq
+    enable_tokens = KVCache.enable_tokens
+
+    def _table(self, t: torch.Tensor) -> torch.Tensor:
+        """The block table: int32 [B, max_pages] on the cache's device, read by the kernel when it runs (not by the host)."""
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("table must be a CUDA tensor")
+        if t.dtype != torch.int32:
+            raise RuntimeError("table must be int32")
+        if t.device != self.device:
+            raise RuntimeError(f"table must be on the cache's device {self.device}")
+        if t.dim() != 2 or tuple(t.shape) != (self.B, self.max_pages) or not t.is_contiguous():
+            raise RuntimeError(f"table must be a contiguous tensor of shape [B = {self.B}, max_pages = {self.max_pages}]")
+        return t
+
+    def append_paged(self, K: torch.Tensor, V: torch.Tensor, pos: torch.Tensor, table: torch.Tensor) -> None:
+        """append_tokens through the table (qmha_kv_cache_append_paged): sequence b's n >= 1 rows go to logical rows
+        [pos[b], pos[b] + n).  pos: int32 [B], table: int32 [B, max_pages], both on the device and read by the kernel --
+        the tensors themselves, so a captured call follows later changes of them.  A sequence whose pos[b] is negative
+        or beyond cap - n, or whose touched pages have an entry outside [0, num_pages), writes nothing.  Needs
+        enable_tokens() on an int8 cache."""
+        Kc, Vc = self._rows(K, "K", self.kv_model), self._rows(V, "V", self.kv_model)
+        if Kc.shape != Vc.shape:
+            raise RuntimeError("K and V must have the same shape")
+        pos, table = self._per_seq(pos, "pos"), self._table(table)
+        with _current_stream(self.device) as stream:
+            st = _lib.load().qmha_kv_cache_append_paged(self._handle, Kc.data_ptr(), Vc.data_ptr(), Kc.shape[1], pos.data_ptr(),
+                                                        table.data_ptr(), stream)
+        _lib.check(st, f"PagedKVCache.append_paged({self.kernel})")
+
+    def attend_paged(self, Q: torch.Tensor, lens: torch.Tensor, table: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """attend_tokens through the table (qmha_attend_cached_paged): row r of sequence b attends its logical rows
+        j <= r + (lens[b] - Nq).  A sequence whose lens[b] is below Nq or above cap, or whose used pages have an entry
+        outside [0, num_pages), gets zeros."""
+        Qc = self._rows(Q, "Q")
+        lens, table = self._per_seq(lens, "lens"), self._table(table)
+        out = _out_for(out, Qc, "size")
+        with _current_stream(self.device) as stream:
+            st = _lib.load().qmha_attend_cached_paged(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[1], lens.data_ptr(),
+                                                      table.data_ptr(), _lib.QMHA_FLAG_CAUSAL, stream)
+        _lib.check(st, f"PagedKVCache.attend_paged({self.kernel})")
+        return out.view(Q.shape) if out.numel() == Q.numel() and out.dim() != Q.dim() else out
+
+
 def quantize_int8(X: torch.Tensor, d_model: int, num_heads: int, layout: int = 0):
     """The INT8 pre-pass as an op: per-32-row-group symmetric int8 of every head.
 

@@ -313,6 +313,45 @@ int qmha_kv_cache_append_paged(qmha_kv_cache_t *c, const float *K, const float *
 int qmha_attend_cached_paged(qmha_kv_cache_t *c, const float *Q, float *O, int Nq, const int32_t *lens, const int32_t *table,
                              unsigned flags, void *stream);
 
+/*
+ * Split-KV -- attend_tokens / attend_paged with the key sweep cut into chunks, for a decode step (small Nq, long
+ * sequences), where the unsplit call runs one wave per head along the whole sequence.  Everything the two calls above
+ * state holds: device lens and table, any 1 <= Nq <= cap, causal only, the validity rules, multi-head and grouped caches.
+ * The result is a deterministic function of its own, inside the same accuracy contract; it is not the
+ * unsplit call's bits.
+ *
+ *   chunk_rows     key rows per chunk: a multiple of 64 with 64 <= chunk_rows <= cap, so C = chunk_rows / 32 tiles are a
+ *                  whole number of two-tile stages (and never cut a page's stage).  NC = ceil(cap / chunk_rows) chunks.
+ *   partial        first launch.  For sequence b, 32-row query group qg (the padded groups of the token-granular contract)
+ *                  and every chunk c with c * C <= last(qg), one wave runs the tiles c * C ... min(c * C + C - 1, last(qg))
+ *                  of the unsplit kernel from the zero state and ends with its epilogue: it stores, for real rows only,
+ *                  Oc = O / l (0 where l is at or below the variant's threshold), the row sum l and the running maximum m
+ *                  (log2 units) of those tiles alone -- bit for bit what the unsplit kernel computes over those key tiles.
+ *                  Chunks a group does not reach are not written.
+ *   combine        second launch, same stream; the only writer of O.  Per real row and head, over the chunks
+ *                  c = 0 ... last(qg) / C in ascending order, in fp32: M = max m_c, a_c = l_c * exp2(m_c - M),
+ *                  Ltot = sum a_c, O = Ltot > thr ? (sum a_c * Oc_c) / Ltot : 0 (thr: 1e-20 int8, 1e-10 fp16).  An invalid
+ *                  sequence (its lens[b], or a used table entry outside the pool): Nq rows of positive zeros, no scratch read.
+ *   scratch        caller-owned device memory, 256-byte aligned, qmha_attend_split_bytes(c, Nq, chunk_rows) bytes (0 on
+ *                  invalid arguments), never allocated or synchronised by the call.  Three fp32 arrays, each starting on
+ *                  a multiple of 256 bytes, in this order:
+ *                      Oc [B][NC][Nq][h * d]      m [B][NC][Nq][h]      l [B][NC][Nq][h]
+ *                  Entries of chunks a row does not reach keep what they held.  Two calls in flight on different streams
+ *                  need different scratch.
+ *
+ * Host checks, all before any HIP call, QMHA_ERR_INVALID: null cache / Q / O / lens / table / scratch, Nq outside
+ * [1, cap], flags other than QMHA_FLAG_CAUSAL, chunk_rows no multiple of 64, below 64 or above cap, scratch misaligned or
+ * below qmha_attend_split_bytes, the contiguous entry point on a paged cache and the reverse.  No allocation, no
+ * synchronisation, no atomics, no waiting between workgroups (both launches can be captured in a hipGraph); one
+ * qmha_profile main pair covers both launches.
+ */
+size_t qmha_attend_split_bytes(const qmha_kv_cache_t *c, int Nq, int chunk_rows);
+int qmha_attend_cached_tokens_split(qmha_kv_cache_t *c, const float *Q, float *O, int Nq, const int32_t *lens,
+                                    int chunk_rows, void *scratch, size_t scratch_bytes, unsigned flags, void *stream);
+int qmha_attend_cached_paged_split(qmha_kv_cache_t *c, const float *Q, float *O, int Nq, const int32_t *lens,
+                                   const int32_t *table, int chunk_rows, void *scratch, size_t scratch_bytes, unsigned flags,
+                                   void *stream);
+
 /* Blocking convenience used by the per-variant `solve` shims and the JAX raw-pointer
  * binding (extensions/jax/jax_ext.cpp:12-28): batch 1, synchronises the device stream. */
 int qmha_solve_variant(const float *Q, const float *K, const float *V, float *O, int N, int d_model, int h,

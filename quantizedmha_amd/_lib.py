@@ -48,6 +48,10 @@ SIGNATURES = {
     "qmha_kv_cache_create_paged": (_i, [ctypes.POINTER(_vp), _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i]),
     "qmha_kv_cache_append_paged": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "qmha_attend_cached_paged": (_i, [_vp, _vp, _vp, _i, _vp, _vp, ctypes.c_uint, _vp]),
+    # split-KV: the two attends with the key sweep in chunks, over the caller's scratch
+    "qmha_attend_split_bytes": (_sz, [_vp, _i, _i]),
+    "qmha_attend_cached_tokens_split": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _sz, ctypes.c_uint, _vp]),
+    "qmha_attend_cached_paged_split": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _sz, ctypes.c_uint, _vp]),
     "qmha_solve_ws": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "qmha_solve_variant": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     "qmha_quantize_int8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),

@@ -900,6 +900,61 @@ int qmha_attend_cached_paged(qmha_kv_cache_t* c, const float* Q, float* O, int N
     });
 }
 
+// ---- split-KV: the token-granular and the paged attend with the key sweep cut into chunks -----------
+namespace {
+
+bool split_chunk_ok(const qmha_kv_cache* c, int chunk_rows) { return chunk_rows >= 64 && chunk_rows % 64 == 0 && chunk_rows <= c->cap; }
+size_t split_bytes(const qmha_kv_cache* c, int Nq, int chunk_rows) {
+    return qmha::split_carve(nullptr, c->B, (c->cap + chunk_rows - 1) / chunk_rows, Nq, c->h, c->D).bytes;
+}
+
+// both entry points: `table` null is the contiguous one
+int attend_split(qmha_kv_cache_t* c, const char* what, const float* Q, float* O, int Nq, const int32_t* lens, const int32_t* table,
+                 bool paged, int chunk_rows, void* scratch, size_t scratch_bytes, unsigned flags, void* stream) {
+    const std::string w = what;
+    if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+    if (int ck = check_cache_kind(c, paged, what)) return ck;
+    if (!Q || !O) return fail(QMHA_ERR_INVALID, "null tensor pointer");
+    if (!lens) return fail(QMHA_ERR_INVALID, w + ": null lens (a device int32[B])");
+    if (paged && !table) return fail(QMHA_ERR_INVALID, w + ": null table (a device int32[B][max_pages])");
+    if (flags != QMHA_FLAG_CAUSAL)
+        return fail(QMHA_ERR_INVALID, w + ": flags must be QMHA_FLAG_CAUSAL (the kernels have no mask but the diagonal)");
+    if (Nq < 1 || Nq > c->cap)
+        return fail(QMHA_ERR_INVALID, w + ": Nq = " + std::to_string(Nq) + " rows, needs 1 <= Nq <= cap = " +
+                                          (paged ? "max_pages * page_rows = " : "") + std::to_string(c->cap));
+    if (!split_chunk_ok(c, chunk_rows))
+        return fail(QMHA_ERR_INVALID, w + ": chunk_rows = " + std::to_string(chunk_rows) + " must be a multiple of 64 with 64 <= chunk_rows <= cap = " +
+                                          std::to_string(c->cap) + " (a chunk is a whole number of two-tile stages)");
+    if (!scratch) return fail(QMHA_ERR_INVALID, w + ": null scratch (qmha_attend_split_bytes bytes of device memory)");
+    if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return fail(QMHA_ERR_INVALID, w + ": scratch must be 256-byte aligned");
+    const size_t need = split_bytes(c, Nq, chunk_rows);
+    if (scratch_bytes < need)
+        return fail(QMHA_ERR_INVALID, w + ": scratch too small: " + std::to_string(scratch_bytes) + " bytes, qmha_attend_split_bytes is " +
+                                          std::to_string(need));
+    const std::string launch = "kv_cache " + w + " launch";
+    return cache_enqueue(c, &ProfRec::main, stream, launch.c_str(), kNoLenCheck, [&](const auto& ws, int) {  // one pair around both launches
+        return qmha::launch_fa_split(ws, Q, O, {c->B, Nq, c->cap, c->h, c->h_kv, c->D, c->d_model, true, -1, lens, true, c->pages(table)},
+                                     chunk_rows, scratch, (hipStream_t)stream);
+    });
+}
+
+}  // namespace
+
+size_t qmha_attend_split_bytes(const qmha_kv_cache_t* c, int Nq, int chunk_rows) {
+    if (!c || Nq < 1 || Nq > c->cap || !split_chunk_ok(c, chunk_rows)) return 0;
+    return split_bytes(c, Nq, chunk_rows);
+}
+
+int qmha_attend_cached_tokens_split(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, const int32_t* lens, int chunk_rows,
+                                    void* scratch, size_t scratch_bytes, unsigned flags, void* stream) {
+    return attend_split(c, "attend_tokens_split", Q, O, Nq, lens, nullptr, false, chunk_rows, scratch, scratch_bytes, flags, stream);
+}
+
+int qmha_attend_cached_paged_split(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, const int32_t* lens, const int32_t* table,
+                                   int chunk_rows, void* scratch, size_t scratch_bytes, unsigned flags, void* stream) {
+    return attend_split(c, "attend_paged_split", Q, O, Nq, lens, table, true, chunk_rows, scratch, scratch_bytes, flags, stream);
+}
+
 int qmha_solve_variant(const float* Q, const float* K, const float* V, float* O, int N, int d_model, int h,
                        int variant) {
     // blocking like the reference (launchers.h:64): hipStreamSynchronize.  r04 A/B: polling

@@ -8,6 +8,8 @@
 // the kernel reads from device memory.  And the ragged kernels: that body once more, over
 // lengths and query counts that are no multiple of 32 (Ragged).  And the paged kernels: the ragged
 // call over a pool of pages, each stage's K/V found through a block table on the device (Paged).
+// The split-KV kernels run the same bodies over Split<Ragged> / Split<Paged>, defined here, from
+// qmha_fa_split.hip.
 //
 // Square causal: query row r attends keys j <= r of its own sequence (Nq = Nk = N).  Both kernels keep the
 // geometry of the non-causal main kernels, so they consume the unchanged pre-pass outputs (qmha_prepass.hip):
@@ -225,6 +227,11 @@ struct PageWalk {
         col = 0, sip_next = 0;
         next = g.entry(b, 0);
     }
+    // a pass that begins at tile t0 (even: a stage's first): a chunk of a split sweep
+    __device__ __forceinline__ void start_at(const Paged& g, int b, int t0) {
+        col = t0 / g.PG, sip_next = t0 % g.PG / kSG;
+        next = g.entry(b, col);
+    }
     __device__ __forceinline__ void take(const Paged& g) { page = next, tile0 = col * g.PG, sip = sip_next; }
     __device__ __forceinline__ void advance(const Paged& g, int b) {
         if (++sip_next == g.PG / kSG) {
@@ -235,12 +242,40 @@ struct PageWalk {
 };
 struct NoWalk {};
 
+// Split-KV: Ragged's or Paged's call with the key sweep cut into chunks of C tiles (C even: a chunk is a
+// whole number of stages, and in a pool never cuts a page's stage).  A workgroup is one unit block of one chunk c < NC
+// (c from the launch index): its waves run tiles c C ... min(c C + C - 1, last(qg)) from the zero state and
+// store the epilogue's O, l and m of those tiles alone into the caller's scratch (SplitScratch, qmha_kernels.hpp); a
+// wave whose last(qg) lies before c C takes no part in the arithmetic and stores nothing.  qmha_split_combine_kernel
+// joins the chunks.  first() / end(): the chunk's first tile and its last.
+template <class Geo>
+struct Split : Geo {
+    float *Oc, *pm, *pl;  // [B][NC][Nq][h D], [B][NC][Nq][h], [B][NC][Nq][h]
+    int C, NC;            // tiles per chunk, chunks
+    int c;                // device: the workgroup's chunk
+    Split(Geo g, const SplitScratch& s, int tiles, int chunks) : Geo(g), Oc(s.Oc), pm(s.m), pl(s.l), C(tiles), NC(chunks), c(0) {}
+    __device__ Split of(int L, int chunk) const {
+        Split v = *this;
+        static_cast<Geo&>(v) = Geo::of(L);
+        v.c = chunk;
+        return v;
+    }
+    __device__ int first() const { return c * C; }
+    __device__ int end() const { return c * C + C - 1; }
+};
+template <class T>
+struct IsSplit : std::false_type {};
+template <class Geo>
+struct IsSplit<Split<Geo>> : std::true_type {};
+
 // A lane's row of Q / O in memory is its row of the (padded) block less row_shift; row_real: that row exists.
 // Constants for every geometry but Ragged (and Paged over it), so the other instances carry no trace of them.
 template <class Geo>
 constexpr bool kRaggedGeo = std::is_base_of<Ragged, std::remove_cv_t<Geo>>::value;
 template <class Geo>
-constexpr bool kPagedGeo = std::is_same<std::remove_cv_t<Geo>, Paged>::value;
+constexpr bool kPagedGeo = std::is_base_of<Paged, std::remove_cv_t<Geo>>::value;
+template <class Geo>
+constexpr bool kSplitGeo = IsSplit<std::remove_cv_t<Geo>>::value;
 // a value of a type that depends on D: the bodies' `if constexpr` branches over a geometry are discarded unchecked
 template <int D, class T>
 __device__ __forceinline__ T as_dependent(T t) { return t; }
@@ -252,6 +287,28 @@ __device__ __forceinline__ int row_shift(const Ragged& g) { return g.s; }
 __device__ __forceinline__ bool row_real(const Ragged& g, int row) { return (unsigned)(row - g.s) < (unsigned)g.Nq; }
 __device__ __forceinline__ int row_shift(const Paged& g) { return g.s; }
 __device__ __forceinline__ bool row_real(const Paged& g, int row) { return (unsigned)(row - g.s) < (unsigned)g.Nq; }
+template <class Geo>
+__device__ __forceinline__ int row_shift(const Split<Geo>& g) { return g.s; }
+template <class Geo>
+__device__ __forceinline__ bool row_real(const Split<Geo>& g, int row) { return (unsigned)(row - g.s) < (unsigned)g.Nq; }
+// The tiles a workgroup may visit and where its stores go: every tile and O itself, but for Split its chunk and the
+// scratch's Oc, whose slice (b, c) has the layout of O's slice b.  Constants for every other geometry.
+template <class Geo>
+__device__ __forceinline__ constexpr int tile_first(const Geo&) { return 0; }
+template <class Geo>
+__device__ __forceinline__ constexpr int tile_end(const Geo&, int last) { return last; }
+template <class Geo>
+__device__ __forceinline__ constexpr float* out_base(const Geo&, float* O) { return O; }
+template <class Geo>
+__device__ __forceinline__ constexpr int out_slice(const Geo&, int b) { return b; }
+template <class Geo>
+__device__ __forceinline__ int tile_first(const Split<Geo>& g) { return g.first(); }
+template <class Geo>
+__device__ __forceinline__ int tile_end(const Split<Geo>& g, int last) { return min(last, g.end()); }
+template <class Geo>
+__device__ __forceinline__ float* out_base(const Split<Geo>& g, float*) { return g.Oc; }
+template <class Geo>
+__device__ __forceinline__ int out_slice(const Split<Geo>& g, int b) { return b * g.NC + g.c; }
 
 // A geometry that also carries the buffers of a dumping instance (int8 kernel; QkDump and PDump in
 // qmha_kernels.hpp): the debug hook's twin of a shipped instance, whose own arguments stay as they are.
@@ -281,6 +338,15 @@ __device__ __forceinline__ void masked_wg(int nqb, int& bh, int& pi) {
     const int wg = xcd_remap(blockIdx.x, gridDim.x);
     bh = wg / masked_pairs(nqb);
     pi = wg % masked_pairs(nqb);
+}
+// Split: launch index -> (K/V slice, unit block, chunk); the chunks of a unit block are neighbours, so c < nc whatever
+// the grid is, and xcd_remap keeps a K/V slice's workgroups on one XCD
+__device__ __forceinline__ void split_wg(int nqb, int nc, int& bh, int& qb, int& c) {
+    const unsigned wg = (unsigned)xcd_remap(blockIdx.x, gridDim.x), per = (unsigned)(nqb * nc);
+    const unsigned r = wg % per;
+    bh = (int)(wg / per);
+    qb = (int)(r / (unsigned)nc);
+    c = (int)(r % (unsigned)nc);
 }
 
 // K/V staging of both kernels: fixed per-lane source offsets (the LDS image's swizzle applied to the
@@ -320,6 +386,11 @@ __device__ __forceinline__ void zero_unit_block(float* __restrict__ O, const Var
     for (int i = lane; i < QMHA_GROUP * C4; i += 64) *reinterpret_cast<v4f*>(o + (size_t)(i / C4) * d_model + 4 * (i % C4)) = v4f{};
 }
 
+// qmha_fa_split.hip takes the geometries, the stager and the checked geometry of a call (masked_geo) from this file's
+// text and none of its kernels: it includes the file with QMHA_FA_SPLIT_TU defined.  (The split kernels are a
+// translation unit of their own because the dumping twins below reach their out-of-line dump lambdas PC-relative: a
+// kernel added to this code object shows in their bytes.)
+#ifndef QMHA_FA_SPLIT_TU
 // ---------------------------------------------------------------------------------------
 // int8: 32x32 accumulator map.  Lane (col, half) holds S^T[acc_row(r, half)][col], r = 0..15: query
 // row `col` of the group against key acc_row(r, half) of the tile, so on the diagonal tile (the groups of
@@ -463,6 +534,8 @@ __global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_f16_paged
 #include "qmha_fa_masked_f16.inc"
 }
 
+#endif  // QMHA_FA_SPLIT_TU
+
 // ---------------------------------------------------------------------------------------
 // host launchers (MaskedCall in qmha_kernels.hpp): per-sequence lengths take the varlen kernels, grouped calls
 // (Hkv < H) the Grouped instances, square causal calls of their own the SquareCausal ones, everything else Rect
@@ -509,6 +582,7 @@ static hipError_t masked_geo(const MaskedCall& c, Launch&& launch) {
     return G > 1 ? launch(Grouped(r, G)) : launch(r);
 }
 
+#ifndef QMHA_FA_SPLIT_TU
 // Launch the instance of `geo` over the call's B * Hkv K/V slices (the kernels' H argument); stream: the dump's is null
 template <class Geo>
 static hipError_t fa_masked_launch(const Int8Workspace& w, const float* Qf, float* O, const MaskedCall& c, hipStream_t stream, Geo geo) {
@@ -590,5 +664,6 @@ hipError_t launch_fa_int8_masked_pstage_dump(const Int8Workspace& w, const float
         else return fa_masked_launch(w, Qf, O, c, nullptr, Dumping<decltype(geo)>(geo, dbg, pd));
     });
 }
+#endif  // QMHA_FA_SPLIT_TU
 
 }  // namespace qmha

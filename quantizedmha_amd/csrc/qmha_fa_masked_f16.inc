@@ -1,7 +1,9 @@
     // qmha_fa_masked_f16.inc -- the body of every fp16 kernel of qmha_fa_masked.hip, included inside the __global__
     // (why a text include and no __device__ function: DESIGN.md 15.3).  In scope: D, the geometry `geo`, and the
     // arguments Qf, Kh, Vt, O, H, d_model, nqb, c_log2.  row_shift(geo) / row_real(geo, row) (qmha_fa_masked.hip) are
-    // 0 / true for every geometry but Ragged, whose query rows sit `s` rows into their 32-row groups.
+    // 0 / true for every geometry but Ragged, whose query rows sit `s` rows into their 32-row groups.  Split<Geo>
+    // (DESIGN.md 19): one unit block of one chunk of tiles per workgroup -- tile_first / tile_end bound the sweep,
+    // out_base / out_slice send the epilogue's O to the scratch, and the row's l and m are stored beside it.
     QMHA_ENABLE_AGPR_MFMA();
     asm volatile("" : "+v"(c_log2));  // a VOP3 fma reading an SGPR issues at the slow rate
     constexpr int WAVES = kWaves, SG = kSG;
@@ -17,7 +19,12 @@
 
     const int Nq = geo.nq(), Nk = geo.nk();
     const int U = geo.units();
+    constexpr bool SPLIT = kSplitGeo<decltype(geo)>;
     int bh, qb0;
+    if constexpr (SPLIT) {  // the chunk is geo.c
+        int c_;
+        split_wg(nqb, geo.NC, bh, qb0, c_);
+    } else
     masked_wg_single(nqb, bh, qb0);
     const int b = bh / H, kvh = bh % H;  // bh: the K/V slice (H K/V heads)
     const int lane = threadIdx.x & 63;
@@ -26,13 +33,16 @@
         if (qb0 * WAVES >= U) return;           // no active unit leaves before any barrier or DMA issue
     }
     const int u = qb0 * WAVES + wave;
-    const bool active = u < U;
+    const bool active = u < U && (SPLIT ? geo.last(geo.group(u)) >= tile_first(geo) : true);  // Split: the wave reaches the chunk
     const int qg = geo.group(u), k = geo.head(kvh, u);  // query group, query head
     const int grp = lane >> 4, r16 = lane & 15;
-    const int wg_last = geo.last(geo.group(min(qb0 * WAVES + WAVES - 1, U - 1)));  // of the last active wave
-    const int nst = wg_last / SG + 1;
+    const int wg_last = tile_end(geo, geo.last(geo.group(min(qb0 * WAVES + WAVES - 1, U - 1))));  // of the last active wave
+    if constexpr (SPLIT) {  // no unit reaches the chunk: the workgroup leaves before any barrier or DMA issue
+        if (wg_last < tile_first(geo)) return;
+    }
+    const int nst = wg_last / SG + 1, st0 = tile_first(geo) / SG;  // the workgroup runs stages st0 ... nst - 1
     const int my_diag = geo.diag(qg);  // this wave's diagonal tile
-    const int my_last = active ? geo.last(qg) : -1;
+    const int my_last = active ? tile_end(geo, geo.last(qg)) : -1;
 
     // Q converted in-kernel (RNE) into the QK B operand: query 16 qb + r16, d = 32 ks + 8 grp .. +7
     v8h qop[2][KS];
@@ -79,7 +89,8 @@
     // Paged: the stage's page slice is the buffer (base formed in 64 bits, records of one page slice), the stage offset
     // the stage's place in its page
     std::conditional_t<kPagedGeo<decltype(geo)>, PageWalk, NoWalk> walk;
-    if constexpr (kPagedGeo<decltype(geo)>) walk.start(geo, b);
+    if constexpr (kPagedGeo<decltype(geo)> && kSplitGeo<decltype(geo)>) walk.start_at(geo, b, tile_first(geo));
+    else if constexpr (kPagedGeo<decltype(geo)>) walk.start(geo, b);
     auto issue = [&](int buf, int st) {
         if constexpr (kPagedGeo<decltype(geo)>) {
             walk.take(geo);
@@ -178,7 +189,7 @@
         }
     };
 
-    issue(0, 0);
+    issue(0, st0);
     qmha_dma_barrier();
     auto stage = [&](auto BUF, int st) {
         constexpr int buf = decltype(BUF)::value;
@@ -195,7 +206,7 @@
         }
         qmha_dma_barrier();
     };
-    int st = 0;
+    int st = st0;
     for (; st + 2 <= nst; st += 2) {
         stage(std::integral_constant<int, 0>{}, st);
         stage(std::integral_constant<int, 1>{}, st + 1);
@@ -208,7 +219,7 @@
             l += __shfl_xor(l, 16);
             l += __shfl_xor(l, 32);
             const bool ok = l > 1e-10f;  // fa_tc_v1a.cu:384-388
-            float* orow = O + ((size_t)b * Nq + (size_t)qg * QMHA_GROUP + 16 * qb + r16 - row_shift(geo)) * d_model + (size_t)k * D + 4 * grp;
+            float* orow = out_base(geo, O) + ((size_t)out_slice(geo, b) * Nq + (size_t)qg * QMHA_GROUP + 16 * qb + r16 - row_shift(geo)) * d_model + (size_t)k * D + 4 * grp;
             if (row_real(geo, qg * QMHA_GROUP + 16 * qb + r16)) {  // a pad lane stores nothing
 #pragma unroll
             for (int m = 0; m < DB; ++m) {
@@ -216,6 +227,13 @@
 #pragma unroll
                 for (int j = 0; j < 4; ++j) w[j] = ok ? o[m][qb][j] / l : 0.0f;
                 *reinterpret_cast<v4f*>(orow + 16 * m) = w;
+            }
+            if constexpr (SPLIT) {  // the chunk's l and m of a real row, [B][NC][Nq][h]: what the combine weighs Oc with
+                if (grp == 0) {
+                    const size_t i = ((size_t)out_slice(geo, b) * Nq + (size_t)(qg * QMHA_GROUP + 16 * qb + r16 - row_shift(geo))) * (size_t)(H * geo.G) + k;
+                    geo.pl[i] = l;
+                    geo.pm[i] = m_run[qb];
+                }
             }
             }
         }

@@ -1,13 +1,16 @@
     // qmha_fa_masked_int8.inc -- the body of every int8 kernel of qmha_fa_masked.hip, included inside the __global__
     // (why a text include and no __device__ function: DESIGN.md 15.3).  In scope: D, Geo, the geometry `geo`, and the
     // arguments Qf, Ki, Vh, sK, sV, O, H, d_model, nqb, c_log2.  row_shift(geo) / row_real(geo, row) (qmha_fa_masked.hip)
-    // are 0 / true for every geometry but Ragged, whose query rows sit `s` rows into their 32-row groups.
+    // are 0 / true for every geometry but Ragged, whose query rows sit `s` rows into their 32-row groups.  Split<Geo>
+    // (DESIGN.md 19): one unit block of one chunk of tiles per workgroup -- tile_first / tile_end bound the sweep,
+    // out_base / out_slice send the epilogue's O to the scratch, and the row's l and m are stored beside it.
     constexpr int WAVES = kWaves, SG = kSG;
     constexpr int KS = D / 32;               // i8 MFMA k-steps (QK) and d-blocks (PV)
     constexpr int KBYTES = SG * 32 * D;      // K int8 per stage
     constexpr int VBYTES = SG * 32 * D * 2;  // V f16 per stage
     constexpr int KCH = KBYTES / 16, VCH = VBYTES / 16;
     constexpr bool DUMP = Geo::kDump;  // also store what the kernel computed (Dumping<Geo>), per tile a wave runs
+    constexpr bool SPLIT = kSplitGeo<decltype(geo)>;
     static_assert(D == 32 || D == 64 || D == 128, "masked int8: d in {32, 64, 128}");
     static_assert(KCH % 64 == 0 && VCH % 64 == 0 && (KCH / SG) % 64 == 0, "whole KiB LDS-DMA pieces");
     __shared__ __attribute__((aligned(16))) char lds[2][KBYTES + VBYTES];
@@ -15,6 +18,10 @@
     const int Nq = geo.nq(), Nk = geo.nk();
     const int Gq = Nq / QMHA_GROUP, Gk = geo.gk(), U = geo.units();
     int bh, pi;
+    if constexpr (SPLIT) {  // no pair: a chunk has no triangle to balance; pi is the unit block, the chunk is geo.c
+        int c_;
+        split_wg(nqb, geo.NC, bh, pi, c_);
+    } else
     masked_wg(nqb, bh, pi);
     const int b = bh / H, kvh = bh % H;  // bh: the K/V slice (H K/V heads)
     const int lane = threadIdx.x & 63;
@@ -22,19 +29,23 @@
     const int half = lane >> 5, col = lane & 31;
 #pragma nounroll
     for (int pass = 0; pass < 2; ++pass) {  // the pair's large q-block, then its mirror (uniform)
-    const int qb = pass == 0 ? nqb - 1 - pi : pi;
-    if (pass == 1 && pi == nqb - 1 - pi) break;  // odd nqb: the middle q-block has no partner
+    const int qb = SPLIT ? pi : pass == 0 ? nqb - 1 - pi : pi;
+    if (pass == 1 && (SPLIT || pi == nqb - 1 - pi)) break;  // odd nqb: the middle q-block has no partner
     if constexpr (kRaggedGeo<decltype(geo)>) {  // its grid follows the host's Nq, U the sequence's length: a pass with no
         if (qb * WAVES >= U) continue;          // active unit leaves before any barrier or DMA issue (workgroup-uniform)
     }
     const int u = qb * WAVES + wave;
-    const bool active = u < U;  // wave-uniform; an inactive wave still stages and syncs
+    // wave-uniform; an inactive wave still stages and syncs.  Split: so does a wave whose tiles end before the chunk
+    const bool active = u < U && (SPLIT ? geo.last(geo.group(u)) >= tile_first(geo) : true);
     const int qg = geo.group(u), k = geo.head(kvh, u);  // query group, query head
     // the workgroup's last tile: that of its last active wave
-    const int wg_last = geo.last(geo.group(min(qb * WAVES + WAVES - 1, U - 1)));
-    const int nst = wg_last / SG + 1;
+    const int wg_last = tile_end(geo, geo.last(geo.group(min(qb * WAVES + WAVES - 1, U - 1))));
+    if constexpr (SPLIT) {  // no unit reaches the chunk: the workgroup leaves before any barrier or DMA issue
+        if (wg_last < tile_first(geo)) break;
+    }
+    const int nst = wg_last / SG + 1, st0 = tile_first(geo) / SG;  // the pass runs stages st0 ... nst - 1
     const int my_diag = geo.diag(qg);              // this wave's diagonal tile
-    const int my_last = active ? geo.last(qg) : -1;  // this wave computes tiles t <= my_last
+    const int my_last = active ? tile_end(geo, geo.last(qg)) : -1;  // this wave computes tiles t <= my_last
 
     // in-register Q quantisation (fa_tc_int8_b.cu:33-152) into the Q^T operand: lane (col, half) holds
     // bytes [32 s + 16 half, +16) of query row col for every k-step s
@@ -114,7 +125,8 @@
     // Paged: the stage's page slice is the buffer (base formed in 64 bits, records of one page slice), the stage offset
     // the stage's place in its page; skb / svb follow the page a stage was issued with (the head of `stage` below)
     std::conditional_t<kPagedGeo<decltype(geo)>, PageWalk, NoWalk> walk;
-    if constexpr (kPagedGeo<decltype(geo)>) walk.start(geo, b);
+    if constexpr (kPagedGeo<decltype(geo)> && kSplitGeo<decltype(geo)>) walk.start_at(geo, b, tile_first(geo));
+    else if constexpr (kPagedGeo<decltype(geo)>) walk.start(geo, b);
     auto issue = [&](int buf, int st) {
         if constexpr (kPagedGeo<decltype(geo)>) {
             walk.take(geo);
@@ -219,8 +231,8 @@
         }
     };
 
-    issue(0, 0);
-    qmha_dma_barrier();  // waits vmcnt(0): stage 0 has landed
+    issue(0, st0);
+    qmha_dma_barrier();  // waits vmcnt(0): stage st0 has landed
     auto stage = [&](auto BUF, int st) {
         constexpr int buf = decltype(BUF)::value;
         if constexpr (kPagedGeo<decltype(geo)>) {  // the scales of the page this stage was issued with: skb[t] is its group t - tile0
@@ -240,7 +252,7 @@
         }
         qmha_dma_barrier();  // vmcnt(0) + barrier: stage st+1 landed, stage st released
     };
-    int st = 0;
+    int st = st0;
     for (; st + 2 <= nst; st += 2) {
         stage(std::integral_constant<int, 0>{}, st);
         stage(std::integral_constant<int, 1>{}, st + 1);
@@ -255,7 +267,7 @@
             if (half == 0) geo.pd.l[drow] = l;
         }
         const bool ok = l > 1e-20f;
-        float* orow = O + ((size_t)b * Nq + (size_t)qg * QMHA_GROUP + col) * d_model + (size_t)k * D + 4 * half;
+        float* orow = out_base(geo, O) + ((size_t)out_slice(geo, b) * Nq + (size_t)qg * QMHA_GROUP + col) * d_model + (size_t)k * D + 4 * half;
         if constexpr (kRaggedGeo<decltype(geo)>) orow -= (size_t)row_shift(geo) * d_model;
         if (kRaggedGeo<decltype(geo)> ? row_real(geo, qg * QMHA_GROUP + col) : true)  // a pad lane (Ragged) stores nothing
 #pragma unroll
@@ -267,5 +279,12 @@
                 for (int jj = 0; jj < 4; ++jj) w[jj] = ok ? (o[m][4 * g4 + jj] * unanchor) / l : 0.0f;
                 *reinterpret_cast<v4f*>(orow + 32 * m + 8 * g4) = w;
             }
+        if constexpr (SPLIT) {  // the chunk's l and m of a real row, [B][NC][Nq][h]: what the combine weighs Oc with
+            if (half == 0 && row_real(geo, qg * QMHA_GROUP + col)) {
+                const size_t i = ((size_t)out_slice(geo, b) * Nq + (size_t)(qg * QMHA_GROUP + col - row_shift(geo))) * (size_t)(H * geo.G) + k;
+                geo.pl[i] = l;
+                geo.pm[i] = m_run;
+            }
+        }
     }
     }  // pass: the last stage's barrier has released both LDS buffers

@@ -221,6 +221,33 @@ hipError_t launch_fa_masked(const F16Workspace& w, const float* Qf, float* O, co
 hipError_t launch_fa_int8_masked_pstage_dump(const Int8Workspace& w, const float* Qf, float* O, const MaskedCall& c, QkDump dbg,
                                              PDump pd);
 
+// ---- split-KV over a cache's token-granular and paged calls (qmha_fa_split.hip) -----------
+// The caller's scratch of a split call, each array on a multiple of 256 bytes: per sequence b, chunk c < NC =
+// ceil(Nk / chunk_rows), real query row r < Nq and query head k < H the chunk's normalised output Oc [B][NC][Nq][H * D],
+// its row sum l and its running maximum m (log2 units), both [B][NC][Nq][H], all fp32.  Only the entries of chunks a row
+// reaches (c * chunk_rows / 32 <= its group's last tile) are written, and only those are read.
+struct SplitScratch {
+    float *Oc, *m, *l;
+    size_t bytes;  // of the whole layout
+};
+inline SplitScratch split_carve(void* p, int B, int NC, int Nq, int H, int D) {
+    const size_t rows = (size_t)B * NC * Nq;
+    Carver c{static_cast<char*>(p)};
+    SplitScratch s{};
+    s.Oc = c.take<float>(align_up(rows * H * D * sizeof(float), 256));
+    s.m = c.take<float>(align_up(rows * H * sizeof(float), 256));
+    s.l = c.take<float>(align_up(rows * H * sizeof(float), 256));
+    s.bytes = c.used;
+    return s;
+}
+// c: a token-granular call (ragged, with lens; a table: paged) as launch_fa_masked takes it.  Two launches on `stream`:
+// the partial kernels, a workgroup per (K/V slice, unit block, chunk of chunk_rows key rows), fill `scratch`
+// (split_carve(..).bytes bytes, 256-byte aligned); the combine kernel writes O.  chunk_rows: a multiple of 64 in [64, Nk].
+hipError_t launch_fa_split(const Int8Workspace& w, const float* Qf, float* O, const MaskedCall& c, int chunk_rows, void* scratch,
+                           hipStream_t stream);
+hipError_t launch_fa_split(const F16Workspace& w, const float* Qf, float* O, const MaskedCall& c, int chunk_rows, void* scratch,
+                           hipStream_t stream);
+
 // ---- K/V cache append (qmha_prepass.hip) ----------------------------------------
 // w: the variant's carve of H heads at N = cap, in caller-owned memory.  The pre-pass of the n new rows K, V
 // [B, n, d_model = H * D] into rows [len, len + n) of every slice, byte for byte what the pre-pass of a whole call writes

@@ -22,6 +22,8 @@
 //     row, any Nq, causal (qmha_kv_cache_attach_tail / qmha_kv_cache_append_tokens / qmha_attend_cached_tokens);
 //   * `PagedKVCache`: a pool of pages and a caller-owned block table on the device, `append_paged` / `attend_paged`
 //     (qmha_kv_cache_create_paged / qmha_kv_cache_append_paged / qmha_attend_cached_paged);
+//   * all three caches' `enable_split` / `attend_tokens_split` (`attend_paged_split`) / `split_partials`: the attend with
+//     the key sweep in chunks over a scratch the object owns (qmha_attend_cached_tokens_split / _paged_split);
 //   * a rejected shape raises (TORCH_CHECK on the C-ABI status) instead of a device assert.
 #include <torch/extension.h>
 // ROCm PyTorch reports HIP devices as device type "cuda": the guard / current-stream
@@ -31,6 +33,7 @@
 
 #include <optional>
 #include <string>
+#include <tuple>
 
 #include "launchers.h"
 
@@ -166,6 +169,42 @@ static Tensor cache_rows(const Tensor& X, const char* name, int64_t width, int64
     return Xc;
 }
 
+// The split-KV scratch of a cache (enable_split; include/launchers.h has the layout): what both cache classes keep for
+// attend_tokens_split / attend_paged_split, and the views split_partials hands out.
+struct SplitState {
+    int64_t chunk_rows = 0, max_nq = 0;
+    Tensor scratch;
+
+    void enable(qmha_kv_cache_t* handle, int64_t chunk, int64_t nq, int64_t cap, const c10::Device& device) {
+        const size_t bytes = qmha_attend_split_bytes(handle, static_cast<int>(nq), static_cast<int>(chunk));
+        TORCH_CHECK(bytes > 0, "enable_split: chunk_rows = ", chunk, " must be a multiple of 64 with 64 <= chunk_rows <= cap = ", cap,
+                    ", and 1 <= max_nq = ", nq, " <= cap");
+        chunk_rows = chunk, max_nq = nq;
+        scratch = torch::zeros({static_cast<int64_t>(bytes)}, torch::TensorOptions().dtype(torch::kUInt8).device(device));
+    }
+    void ready(int64_t Nq, const char* what) const {
+        TORCH_CHECK(scratch.defined(), what, ": call enable_split(chunk_rows) first");
+        TORCH_CHECK(Nq <= max_nq, what, ": Nq = ", Nq, " rows exceed enable_split's max_nq = ", max_nq);
+    }
+    // (Oc [B, NC, Nq, d_model], m [B, NC, Nq, heads], l [B, NC, Nq, heads]) of the last split attend of Nq rows
+    std::tuple<Tensor, Tensor, Tensor> partials(qmha_kv_cache_t* handle, int64_t Nq, int64_t B, int64_t cap, int64_t d_model,
+                                                int64_t heads) const {
+        ready(Nq, "split_partials");
+        TORCH_CHECK(Nq >= 1, "split_partials: Nq must be at least 1");
+        const int64_t nc = (cap + chunk_rows - 1) / chunk_rows, rows = B * nc * Nq;
+        const auto al = [](int64_t x) { return (x + 255) / 256 * 256; };  // each array starts on a multiple of 256 bytes
+        const int64_t o_bytes = 4 * rows * d_model, s_bytes = 4 * rows * heads;
+        TORCH_CHECK(static_cast<size_t>(al(o_bytes) + 2 * al(s_bytes)) ==
+                        qmha_attend_split_bytes(handle, static_cast<int>(Nq), static_cast<int>(chunk_rows)),
+                    "split_partials: the scratch layout is not the library's");
+        const auto arr = [&](int64_t off, int64_t bytes, int64_t width) {
+            return scratch.slice(0, off, off + bytes).view(torch::kFloat32).view({B, nc, Nq, width});
+        };
+        return {arr(0, o_bytes, d_model), arr(al(o_bytes), s_bytes, heads), arr(al(o_bytes) + al(s_bytes), s_bytes, heads)};
+    }
+    std::optional<Tensor> tensor() const { return scratch.defined() ? std::optional<Tensor>(scratch) : std::nullopt; }
+};
+
 // A persistent quantised K/V cache (qmha_kv_cache_*): the compiled form of quantizedmha_amd/torch_ext.py's KVCache.
 // Owns a uint8 tensor of qmha_kv_cache_bytes and the host handle; append / attend run on PyTorch's current stream.
 class KVCache {
@@ -173,7 +212,7 @@ public:
     // num_kv_heads (GroupedKVCache): the cache holds that many K/V heads, shared by the num_heads query heads
     KVCache(int64_t B, int64_t cap, int64_t d_model, int64_t num_heads, const std::string& kernel, const std::string& device,
             std::optional<int64_t> num_kv_heads = std::nullopt)
-        : B_(B), cap_(cap), d_model_(d_model), kv_model_(d_model), kernel_(kernel) {
+        : B_(B), cap_(cap), d_model_(d_model), kv_model_(d_model), num_heads_(num_heads), kernel_(kernel) {
         const int variant = qmha_variant_from_name(kernel.c_str());
         TORCH_CHECK(variant >= 0, "KVCache: unknown kernel '", kernel, "'");
         c10::Device dev(device);
@@ -282,12 +321,35 @@ public:
         return out_opt ? out : out.view(Q.sizes());
     }
 
+    // allocate the scratch of the split-KV attend (qmha_attend_split_bytes at Nq = max_nq); once, outside a capture
+    void enable_split(int64_t chunk_rows, int64_t max_nq) { split_.enable(handle_, chunk_rows, max_nq, cap_, mem_.device()); }
+    std::optional<Tensor> split_scratch() const { return split_.tensor(); }
+    std::tuple<Tensor, Tensor, Tensor> split_partials(int64_t Nq) const {
+        return split_.partials(handle_, Nq, B_, cap_, d_model_, num_heads_);
+    }
+
+    // attend_tokens with the key sweep in chunks and a combine pass (qmha_attend_cached_tokens_split)
+    Tensor attend_tokens_split(const Tensor& Q, const Tensor& lens, std::optional<Tensor> out_opt) {
+        auto Qc = rows(Q, "Q", d_model_);
+        per_seq(lens, "lens");
+        split_.ready(Qc.size(1), "attend_tokens_split");
+        Tensor out = out_for(out_opt, Qc);
+        const OnStream on = current_stream(mem_.device());
+        const int st = qmha_attend_cached_tokens_split(handle_, Qc.data_ptr<float>(), out.data_ptr<float>(), static_cast<int>(Qc.size(1)),
+                                                       lens.data_ptr<int32_t>(), static_cast<int>(split_.chunk_rows),
+                                                       split_.scratch.data_ptr(), static_cast<size_t>(split_.scratch.numel()),
+                                                       QMHA_FLAG_CAUSAL, on.stream);
+        TORCH_CHECK(st == QMHA_OK, "KVCache.attend_tokens_split", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+        return out_opt ? out : out.view(Q.sizes());
+    }
+
 private:
     void per_seq(const Tensor& t, const char* name) const { cache_per_seq(t, name, B_, mem_.device()); }
     Tensor rows(const Tensor& X, const char* name, int64_t width) const { return cache_rows(X, name, width, B_, mem_.device()); }
-    int64_t B_, cap_, d_model_, kv_model_;
+    int64_t B_, cap_, d_model_, kv_model_, num_heads_;
     std::string kernel_;
     Tensor mem_, tail_;
+    SplitState split_;
     qmha_kv_cache_t* handle_ = nullptr;
 };
 
@@ -305,7 +367,8 @@ class PagedKVCache {
 public:
     PagedKVCache(int64_t B, int64_t num_pages, int64_t page_rows, int64_t max_pages, int64_t d_model, int64_t num_heads,
                  std::optional<int64_t> num_kv_heads, const std::string& kernel, const std::string& device)
-        : B_(B), max_pages_(max_pages), cap_(max_pages * page_rows), d_model_(d_model), kv_model_(d_model), kernel_(kernel) {
+        : B_(B), max_pages_(max_pages), cap_(max_pages * page_rows), d_model_(d_model), kv_model_(d_model), num_heads_(num_heads),
+          kernel_(kernel) {
         const int variant = qmha_variant_from_name(kernel.c_str());
         TORCH_CHECK(variant >= 0, "PagedKVCache: unknown kernel '", kernel, "'");
         c10::Device dev(device);
@@ -362,6 +425,29 @@ public:
         return out_opt ? out : out.view(Q.sizes());
     }
 
+    // the split-KV scratch, as KVCache's
+    void enable_split(int64_t chunk_rows, int64_t max_nq) { split_.enable(handle_, chunk_rows, max_nq, cap_, mem_.device()); }
+    std::optional<Tensor> split_scratch() const { return split_.tensor(); }
+    std::tuple<Tensor, Tensor, Tensor> split_partials(int64_t Nq) const {
+        return split_.partials(handle_, Nq, B_, cap_, d_model_, num_heads_);
+    }
+
+    // attend_tokens_split through the block table (qmha_attend_cached_paged_split)
+    Tensor attend_paged_split(const Tensor& Q, const Tensor& lens, const Tensor& table, std::optional<Tensor> out_opt) {
+        auto Qc = cache_rows(Q, "Q", d_model_, B_, mem_.device());
+        cache_per_seq(lens, "lens", B_, mem_.device());
+        check_table(table);
+        split_.ready(Qc.size(1), "attend_paged_split");
+        Tensor out = out_for(out_opt, Qc);
+        const OnStream on = current_stream(mem_.device());
+        const int st = qmha_attend_cached_paged_split(handle_, Qc.data_ptr<float>(), out.data_ptr<float>(), static_cast<int>(Qc.size(1)),
+                                                      lens.data_ptr<int32_t>(), table.data_ptr<int32_t>(), static_cast<int>(split_.chunk_rows),
+                                                      split_.scratch.data_ptr(), static_cast<size_t>(split_.scratch.numel()),
+                                                      QMHA_FLAG_CAUSAL, on.stream);
+        TORCH_CHECK(st == QMHA_OK, "PagedKVCache.attend_paged_split", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+        return out_opt ? out : out.view(Q.sizes());
+    }
+
 private:
     // the block table: int32 [B, max_pages] on the cache's device, contiguous: the kernel reads it, the host does not
     void check_table(const Tensor& t) const {
@@ -371,9 +457,10 @@ private:
         TORCH_CHECK(t.dim() == 2 && t.size(0) == B_ && t.size(1) == max_pages_ && t.is_contiguous(),
                     "table must be a contiguous tensor of shape [B = ", B_, ", max_pages = ", max_pages_, "]");
     }
-    int64_t B_, max_pages_, cap_, d_model_, kv_model_;
+    int64_t B_, max_pages_, cap_, d_model_, kv_model_, num_heads_;
     std::string kernel_;
     Tensor mem_, tail_;
+    SplitState split_;
     qmha_kv_cache_t* handle_ = nullptr;
 };
 
@@ -396,6 +483,15 @@ PYBIND11_MODULE(torch_ext, m) {
         .def("attend_paged", &PagedKVCache::attend_paged, pybind11::arg("Q"), pybind11::arg("lens"), pybind11::arg("table"),
              pybind11::arg("out") = pybind11::none(),
              "attend_tokens through the table; an invalid lens[b] or a used table entry outside [0, num_pages) gives zeros.")
+        .def("enable_split", &PagedKVCache::enable_split, pybind11::arg("chunk_rows"), pybind11::arg("max_nq") = 32,
+             "allocate the scratch of attend_paged_split for chunks of chunk_rows key rows (a multiple of 64) and up to max_nq\n"
+             "query rows; once, outside a graph capture.")
+        .def("attend_paged_split", &PagedKVCache::attend_paged_split, pybind11::arg("Q"), pybind11::arg("lens"), pybind11::arg("table"),
+             pybind11::arg("out") = pybind11::none(),
+             "attend_paged with the key sweep in chunks and a combine pass: attend_tokens_split through the table, bit for bit.")
+        .def("split_partials", &PagedKVCache::split_partials, pybind11::arg("Nq"),
+             "(Oc, m, l) views of the scratch: what the last split attend of Nq rows left per chunk.")
+        .def_property_readonly("split_scratch", &PagedKVCache::split_scratch)
         .def_property_readonly("tail", &PagedKVCache::tail)
         .def_property_readonly("cap", &PagedKVCache::cap)
         .def_property_readonly("mem", &PagedKVCache::mem);
@@ -422,6 +518,15 @@ PYBIND11_MODULE(torch_ext, m) {
              "for their rows so far, zero-padded; an invalid pos[b] writes nothing for that sequence.")
         .def("attend_tokens", &KVCache::attend_tokens, pybind11::arg("Q"), pybind11::arg("lens"), pybind11::arg("out") = pybind11::none(),
              "causal attend_varlen for any Nq >= 1 and any lens[b] in [Nq, cap]; an invalid lens[b] gives zeros.")
+        .def("enable_split", &KVCache::enable_split, pybind11::arg("chunk_rows"), pybind11::arg("max_nq") = 32,
+             "allocate the scratch of attend_tokens_split for chunks of chunk_rows key rows (a multiple of 64) and up to max_nq\n"
+             "query rows; once, outside a graph capture.")
+        .def("attend_tokens_split", &KVCache::attend_tokens_split, pybind11::arg("Q"), pybind11::arg("lens"),
+             pybind11::arg("out") = pybind11::none(),
+             "attend_tokens with the key sweep in chunks and a combine pass, for a decode step on long sequences.")
+        .def("split_partials", &KVCache::split_partials, pybind11::arg("Nq"),
+             "(Oc, m, l) views of the scratch: what the last split attend of Nq rows left per chunk.")
+        .def_property_readonly("split_scratch", &KVCache::split_scratch)
         .def_property_readonly("tail", &KVCache::tail)
         .def_property_readonly("len", &KVCache::len)
         .def_property_readonly("cap", &KVCache::cap)

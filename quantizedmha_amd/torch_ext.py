@@ -176,7 +176,9 @@ class KVCache:
     device, read by the kernels when they run: sequences of different lengths in one cache, and a step that is captured
     once and replayed while the caller advances pos / lens in device memory.  They leave `len` alone.
     enable_tokens() once, then append_tokens(K, V, pos) / attend_tokens(Q, lens): the same at any length -- a prompt of
-    1000 rows, a decode step of one (qmha_kv_cache_append_tokens / qmha_attend_cached_tokens; causal only)."""
+    1000 rows, a decode step of one (qmha_kv_cache_append_tokens / qmha_attend_cached_tokens; causal only).
+    enable_split(chunk_rows) once, then attend_tokens_split(Q, lens): attend_tokens with the key sweep cut into chunks and
+    a combine pass (qmha_attend_cached_tokens_split), for a decode step on long sequences."""
 
     def __init__(self, B: int, cap: int, d_model: int, num_heads: int, kernel: str = _lib.DEFAULT_KERNEL, device="cuda"):
         self._setup(B, cap, d_model, num_heads, None, kernel, device)
@@ -197,6 +199,7 @@ class KVCache:
         vid = _lib.variant_id(kernel)
         self._handle = None
         self.tail = None  # enable_tokens()
+        self.split_scratch = None  # enable_split()
         if num_kv_heads is None:
             nbytes = lib.qmha_kv_cache_bytes(self.B, self.cap, self.d_model, self.num_heads, vid)
         else:  # the carve of num_kv_heads heads
@@ -337,6 +340,61 @@ class KVCache:
         _lib.check(st, f"KVCache.attend_tokens({self.kernel})")
         return out.view(Q.shape) if out.numel() == Q.numel() and out.dim() != Q.dim() else out
 
+    def enable_split(self, chunk_rows: int, max_nq: int = 32) -> None:
+        """Allocate the scratch of the split-KV attend (qmha_attend_split_bytes at Nq = max_nq), `.split_scratch`, for
+        chunks of chunk_rows key rows: a multiple of 64 with 64 <= chunk_rows <= cap.  Once (a second call replaces the
+        scratch), and outside a graph capture: the split attend itself allocates nothing.  One scratch serves one call
+        at a time: calls in flight on different streams need caches, or scratches, of their own."""
+        chunk_rows, max_nq = int(chunk_rows), int(max_nq)
+        nbytes = _lib.load().qmha_attend_split_bytes(self._handle, max_nq, chunk_rows)
+        if nbytes == 0:
+            raise RuntimeError(f"enable_split: chunk_rows = {chunk_rows} must be a multiple of 64 with 64 <= chunk_rows <= cap = "
+                               f"{self.cap}, and 1 <= max_nq = {max_nq} <= cap")
+        self.split_chunk_rows, self.split_max_nq = chunk_rows, max_nq
+        self.split_scratch = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+
+    def _split_ready(self, Nq: int, what: str) -> None:
+        if getattr(self, "split_scratch", None) is None:
+            raise RuntimeError(f"{what}: call enable_split(chunk_rows) first")
+        if Nq > self.split_max_nq:
+            raise RuntimeError(f"{what}: Nq = {Nq} rows exceed enable_split's max_nq = {self.split_max_nq}")
+
+    def split_partials(self, Nq: int):
+        """What the last split attend of Nq rows left in `.split_scratch`, as views: (Oc [B, NC, Nq, d_model],
+        m [B, NC, Nq, num_heads], l [B, NC, Nq, num_heads]), NC = ceil(cap / chunk_rows) -- each chunk's normalised
+        output, running maximum (log2 units) and row sum.  Only the chunks a row reaches are written (include/launchers.h)."""
+        Nq = int(Nq)
+        self._split_ready(Nq, "split_partials")
+        if Nq < 1:
+            raise RuntimeError("split_partials: Nq must be at least 1")
+        nc = -(-self.cap // self.split_chunk_rows)
+        rows, h = self.B * nc * Nq, self.num_heads
+        al = lambda x: -(-x // 256) * 256  # noqa: E731 -- each array starts on a multiple of 256 bytes
+        o_bytes, s_bytes = 4 * rows * self.d_model, 4 * rows * h
+        total = al(o_bytes) + 2 * al(s_bytes)
+        if total != _lib.load().qmha_attend_split_bytes(self._handle, Nq, self.split_chunk_rows):
+            raise RuntimeError("split_partials: the scratch layout is not the library's")
+        mem = self.split_scratch
+        Oc = mem[:o_bytes].view(torch.float32).view(self.B, nc, Nq, self.d_model)
+        m = mem[al(o_bytes):al(o_bytes) + s_bytes].view(torch.float32).view(self.B, nc, Nq, h)
+        l = mem[al(o_bytes) + al(s_bytes):al(o_bytes) + al(s_bytes) + s_bytes].view(torch.float32).view(self.B, nc, Nq, h)
+        return Oc, m, l
+
+    def attend_tokens_split(self, Q: torch.Tensor, lens: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """attend_tokens with the key sweep in chunks of enable_split's chunk_rows and a combine pass
+        (qmha_attend_cached_tokens_split): for a decode step on long sequences.  Same arguments, validity rules and
+        accuracy contract; a deterministic result of its own, not attend_tokens' bits."""
+        Qc = self._rows(Q, "Q")
+        lens = self._per_seq(lens, "lens")
+        self._split_ready(Qc.shape[1], "attend_tokens_split")
+        out = _out_for(out, Qc, "size")
+        with _current_stream(self.device) as stream:
+            st = _lib.load().qmha_attend_cached_tokens_split(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[1], lens.data_ptr(),
+                                                             self.split_chunk_rows, self.split_scratch.data_ptr(),
+                                                             self.split_scratch.numel(), _lib.QMHA_FLAG_CAUSAL, stream)
+        _lib.check(st, f"KVCache.attend_tokens_split({self.kernel})")
+        return out.view(Q.shape) if out.numel() == Q.numel() and out.dim() != Q.dim() else out
+
 
 class GroupedKVCache(KVCache):
     """KVCache for grouped-query attention (qmha_kv_cache_create_gqa): the cache holds num_kv_heads K/V heads shared
@@ -383,6 +441,7 @@ class PagedKVCache:
         vid = _lib.variant_id(kernel)
         self._handle = None
         self.tail = None  # enable_tokens()
+        self.split_scratch = None  # enable_split()
         nbytes = lib.qmha_kv_cache_paged_bytes(self.num_pages, self.page_rows, self.d_model, self.num_heads, self.num_kv_heads, vid)
         self.mem = torch.zeros(max(nbytes, 1), dtype=torch.uint8, device=self.device)
         handle = ctypes.c_void_p()
@@ -395,6 +454,9 @@ class PagedKVCache:
     _rows = KVCache._rows
     _per_seq = KVCache._per_seq
     enable_tokens = KVCache.enable_tokens
+    enable_split = KVCache.enable_split
+    _split_ready = KVCache._split_ready
+    split_partials = KVCache.split_partials
 
     def _table(self, t: torch.Tensor) -> torch.Tensor:
         """The block table: int32 [B, max_pages] on the cache's device, read by the kernel when it runs (not by the host)."""
@@ -434,6 +496,19 @@ class PagedKVCache:
             st = _lib.load().qmha_attend_cached_paged(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[1], lens.data_ptr(),
                                                       table.data_ptr(), _lib.QMHA_FLAG_CAUSAL, stream)
         _lib.check(st, f"PagedKVCache.attend_paged({self.kernel})")
+        return out.view(Q.shape) if out.numel() == Q.numel() and out.dim() != Q.dim() else out
+
+    def attend_paged_split(self, Q: torch.Tensor, lens: torch.Tensor, table: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """attend_tokens_split through the table (qmha_attend_cached_paged_split), bit for bit; needs enable_split()."""
+        Qc = self._rows(Q, "Q")
+        lens, table = self._per_seq(lens, "lens"), self._table(table)
+        self._split_ready(Qc.shape[1], "attend_paged_split")
+        out = _out_for(out, Qc, "size")
+        with _current_stream(self.device) as stream:
+            st = _lib.load().qmha_attend_cached_paged_split(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[1], lens.data_ptr(),
+                                                            table.data_ptr(), self.split_chunk_rows, self.split_scratch.data_ptr(),
+                                                            self.split_scratch.numel(), _lib.QMHA_FLAG_CAUSAL, stream)
+        _lib.check(st, f"PagedKVCache.attend_paged_split({self.kernel})")
         return out.view(Q.shape) if out.numel() == Q.numel() and out.dim() != Q.dim() else out
 
 

@@ -352,6 +352,49 @@ int qmha_attend_cached_paged_split(qmha_kv_cache_t *c, const float *Q, float *O,
                                    const int32_t *table, int chunk_rows, void *scratch, size_t scratch_bytes, unsigned flags,
                                    void *stream);
 
+/*
+ * Packed batches -- a query count and an append count per sequence in one call, for a continuous-batching step that
+ * mixes chunked prefill and decode.  The operands have no batch axis, in the cu_seqlens convention of varlen attention:
+ *
+ *   Q, O           [total, d_model]          K, V  [total, h_kv * d]
+ *   cu             a DEVICE int32 [B + 1] array, caller-owned, read by the kernels when they run, like pos, lens and
+ *                  table: sequence b owns the rows [cu[b], cu[b + 1]) of the packed operands, n_b = cu[b + 1] - cu[b] of
+ *                  them.  The host never reads it, so a captured step follows a mix the caller changes in device memory.
+ *                  One cu array may serve the append and the attend of a step.  A monotone cu is the caller's side of
+ *                  the contract: ranges of different sequences that overlap stay in bounds, their content is unspecified.
+ *   total          the rows of the packed operands (host); rows outside every range are neither read nor written.
+ *   max_n, max_nq  an upper bound (host) of the counts, 1 <= bound <= min(total, cap): it sizes the grid, as n and Nq do
+ *                  for the calls above.
+ *
+ * The contract is the calls' above, per sequence and bit for bit.  Multi-head, grouped and paged caches; causal only.
+ *
+ *   append_packed, append_paged_packed
+ *                  a sequence with 1 <= n_b <= max_n rows, pos[b] >= 0 and pos[b] + n_b <= cap (paged: and every table
+ *                  entry the rows touch in [0, num_pages)): the cache and the tail hold afterwards what append_tokens
+ *                  (append_paged) with n = n_b writes for it; no other group is written.  n_b == 0: the sequence sits
+ *                  out, pos[b] is not looked at.  Any other sequence writes nothing, the tail included.
+ *   attend_packed, attend_paged_packed
+ *                  a sequence with 1 <= nq_b <= max_nq rows and nq_b <= lens[b] <= cap (paged: and every used table entry
+ *                  in the pool): its rows of O are the rows attend_tokens (attend_paged) writes for a sequence of that
+ *                  Nq and lens[b] over the same cache bytes.  nq_b == 0: the sequence sits out, lens[b] is not looked at.
+ *                  Any other sequence whose range is in bounds: its rows of O are positive zeros, none of its K/V is read.
+ *   range          in bounds when 0 <= cu[b] <= cu[b + 1] <= total.  A range that is not never becomes an address: nothing
+ *                  of that sequence is read or written.
+ *
+ * Host checks, all before any HIP call, QMHA_ERR_INVALID: null cache / tensor / cu / pos / lens / table, total < 1,
+ * max_n or max_nq outside [1, min(total, cap)], flags other than QMHA_FLAG_CAUSAL, an int8 cache without its tail, the
+ * contiguous entry point on a paged cache and the reverse.  No allocation, no synchronisation (the calls can be captured
+ * in a hipGraph); the cache's mutex is held across the enqueue; qmha_profile records are those of append / attend.
+ */
+int qmha_kv_cache_append_packed(qmha_kv_cache_t *c, const float *K, const float *V, int total, int max_n, const int32_t *cu,
+                                const int32_t *pos, void *stream);
+int qmha_kv_cache_append_paged_packed(qmha_kv_cache_t *c, const float *K, const float *V, int total, int max_n,
+                                      const int32_t *cu, const int32_t *pos, const int32_t *table, void *stream);
+int qmha_attend_cached_packed(qmha_kv_cache_t *c, const float *Q, float *O, int total, int max_nq, const int32_t *cu,
+                              const int32_t *lens, unsigned flags, void *stream);
+int qmha_attend_cached_paged_packed(qmha_kv_cache_t *c, const float *Q, float *O, int total, int max_nq, const int32_t *cu,
+                                    const int32_t *lens, const int32_t *table, unsigned flags, void *stream);
+
 /* Blocking convenience used by the per-variant `solve` shims and the JAX raw-pointer
  * binding (extensions/jax/jax_ext.cpp:12-28): batch 1, synchronises the device stream. */
 int qmha_solve_variant(const float *Q, const float *K, const float *V, float *O, int N, int d_model, int h,

@@ -52,6 +52,11 @@ SIGNATURES = {
     "qmha_attend_split_bytes": (_sz, [_vp, _i, _i]),
     "qmha_attend_cached_tokens_split": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _sz, ctypes.c_uint, _vp]),
     "qmha_attend_cached_paged_split": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _sz, ctypes.c_uint, _vp]),
+    # packed batches: operands without a batch axis and a device int32[B + 1] cu beside pos / lens / table
+    "qmha_kv_cache_append_packed": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "qmha_kv_cache_append_paged_packed": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "qmha_attend_cached_packed": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, ctypes.c_uint, _vp]),
+    "qmha_attend_cached_paged_packed": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, ctypes.c_uint, _vp]),
     "qmha_solve_ws": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "qmha_solve_variant": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     "qmha_quantize_int8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),

@@ -955,6 +955,85 @@ int qmha_attend_cached_paged_split(qmha_kv_cache_t* c, const float* Q, float* O,
     return attend_split(c, "attend_paged_split", Q, O, Nq, lens, table, true, chunk_rows, scratch, scratch_bytes, flags, stream);
 }
 
+// ---- packed batches: a query / append count per sequence from a device cu[B + 1], no batch axis -----------
+namespace {
+
+// the bound a packed call's grid is sized for: 1 <= bound <= min(total, cap)
+int packed_bound_check(const qmha_kv_cache* c, const std::string& w, const char* name, int total, int bound, bool paged) {
+    if (total < 1) return fail(QMHA_ERR_INVALID, w + ": total = " + std::to_string(total) + " rows, needs total >= 1");
+    if (bound < 1 || bound > total || bound > c->cap)
+        return fail(QMHA_ERR_INVALID, w + ": " + name + " = " + std::to_string(bound) + ", needs 1 <= " + name + " <= min(total = " +
+                                          std::to_string(total) + ", cap = " + (paged ? "max_pages * page_rows = " : "") +
+                                          std::to_string(c->cap) + ")");
+    return QMHA_OK;
+}
+
+// both append entry points: `table` null is the contiguous one
+int append_packed(qmha_kv_cache_t* c, const char* what, const float* K, const float* V, int total, int max_n, const int32_t* cu,
+                  const int32_t* pos, const int32_t* table, bool paged, void* stream) {
+    const std::string w = what;
+    if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+    if (int ck = check_cache_kind(c, paged, what)) return ck;
+    if (!K || !V) return fail(QMHA_ERR_INVALID, "null tensor pointer");
+    if (!cu) return fail(QMHA_ERR_INVALID, w + ": null cu (a device int32[B + 1])");
+    if (!pos) return fail(QMHA_ERR_INVALID, w + ": null pos (a device int32[B])");
+    if (paged && !table) return fail(QMHA_ERR_INVALID, w + ": null table (a device int32[B][max_pages])");
+    if (int st = packed_bound_check(c, w, "max_n", total, max_n, paged)) return st;
+    const std::string launch = "kv_cache " + w + " launch";
+    return cache_enqueue(
+        c, &ProfRec::pre, stream, launch.c_str(),
+        [&](int) {  // under the mutex: attach_tail writes `tail` under it
+            if (c->variant == QMHA_FA_TC_INT8_B && !c->tail)
+                return fail(QMHA_ERR_INVALID, w + ": an int8 cache needs its tail (qmha_kv_cache_attach_tail)");
+            return (int)QMHA_OK;
+        },
+        [&](const auto& ws, int) {
+            return qmha::launch_kv_packed(K, V, ws, static_cast<float*>(c->tail), c->B, total, max_n, c->cap, cu, pos, c->h_kv, c->D,
+                                          c->h_kv * c->D, (hipStream_t)stream, c->pages(table));
+        });
+}
+
+int attend_packed(qmha_kv_cache_t* c, const char* what, const float* Q, float* O, int total, int max_nq, const int32_t* cu,
+                  const int32_t* lens, const int32_t* table, bool paged, unsigned flags, void* stream) {
+    const std::string w = what;
+    if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+    if (int ck = check_cache_kind(c, paged, what)) return ck;
+    if (!Q || !O) return fail(QMHA_ERR_INVALID, "null tensor pointer");
+    if (!cu) return fail(QMHA_ERR_INVALID, w + ": null cu (a device int32[B + 1])");
+    if (!lens) return fail(QMHA_ERR_INVALID, w + ": null lens (a device int32[B])");
+    if (paged && !table) return fail(QMHA_ERR_INVALID, w + ": null table (a device int32[B][max_pages])");
+    if (flags != QMHA_FLAG_CAUSAL)
+        return fail(QMHA_ERR_INVALID, w + ": flags must be QMHA_FLAG_CAUSAL (the kernels have no mask but the diagonal)");
+    if (int st = packed_bound_check(c, w, "max_nq", total, max_nq, paged)) return st;
+    const std::string launch = "kv_cache " + w + " launch";
+    return cache_enqueue(c, &ProfRec::main, stream, launch.c_str(), kNoLenCheck, [&](const auto& ws, int) {
+        return qmha::launch_fa_packed(ws, Q, O, {c->B, max_nq, c->cap, c->h, c->h_kv, c->D, c->d_model, true, -1, lens, true, c->pages(table)},
+                                      cu, total, (hipStream_t)stream);
+    });
+}
+
+}  // namespace
+
+int qmha_kv_cache_append_packed(qmha_kv_cache_t* c, const float* K, const float* V, int total, int max_n, const int32_t* cu,
+                                const int32_t* pos, void* stream) {
+    return append_packed(c, "append_packed", K, V, total, max_n, cu, pos, nullptr, false, stream);
+}
+
+int qmha_kv_cache_append_paged_packed(qmha_kv_cache_t* c, const float* K, const float* V, int total, int max_n, const int32_t* cu,
+                                      const int32_t* pos, const int32_t* table, void* stream) {
+    return append_packed(c, "append_paged_packed", K, V, total, max_n, cu, pos, table, true, stream);
+}
+
+int qmha_attend_cached_packed(qmha_kv_cache_t* c, const float* Q, float* O, int total, int max_nq, const int32_t* cu,
+                              const int32_t* lens, unsigned flags, void* stream) {
+    return attend_packed(c, "attend_packed", Q, O, total, max_nq, cu, lens, nullptr, false, flags, stream);
+}
+
+int qmha_attend_cached_paged_packed(qmha_kv_cache_t* c, const float* Q, float* O, int total, int max_nq, const int32_t* cu,
+                                    const int32_t* lens, const int32_t* table, unsigned flags, void* stream) {
+    return attend_packed(c, "attend_paged_packed", Q, O, total, max_nq, cu, lens, table, true, flags, stream);
+}
+
 int qmha_solve_variant(const float* Q, const float* K, const float* V, float* O, int N, int d_model, int h,
                        int variant) {
     // blocking like the reference (launchers.h:64): hipStreamSynchronize.  r04 A/B: polling

@@ -9,7 +9,8 @@
 // lengths and query counts that are no multiple of 32 (Ragged).  And the paged kernels: the ragged
 // call over a pool of pages, each stage's K/V found through a block table on the device (Paged).
 // The split-KV kernels run the same bodies over Split<Ragged> / Split<Paged>, defined here, from
-// qmha_fa_split.hip.
+// qmha_fa_split.hip; the packed-batch kernels over Packed<Ragged> / Packed<Paged>, defined here, from
+// qmha_fa_packed.hip.
 //
 // Square causal: query row r attends keys j <= r of its own sequence (Nq = Nk = N).  Both kernels keep the
 // geometry of the non-causal main kernels, so they consume the unchanged pre-pass outputs (qmha_prepass.hip):
@@ -268,6 +269,31 @@ struct IsSplit : std::false_type {};
 template <class Geo>
 struct IsSplit<Split<Geo>> : std::true_type {};
 
+// Packed batches: Ragged's or Paged's call on operands without a batch axis.  Q and O are
+// [total, d_model]; sequence b owns the rows [cu[b], cu[b + 1]) (cu: DEVICE int32 [B + 1]), so it brings a query count
+// of its own, nq_b = cu[b + 1] - cu[b].  The host's Nq is the bound max_nq the grid is sized for (Ragged::max_units);
+// the kernel's prologue (qmha_fa_packed.hip) checks the range, nq_b and lens[b] and then forms the sequence's geometry
+// with of(): Base's geometry at Nq = nq_b -- what the unpacked call forms for a batch of that Nq --, and row0 = cu[b],
+// the first row of the sequence in Q and O, where the other geometries have b * Nq (seq_row0 below).
+template <class Base>
+struct Packed : Base {
+    const int32_t* cu;  // DEVICE int32 [B + 1]
+    int total;          // rows of Q and O
+    int row0;           // device: the sequence's first row
+    Packed(Base g, const int32_t* c, int t) : Base(g), cu(c), total(t), row0(0) {}
+    __device__ Packed of(int first, int nq, int L) const {
+        Packed v = *this;
+        v.Nq = nq;
+        static_cast<Base&>(v) = static_cast<const Base&>(v).of(L);
+        v.row0 = first;
+        return v;
+    }
+};
+template <class T>
+struct IsPacked : std::false_type {};
+template <class Base>
+struct IsPacked<Packed<Base>> : std::true_type {};
+
 // A lane's row of Q / O in memory is its row of the (padded) block less row_shift; row_real: that row exists.
 // Constants for every geometry but Ragged (and Paged over it), so the other instances carry no trace of them.
 template <class Geo>
@@ -291,6 +317,19 @@ template <class Geo>
 __device__ __forceinline__ int row_shift(const Split<Geo>& g) { return g.s; }
 template <class Geo>
 __device__ __forceinline__ bool row_real(const Split<Geo>& g, int row) { return (unsigned)(row - g.s) < (unsigned)g.Nq; }
+template <class Geo>
+__device__ __forceinline__ int row_shift(const Packed<Geo>& g) { return g.s; }
+template <class Geo>
+__device__ __forceinline__ bool row_real(const Packed<Geo>& g, int row) { return (unsigned)(row - g.s) < (unsigned)g.Nq; }
+// The first row of a sequence in Q and O: slice * Nq where the operands have a batch axis (slice: b, or Split's
+// (b, chunk) slice of the scratch); a packed sequence's cu[b].  kPackedGeo: the int8 body takes the second under
+// `if constexpr`, as it takes row_shift and row_real.
+template <class Geo>
+constexpr bool kPackedGeo = IsPacked<std::remove_cv_t<Geo>>::value;
+template <class Geo>
+__device__ __forceinline__ size_t seq_row0(const Geo& g, int slice) { return (size_t)slice * g.nq(); }
+template <class Geo>
+__device__ __forceinline__ size_t seq_row0(const Packed<Geo>& g, int) { return (size_t)g.row0; }
 // The tiles a workgroup may visit and where its stores go: every tile and O itself, but for Split its chunk and the
 // scratch's Oc, whose slice (b, c) has the layout of O's slice b.  Constants for every other geometry.
 template <class Geo>

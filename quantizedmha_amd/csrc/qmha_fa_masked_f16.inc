@@ -4,6 +4,8 @@
     // 0 / true for every geometry but Ragged, whose query rows sit `s` rows into their 32-row groups.  Split<Geo>
     // (DESIGN.md 19): one unit block of one chunk of tiles per workgroup -- tile_first / tile_end bound the sweep,
     // out_base / out_slice send the epilogue's O to the scratch, and the row's l and m are stored beside it.
+    // seq_row0(geo, slice): the first row of a sequence in Q / O, slice * Nq but for Packed<Geo> (DESIGN.md 20), whose
+    // sequences lie at cu[b] in operands without a batch axis.
     QMHA_ENABLE_AGPR_MFMA();
     asm volatile("" : "+v"(c_log2));  // a VOP3 fma reading an SGPR issues at the slow rate
     constexpr int WAVES = kWaves, SG = kSG;
@@ -51,7 +53,7 @@
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             if (active && row_real(geo, qg * QMHA_GROUP + 16 * qb + r16)) {  // a pad lane (Ragged) loads nothing
-                const float* qp = Qf + ((size_t)b * Nq + (size_t)qg * QMHA_GROUP + 16 * qb + r16 - row_shift(geo)) * d_model + (size_t)k * D +
+                const float* qp = Qf + (seq_row0(geo, b) + (size_t)qg * QMHA_GROUP + 16 * qb + r16 - row_shift(geo)) * d_model + (size_t)k * D +
                                   32 * ks + 8 * grp;
                 const v4f a = *reinterpret_cast<const v4f*>(qp), c = *reinterpret_cast<const v4f*>(qp + 4);
 #pragma unroll
@@ -219,7 +221,7 @@
             l += __shfl_xor(l, 16);
             l += __shfl_xor(l, 32);
             const bool ok = l > 1e-10f;  // fa_tc_v1a.cu:384-388
-            float* orow = out_base(geo, O) + ((size_t)out_slice(geo, b) * Nq + (size_t)qg * QMHA_GROUP + 16 * qb + r16 - row_shift(geo)) * d_model + (size_t)k * D + 4 * grp;
+            float* orow = out_base(geo, O) + (seq_row0(geo, out_slice(geo, b)) + (size_t)qg * QMHA_GROUP + 16 * qb + r16 - row_shift(geo)) * d_model + (size_t)k * D + 4 * grp;
             if (row_real(geo, qg * QMHA_GROUP + 16 * qb + r16)) {  // a pad lane stores nothing
 #pragma unroll
             for (int m = 0; m < DB; ++m) {

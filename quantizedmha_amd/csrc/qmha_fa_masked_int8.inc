@@ -4,6 +4,8 @@
     // are 0 / true for every geometry but Ragged, whose query rows sit `s` rows into their 32-row groups.  Split<Geo>
     // (DESIGN.md 19): one unit block of one chunk of tiles per workgroup -- tile_first / tile_end bound the sweep,
     // out_base / out_slice send the epilogue's O to the scratch, and the row's l and m are stored beside it.
+    // Packed<Geo> (DESIGN.md 20): the first row of a sequence in Q / O is seq_row0(geo, b) = cu[b], where every other
+    // geometry has b * Nq; under `if constexpr`, so the other instances' IR is what it was.
     constexpr int WAVES = kWaves, SG = kSG;
     constexpr int KS = D / 32;               // i8 MFMA k-steps (QK) and d-blocks (PV)
     constexpr int KBYTES = SG * 32 * D;      // K int8 per stage
@@ -53,6 +55,7 @@
     float cq = 0.0f;
     if (active) {
         const float* qrow = Qf + ((size_t)b * Nq + (size_t)qg * QMHA_GROUP + col) * d_model + (size_t)k * D;
+        if constexpr (kPackedGeo<decltype(geo)>) qrow = Qf + (seq_row0(geo, b) + (size_t)qg * QMHA_GROUP + col) * d_model + (size_t)k * D;
         if constexpr (kRaggedGeo<decltype(geo)>) qrow -= (size_t)row_shift(geo) * d_model;
         v4f x[KS][4];
         float amax = 0.0f;
@@ -268,6 +271,7 @@
         }
         const bool ok = l > 1e-20f;
         float* orow = out_base(geo, O) + ((size_t)out_slice(geo, b) * Nq + (size_t)qg * QMHA_GROUP + col) * d_model + (size_t)k * D + 4 * half;
+        if constexpr (kPackedGeo<decltype(geo)>) orow = O + (seq_row0(geo, b) + (size_t)qg * QMHA_GROUP + col) * d_model + (size_t)k * D + 4 * half;
         if constexpr (kRaggedGeo<decltype(geo)>) orow -= (size_t)row_shift(geo) * d_model;
         if (kRaggedGeo<decltype(geo)> ? row_real(geo, qg * QMHA_GROUP + col) : true)  // a pad lane (Ragged) stores nothing
 #pragma unroll

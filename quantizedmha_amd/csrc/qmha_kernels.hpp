@@ -273,6 +273,27 @@ hipError_t launch_kv_tokens(const float* K, const float* V, const Int8Workspace&
 hipError_t launch_kv_tokens(const float* K, const float* V, const F16Workspace& w, float* tail, int B, int n, int cap,
                             const int32_t* pos, int H, int D, int d_model, hipStream_t stream, const PageTable& pt = {});
 
+// ---- packed batches (qmha_fa_packed.hip, qmha_prepass.hip) ---------------------------------
+// The token-granular / paged attend and append on operands without a batch axis: Q, O [total, d_model], K, V
+// [rows, H * D], and cu (DEVICE int32 [B + 1], read by the kernels) gives sequence b the rows [cu[b], cu[b + 1]).
+// Attend: c is a token-granular call as launch_fa_masked takes it (ragged, with lens; a table: paged) whose Nq is the
+// bound max_nq the grid is sized for, 1 <= max_nq <= min(total, Nk).  A sequence with 1 <= nq_b <= max_nq rows and
+// nq_b <= lens[b] <= Nk gets the bits of that call at Nq = nq_b; nq_b == 0: it sits out; a range outside
+// 0 <= cu[b] <= cu[b + 1] <= total: nothing of it is read or written; any other: its rows of O are zeros.
+// Append: launch_kv_tokens with n_b = cu[b + 1] - cu[b] rows for sequence b, 1 <= max_n <= min(rows, cap) the bound the
+// items are sized for; n_b == 0, n_b > max_n, a bad range, pos[b] < 0 or pos[b] + n_b > cap (or a touched table entry
+// outside the pool): that sequence writes nothing, the tail included.  Bad host arguments: hipErrorInvalidValue.
+hipError_t launch_fa_packed(const Int8Workspace& w, const float* Qf, float* O, const MaskedCall& c, const int32_t* cu, int total,
+                            hipStream_t stream);
+hipError_t launch_fa_packed(const F16Workspace& w, const float* Qf, float* O, const MaskedCall& c, const int32_t* cu, int total,
+                            hipStream_t stream);
+hipError_t launch_kv_packed(const float* K, const float* V, const Int8Workspace& w, float* tail, int B, int rows, int max_n, int cap,
+                            const int32_t* cu, const int32_t* pos, int H, int D, int d_model, hipStream_t stream,
+                            const PageTable& pt = {});
+hipError_t launch_kv_packed(const float* K, const float* V, const F16Workspace& w, float* tail, int B, int rows, int max_n, int cap,
+                            const int32_t* cu, const int32_t* pos, int H, int D, int d_model, hipStream_t stream,
+                            const PageTable& pt = {});
+
 // ---- FP32 (fa: scalar VALU kernel; fa_mfma: the same contract on v_mfma_f32_32x32x2_f32) -----
 hipError_t launch_fa_f32(const float* Q, const float* K, const float* V, float* O, int B, int N, int H, int D,
                          int d_model, bool mfma, hipStream_t stream);

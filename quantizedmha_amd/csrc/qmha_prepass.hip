@@ -13,6 +13,9 @@
 //                           again from its raw rows (qmha_kv_cache_append_tokens)
 //   qmha_kv_paged_{int8,f16}_kernel   the token kernels' groups in the pages of a pool, found through a block table
 //                           on the device (qmha_kv_cache_append_paged)
+//   qmha_kv_packed_{int8,f16}_kernel, qmha_kv_packed_pages_{int8,f16}_kernel   the token / paged kernels with a row
+//                           count per sequence, read from a device cu[B + 1] over K / V without a batch axis
+//                           (qmha_kv_cache_append_packed / _paged_packed)
 #include <atomic>
 
 #include "qmha_common.hpp"
@@ -477,6 +480,121 @@ __global__ __launch_bounds__(256) void qmha_kv_paged_f16_kernel(
     const size_t src = (size_t)(it.bh / H) * n * d_model + (size_t)(it.bh % H) * D;
     if (blockIdx.y == 1) token_groups_f16<D, true>(V + src, Kh, Vt, vtr[threadIdx.x >> 6], it, n, groups, d_model);
     else token_groups_f16<D, false>(K + src, Kh, Vt, vtr[threadIdx.x >> 6], it, n, groups, d_model);
+}
+
+// ---------------------------------------------------------------------------------------
+// Packed append (qmha_kv_cache_append_packed / _paged_packed): K and V are [total, H * D] with no batch
+// axis, and sequence b brings the n_b = cu[b + 1] - cu[b] rows [cu[b], cu[b + 1]) (cu: DEVICE int32 [B + 1]) to cache
+// rows [pos[b], pos[b] + n_b).  The token kernels' items, groups and tail protocol, with n and the source row taken
+// from the device: a slice has `maxg` items sized for the host's bound max_n (token_items is monotone, so they suffice
+// for every n_b <= max_n), item 0 runs group g0 and then g1 -- reading the tail before it rewrites it --, and the items
+// beyond a sequence's own groups return.  A wave returns with nothing written, the tail included, when the range is not
+// 0 <= cu[b] <= cu[b + 1] <= total (it never becomes an address), when n_b == 0 (pos[b] is not looked at), n_b > max_n,
+// pos[b] < 0 or pos[b] + n_b > cap; every wave of a sequence reads the same words, so they agree.  The item is per wave
+// and is held in scalar registers, as paged_item's.
+// ---------------------------------------------------------------------------------------
+struct PackedItem {
+    TokenItem it;
+    int n, row0;  // the sequence's rows, and the first of them in K / V
+};
+__device__ __forceinline__ PackedItem packed_item(const int32_t* __restrict__ cu, const int32_t* __restrict__ pos, int rows, int max_n,
+                                                  int cap, int H, int maxg, int total) {
+    PackedItem r{{0, 0, -1, 0, 0}, 0, 0};
+    const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (item >= total) return r;
+    r.it.bh = item / maxg, r.it.j = item % maxg;
+    const int b = r.it.bh / H;
+    const int c0 = __builtin_amdgcn_readfirstlane(cu[b]), c1 = __builtin_amdgcn_readfirstlane(cu[b + 1]);
+    if (c0 < 0 || c1 < c0 || c1 > rows) return r;
+    const int n = c1 - c0;
+    if (n == 0 || n > max_n) return r;
+    const int p = __builtin_amdgcn_readfirstlane(pos[b]);
+    if (p < 0 || p > cap - n) return r;
+    r.n = n, r.row0 = c0;
+    r.it.g0 = p / QMHA_GROUP, r.it.g1 = (p + n - 1) / QMHA_GROUP;
+    if (r.it.j == 0 || r.it.j < r.it.g1 - r.it.g0) r.it.p = p;
+    return r;
+}
+// paged_item's scan of the table entries that rows [pos[b], pos[b] + n_b) touch: one outside the pool and the item returns
+__device__ __forceinline__ void packed_scan(TokenItem& it, const PagedTable& t, int H) {
+    if (it.p < 0) return;
+    const int32_t* row = t.table + (size_t)(it.bh / H) * t.max_pages;
+    const int c0 = (unsigned)it.g0 / (unsigned)t.PG, c1 = (unsigned)it.g1 / (unsigned)t.PG;  // <= max_pages - 1: p + n_b <= cap
+    bool bad = false;
+    for (int c = c0 + (threadIdx.x & 63); c <= c1; c += 64) bad |= (unsigned)row[c] >= (unsigned)t.num_pages;
+    if (__builtin_amdgcn_ballot_w64(bad)) it.p = -1;
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void qmha_kv_packed_int8_kernel(
+    const float* __restrict__ K, const float* __restrict__ V, int8_t* __restrict__ Ki, _Float16* __restrict__ Vh,
+    float* __restrict__ sK, float* __restrict__ sV, float* __restrict__ tail, int B, int rows, int max_n, int cap,
+    const int32_t* __restrict__ cu, const int32_t* __restrict__ pos, int H, int d_model, int maxg, int total) {
+    __shared__ __attribute__((aligned(16))) char vtr[4][D * QMHA_VT_PITCH];
+    const PackedItem pk = packed_item(cu, pos, rows, max_n, cap, H, maxg, total);
+    const TokenItem it = pk.it;
+    if (it.p < 0) return;  // wave-uniform; the LDS tile is per wave, no workgroup barrier follows
+    const int b = it.bh / H, k = it.bh % H;
+    const size_t col = (size_t)k * D + 4 * ((threadIdx.x & 63) % (D / 4));  // this lane's columns of a row
+    const size_t src = (size_t)pk.row0 * d_model + col, trow = (size_t)b * QMHA_GROUP * d_model + col;
+    if (blockIdx.y == 1)
+        token_groups_int8<D, true>(V + src, tail + (size_t)B * QMHA_GROUP * d_model + trow, Ki, Vh, sV, vtr[threadIdx.x >> 6], it, pk.n,
+                                   ContiguousGroups{cap / QMHA_GROUP}, d_model);
+    else
+        token_groups_int8<D, false>(K + src, tail + trow, Ki, Vh, sK, vtr[threadIdx.x >> 6], it, pk.n, ContiguousGroups{cap / QMHA_GROUP},
+                                    d_model);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void qmha_kv_packed_f16_kernel(
+    const float* __restrict__ K, const float* __restrict__ V, _Float16* __restrict__ Kh, _Float16* __restrict__ Vt,
+    int rows, int max_n, int cap, const int32_t* __restrict__ cu, const int32_t* __restrict__ pos, int H, int d_model, int maxg,
+    int total) {
+    __shared__ __attribute__((aligned(16))) char vtr[4][D * QMHA_VT_PITCH];
+    const PackedItem pk = packed_item(cu, pos, rows, max_n, cap, H, maxg, total);
+    const TokenItem it = pk.it;
+    if (it.p < 0) return;  // wave-uniform; the LDS tile is per wave, no workgroup barrier follows
+    const size_t src = (size_t)pk.row0 * d_model + (size_t)(it.bh % H) * D;
+    if (blockIdx.y == 1) token_groups_f16<D, true>(V + src, Kh, Vt, vtr[threadIdx.x >> 6], it, pk.n, ContiguousGroups{cap / QMHA_GROUP}, d_model);
+    else token_groups_f16<D, false>(K + src, Kh, Vt, vtr[threadIdx.x >> 6], it, pk.n, ContiguousGroups{cap / QMHA_GROUP}, d_model);
+}
+
+// Over a pool of pages: the logical capacity is max_pages * page_rows, the touched entries are scanned, the groups looked up
+template <int D>
+__global__ __launch_bounds__(256) void qmha_kv_packed_pages_int8_kernel(
+    const float* __restrict__ K, const float* __restrict__ V, int8_t* __restrict__ Ki, _Float16* __restrict__ Vh,
+    float* __restrict__ sK, float* __restrict__ sV, float* __restrict__ tail, int B, int rows, int max_n,
+    const int32_t* __restrict__ cu, const int32_t* __restrict__ pos, PagedTable t, int H, int d_model, int maxg, int total) {
+    __shared__ __attribute__((aligned(16))) char vtr[4][D * QMHA_VT_PITCH];
+    const PackedItem pk = packed_item(cu, pos, rows, max_n, t.max_pages * t.PG * QMHA_GROUP, H, maxg, total);
+    TokenItem it = pk.it;
+    packed_scan(it, t, H);
+    if (it.p < 0) return;  // wave-uniform; the LDS tile is per wave, no workgroup barrier follows
+    const int b = it.bh / H, k = it.bh % H;
+    const PagedGroups groups = paged_groups(t, it, H);
+    const size_t col = (size_t)k * D + 4 * ((threadIdx.x & 63) % (D / 4));  // this lane's columns of a row
+    const size_t src = (size_t)pk.row0 * d_model + col, trow = (size_t)b * QMHA_GROUP * d_model + col;
+    if (blockIdx.y == 1)
+        token_groups_int8<D, true>(V + src, tail + (size_t)B * QMHA_GROUP * d_model + trow, Ki, Vh, sV, vtr[threadIdx.x >> 6], it, pk.n,
+                                   groups, d_model);
+    else
+        token_groups_int8<D, false>(K + src, tail + trow, Ki, Vh, sK, vtr[threadIdx.x >> 6], it, pk.n, groups, d_model);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void qmha_kv_packed_pages_f16_kernel(
+    const float* __restrict__ K, const float* __restrict__ V, _Float16* __restrict__ Kh, _Float16* __restrict__ Vt,
+    int rows, int max_n, const int32_t* __restrict__ cu, const int32_t* __restrict__ pos, PagedTable t, int H, int d_model, int maxg,
+    int total) {
+    __shared__ __attribute__((aligned(16))) char vtr[4][D * QMHA_VT_PITCH];
+    const PackedItem pk = packed_item(cu, pos, rows, max_n, t.max_pages * t.PG * QMHA_GROUP, H, maxg, total);
+    TokenItem it = pk.it;
+    packed_scan(it, t, H);
+    if (it.p < 0) return;  // wave-uniform; the LDS tile is per wave, no workgroup barrier follows
+    const PagedGroups groups = paged_groups(t, it, H);
+    const size_t src = (size_t)pk.row0 * d_model + (size_t)(it.bh % H) * D;
+    if (blockIdx.y == 1) token_groups_f16<D, true>(V + src, Kh, Vt, vtr[threadIdx.x >> 6], it, pk.n, groups, d_model);
+    else token_groups_f16<D, false>(K + src, Kh, Vt, vtr[threadIdx.x >> 6], it, pk.n, groups, d_model);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1010,6 +1128,46 @@ hipError_t launch_kv_tokens(const float* K, const float* V, const F16Workspace& 
         }
         hipLaunchKernelGGL((qmha_kv_token_f16_kernel<decltype(d)::value>), dim3((total + 3) / 4, 2), dim3(256), 0, stream, K, V, w.Kh,
                            w.Vt, n, cap, pos, H, d_model, maxg, total);
+        return hipGetLastError();
+    });
+}
+
+// ---- packed append: rows [cu[b], cu[b + 1]) of K / V to rows [pos[b], ...) of sequence b ----
+static bool kv_packed_shape_ok(int B, int rows, int max_n, int cap, const int32_t* cu, const int32_t* pos, int H) {
+    return cu && rows >= 1 && max_n <= rows && kv_tokens_shape_ok(B, max_n, cap, pos, H) &&
+           (long long)B * H * token_items(max_n) <= 0x7fffffffLL;
+}
+
+hipError_t launch_kv_packed(const float* K, const float* V, const Int8Workspace& w, float* tail, int B, int rows, int max_n, int cap,
+                            const int32_t* cu, const int32_t* pos, int H, int D, int d_model, hipStream_t stream, const PageTable& pt) {
+    if (!kv_packed_shape_ok(B, rows, max_n, cap, cu, pos, H) || !tail || !kv_pages_ok(pt, cap)) return hipErrorInvalidValue;
+    const int maxg = token_items(max_n), total = B * H * maxg;
+    return int8_masked_d(D, [&](auto d) {
+        if (pt.table) {
+            hipLaunchKernelGGL((qmha_kv_packed_pages_int8_kernel<decltype(d)::value>), dim3((total + 3) / 4, 2), dim3(256), 0, stream, K, V,
+                               w.Ki, w.Vh, w.sK, w.sV, tail, B, rows, max_n, cu, pos,
+                               PagedTable{pt.table, pt.page_rows / QMHA_GROUP, pt.max_pages, pt.num_pages}, H, d_model, maxg, total);
+            return hipGetLastError();
+        }
+        hipLaunchKernelGGL((qmha_kv_packed_int8_kernel<decltype(d)::value>), dim3((total + 3) / 4, 2), dim3(256), 0, stream, K, V, w.Ki,
+                           w.Vh, w.sK, w.sV, tail, B, rows, max_n, cap, cu, pos, H, d_model, maxg, total);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_kv_packed(const float* K, const float* V, const F16Workspace& w, float*, int B, int rows, int max_n, int cap,
+                            const int32_t* cu, const int32_t* pos, int H, int D, int d_model, hipStream_t stream, const PageTable& pt) {
+    if (!kv_packed_shape_ok(B, rows, max_n, cap, cu, pos, H) || !kv_pages_ok(pt, cap)) return hipErrorInvalidValue;
+    const int maxg = token_items(max_n), total = B * H * maxg;
+    return f16_masked_d(D, [&](auto d) {
+        if (pt.table) {
+            hipLaunchKernelGGL((qmha_kv_packed_pages_f16_kernel<decltype(d)::value>), dim3((total + 3) / 4, 2), dim3(256), 0, stream, K, V,
+                               w.Kh, w.Vt, rows, max_n, cu, pos, PagedTable{pt.table, pt.page_rows / QMHA_GROUP, pt.max_pages, pt.num_pages},
+                               H, d_model, maxg, total);
+            return hipGetLastError();
+        }
+        hipLaunchKernelGGL((qmha_kv_packed_f16_kernel<decltype(d)::value>), dim3((total + 3) / 4, 2), dim3(256), 0, stream, K, V, w.Kh,
+                           w.Vt, rows, max_n, cap, cu, pos, H, d_model, maxg, total);
         return hipGetLastError();
     });
 }

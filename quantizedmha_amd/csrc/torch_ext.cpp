@@ -24,6 +24,8 @@
 //     (qmha_kv_cache_create_paged / qmha_kv_cache_append_paged / qmha_attend_cached_paged);
 //   * all three caches' `enable_split` / `attend_tokens_split` (`attend_paged_split`) / `split_partials`: the attend with
 //     the key sweep in chunks over a scratch the object owns (qmha_attend_cached_tokens_split / _paged_split);
+//   * all three caches' `append_packed` / `attend_packed` (`append_paged_packed` / `attend_paged_packed`): a count per
+//     sequence from a device cu[B + 1] over operands without a batch axis (qmha_kv_cache_append_packed / ..._paged_packed);
 //   * a rejected shape raises (TORCH_CHECK on the C-ABI status) instead of a device assert.
 #include <torch/extension.h>
 // ROCm PyTorch reports HIP devices as device type "cuda": the guard / current-stream
@@ -167,6 +169,33 @@ static Tensor cache_rows(const Tensor& X, const char* name, int64_t width, int64
     TORCH_CHECK(Xc.dim() == 3 && Xc.size(0) == B && Xc.size(2) == width, name, " must be [B = ", B, ", n, d_model = ", width, "]",
                 B == 1 ? " or [n, d_model]" : "");
     return Xc;
+}
+
+// A packed operand: fp32 [total, width] on the cache's device, contiguous, no batch axis
+static Tensor cache_packed_rows(const Tensor& X, const char* name, int64_t width, const c10::Device& device) {
+    TORCH_CHECK(X.is_cuda(), "Inputs must be CUDA tensors");
+    TORCH_CHECK(X.dtype() == torch::kFloat32, name, " must be float32");
+    TORCH_CHECK(X.device() == device, name, " must be on the cache's device");
+    auto Xc = X.contiguous();
+    TORCH_CHECK(Xc.dim() == 2 && Xc.size(0) >= 1 && Xc.size(1) == width, name, " must be [total, d_model = ", width,
+                "] (packed: no batch axis)");
+    return Xc;
+}
+// cu: int32 [B + 1] on the cache's device, contiguous: the kernel reads it, the host does not
+static void cache_cu(const Tensor& t, int64_t B, const c10::Device& device) {
+    TORCH_CHECK(t.is_cuda(), "cu must be a CUDA tensor");
+    TORCH_CHECK(t.dtype() == torch::kInt32, "cu must be int32");
+    TORCH_CHECK(t.device() == device, "cu must be on the cache's device");
+    TORCH_CHECK(t.dim() == 1 && t.size(0) == B + 1 && t.is_contiguous(), "cu must be a contiguous tensor of shape [B + 1 = ", B + 1, "]");
+}
+// O of a packed attend: the caller's, of Q's shape, or zeros (rows outside every range are not written by the call)
+static Tensor packed_out(const std::optional<Tensor>& out_opt, const Tensor& Qc) {
+    if (!out_opt) return torch::zeros_like(Qc);
+    const Tensor& out = *out_opt;
+    TORCH_CHECK(out.is_cuda() && out.dtype() == torch::kFloat32 && out.device() == Qc.device() && out.is_contiguous() &&
+                    out.sizes() == Qc.sizes(),
+                "out must be a contiguous float32 CUDA tensor of Q's shape on Q's device");
+    return out;
 }
 
 // The split-KV scratch of a cache (enable_split; include/launchers.h has the layout): what both cache classes keep for
@@ -343,6 +372,32 @@ public:
         return out_opt ? out : out.view(Q.sizes());
     }
 
+    // append_tokens with a row count per sequence (qmha_kv_cache_append_packed): K, V [total, num_kv_heads * d], cu int32 [B + 1]
+    void append_packed(const Tensor& K, const Tensor& V, const Tensor& cu, const Tensor& pos, int64_t max_n) {
+        auto Kc = cache_packed_rows(K, "K", kv_model_, mem_.device()), Vc = cache_packed_rows(V, "V", kv_model_, mem_.device());
+        TORCH_CHECK(Kc.sizes() == Vc.sizes(), "K and V must have the same shape");
+        cache_cu(cu, B_, mem_.device());
+        per_seq(pos, "pos");
+        const OnStream on = current_stream(mem_.device());
+        const int st = qmha_kv_cache_append_packed(handle_, Kc.data_ptr<float>(), Vc.data_ptr<float>(), static_cast<int>(Kc.size(0)),
+                                                   static_cast<int>(max_n), cu.data_ptr<int32_t>(), pos.data_ptr<int32_t>(), on.stream);
+        TORCH_CHECK(st == QMHA_OK, "KVCache.append_packed", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+    }
+
+    // attend_tokens with a query count per sequence (qmha_attend_cached_packed): Q [total, d_model], cu int32 [B + 1]
+    Tensor attend_packed(const Tensor& Q, const Tensor& cu, const Tensor& lens, int64_t max_nq, std::optional<Tensor> out_opt) {
+        auto Qc = cache_packed_rows(Q, "Q", d_model_, mem_.device());
+        cache_cu(cu, B_, mem_.device());
+        per_seq(lens, "lens");
+        Tensor out = packed_out(out_opt, Qc);
+        const OnStream on = current_stream(mem_.device());
+        const int st = qmha_attend_cached_packed(handle_, Qc.data_ptr<float>(), out.data_ptr<float>(), static_cast<int>(Qc.size(0)),
+                                                 static_cast<int>(max_nq), cu.data_ptr<int32_t>(), lens.data_ptr<int32_t>(),
+                                                 QMHA_FLAG_CAUSAL, on.stream);
+        TORCH_CHECK(st == QMHA_OK, "KVCache.attend_packed", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+        return out;
+    }
+
 private:
     void per_seq(const Tensor& t, const char* name) const { cache_per_seq(t, name, B_, mem_.device()); }
     Tensor rows(const Tensor& X, const char* name, int64_t width) const { return cache_rows(X, name, width, B_, mem_.device()); }
@@ -448,6 +503,36 @@ public:
         return out_opt ? out : out.view(Q.sizes());
     }
 
+    // append_packed through the block table (qmha_kv_cache_append_paged_packed)
+    void append_paged_packed(const Tensor& K, const Tensor& V, const Tensor& cu, const Tensor& pos, const Tensor& table, int64_t max_n) {
+        auto Kc = cache_packed_rows(K, "K", kv_model_, mem_.device()), Vc = cache_packed_rows(V, "V", kv_model_, mem_.device());
+        TORCH_CHECK(Kc.sizes() == Vc.sizes(), "K and V must have the same shape");
+        cache_cu(cu, B_, mem_.device());
+        cache_per_seq(pos, "pos", B_, mem_.device());
+        check_table(table);
+        const OnStream on = current_stream(mem_.device());
+        const int st = qmha_kv_cache_append_paged_packed(handle_, Kc.data_ptr<float>(), Vc.data_ptr<float>(), static_cast<int>(Kc.size(0)),
+                                                         static_cast<int>(max_n), cu.data_ptr<int32_t>(), pos.data_ptr<int32_t>(),
+                                                         table.data_ptr<int32_t>(), on.stream);
+        TORCH_CHECK(st == QMHA_OK, "PagedKVCache.append_paged_packed", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+    }
+
+    // attend_packed through the block table (qmha_attend_cached_paged_packed)
+    Tensor attend_paged_packed(const Tensor& Q, const Tensor& cu, const Tensor& lens, const Tensor& table, int64_t max_nq,
+                               std::optional<Tensor> out_opt) {
+        auto Qc = cache_packed_rows(Q, "Q", d_model_, mem_.device());
+        cache_cu(cu, B_, mem_.device());
+        cache_per_seq(lens, "lens", B_, mem_.device());
+        check_table(table);
+        Tensor out = packed_out(out_opt, Qc);
+        const OnStream on = current_stream(mem_.device());
+        const int st = qmha_attend_cached_paged_packed(handle_, Qc.data_ptr<float>(), out.data_ptr<float>(), static_cast<int>(Qc.size(0)),
+                                                       static_cast<int>(max_nq), cu.data_ptr<int32_t>(), lens.data_ptr<int32_t>(),
+                                                       table.data_ptr<int32_t>(), QMHA_FLAG_CAUSAL, on.stream);
+        TORCH_CHECK(st == QMHA_OK, "PagedKVCache.attend_paged_packed", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+        return out;
+    }
+
 private:
     // the block table: int32 [B, max_pages] on the cache's device, contiguous: the kernel reads it, the host does not
     void check_table(const Tensor& t) const {
@@ -491,6 +576,14 @@ PYBIND11_MODULE(torch_ext, m) {
              "attend_paged with the key sweep in chunks and a combine pass: attend_tokens_split through the table, bit for bit.")
         .def("split_partials", &PagedKVCache::split_partials, pybind11::arg("Nq"),
              "(Oc, m, l) views of the scratch: what the last split attend of Nq rows left per chunk.")
+        .def("append_paged_packed", &PagedKVCache::append_paged_packed, pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("cu"),
+             pybind11::arg("pos"), pybind11::arg("table"), pybind11::arg("max_n"),
+             "append_paged with a row count per sequence: K, V [total, num_kv_heads * d], rows [cu[b], cu[b + 1]) are sequence b's;\n"
+             "cu: int32 [B + 1] on the device, read by the kernel; max_n: an upper bound of the counts.")
+        .def("attend_paged_packed", &PagedKVCache::attend_paged_packed, pybind11::arg("Q"), pybind11::arg("cu"), pybind11::arg("lens"),
+             pybind11::arg("table"), pybind11::arg("max_nq"), pybind11::arg("out") = pybind11::none(),
+             "attend_paged with a query count per sequence: Q [total, d_model], rows [cu[b], cu[b + 1]) are sequence b's;\n"
+             "max_nq: an upper bound of the counts.")
         .def_property_readonly("split_scratch", &PagedKVCache::split_scratch)
         .def_property_readonly("tail", &PagedKVCache::tail)
         .def_property_readonly("cap", &PagedKVCache::cap)
@@ -526,6 +619,14 @@ PYBIND11_MODULE(torch_ext, m) {
              "attend_tokens with the key sweep in chunks and a combine pass, for a decode step on long sequences.")
         .def("split_partials", &KVCache::split_partials, pybind11::arg("Nq"),
              "(Oc, m, l) views of the scratch: what the last split attend of Nq rows left per chunk.")
+        .def("append_packed", &KVCache::append_packed, pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("cu"), pybind11::arg("pos"),
+             pybind11::arg("max_n"),
+             "append_tokens with a row count per sequence: K, V [total, num_kv_heads * d], rows [cu[b], cu[b + 1]) are sequence b's;\n"
+             "cu: int32 [B + 1] on the device, read by the kernel; max_n: an upper bound of the counts.")
+        .def("attend_packed", &KVCache::attend_packed, pybind11::arg("Q"), pybind11::arg("cu"), pybind11::arg("lens"),
+             pybind11::arg("max_nq"), pybind11::arg("out") = pybind11::none(),
+             "attend_tokens with a query count per sequence: Q [total, d_model], rows [cu[b], cu[b + 1]) are sequence b's;\n"
+             "max_nq: an upper bound of the counts.")
         .def_property_readonly("split_scratch", &KVCache::split_scratch)
         .def_property_readonly("tail", &KVCache::tail)
         .def_property_readonly("len", &KVCache::len)

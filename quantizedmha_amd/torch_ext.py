@@ -178,7 +178,9 @@ class KVCache:
     enable_tokens() once, then append_tokens(K, V, pos) / attend_tokens(Q, lens): the same at any length -- a prompt of
     1000 rows, a decode step of one (qmha_kv_cache_append_tokens / qmha_attend_cached_tokens; causal only).
     enable_split(chunk_rows) once, then attend_tokens_split(Q, lens): attend_tokens with the key sweep cut into chunks and
-    a combine pass (qmha_attend_cached_tokens_split), for a decode step on long sequences."""
+    a combine pass (qmha_attend_cached_tokens_split), for a decode step on long sequences.
+    append_packed(K, V, cu, pos, max_n) / attend_packed(Q, cu, lens, max_nq): the token calls with a count per sequence --
+    packed [total, ...] operands and an int32 [B + 1] cu on the device, for a step that mixes prefill and decode."""
 
     def __init__(self, B: int, cap: int, d_model: int, num_heads: int, kernel: str = _lib.DEFAULT_KERNEL, device="cuda"):
         self._setup(B, cap, d_model, num_heads, None, kernel, device)
@@ -395,6 +397,68 @@ class KVCache:
         _lib.check(st, f"KVCache.attend_tokens_split({self.kernel})")
         return out.view(Q.shape) if out.numel() == Q.numel() and out.dim() != Q.dim() else out
 
+    def _packed_rows(self, X: torch.Tensor, name: str, width: int) -> torch.Tensor:
+        """A packed operand: float32 [total, width] on the cache's device, no batch axis."""
+        if not isinstance(X, torch.Tensor) or not X.is_cuda:
+            raise RuntimeError("Inputs must be CUDA tensors")
+        if X.dtype != torch.float32:
+            raise RuntimeError(f"{name} must be float32")
+        if X.device != self.device:
+            raise RuntimeError(f"{name} must be on the cache's device {self.device}")
+        Xc = X.contiguous()
+        if Xc.dim() != 2 or Xc.shape[0] < 1 or Xc.shape[1] != width:
+            raise RuntimeError(f"{name} must be [total, d_model = {width}] (packed: no batch axis)")
+        return Xc
+
+    def _cu(self, t: torch.Tensor) -> torch.Tensor:
+        """cu: int32 [B + 1] on the cache's device, read by the kernel when it runs (not by the host)."""
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("cu must be a CUDA tensor")
+        if t.dtype != torch.int32:
+            raise RuntimeError("cu must be int32")
+        if t.device != self.device:
+            raise RuntimeError(f"cu must be on the cache's device {self.device}")
+        if t.dim() != 1 or t.shape[0] != self.B + 1 or not t.is_contiguous():
+            raise RuntimeError(f"cu must be a contiguous tensor of shape [B + 1 = {self.B + 1}]")
+        return t
+
+    def _packed_out(self, out: Optional[torch.Tensor], Qc: torch.Tensor) -> torch.Tensor:
+        if out is None:  # zeros: rows outside every range are not written by the call
+            return torch.zeros_like(Qc)
+        if not out.is_cuda or out.dtype != torch.float32 or out.device != Qc.device or not out.is_contiguous() or out.shape != Qc.shape:
+            raise RuntimeError("out must be a contiguous float32 CUDA tensor of Q's shape on Q's device")
+        return out
+
+    def append_packed(self, K: torch.Tensor, V: torch.Tensor, cu: torch.Tensor, pos: torch.Tensor, max_n: int) -> None:
+        """append_tokens with a row count per sequence (qmha_kv_cache_append_packed): K, V are [total, num_kv_heads * d]
+        with no batch axis, sequence b brings the rows [cu[b], cu[b + 1]) to cache rows [pos[b], ...).  cu: int32 [B + 1],
+        pos: int32 [B], both on the device and read by the kernel -- the tensors themselves, so a captured call follows
+        later changes of them.  max_n: an upper bound of the counts, 1 <= max_n <= min(total, cap).  An empty sequence
+        sits out; one with more than max_n rows, a range outside [0, total] or an invalid pos[b] writes nothing."""
+        Kc, Vc = self._packed_rows(K, "K", self.kv_model), self._packed_rows(V, "V", self.kv_model)
+        if Kc.shape != Vc.shape:
+            raise RuntimeError("K and V must have the same shape")
+        cu, pos = self._cu(cu), self._per_seq(pos, "pos")
+        with _current_stream(self.device) as stream:
+            st = _lib.load().qmha_kv_cache_append_packed(self._handle, Kc.data_ptr(), Vc.data_ptr(), Kc.shape[0], int(max_n),
+                                                         cu.data_ptr(), pos.data_ptr(), stream)
+        _lib.check(st, f"KVCache.append_packed({self.kernel})")
+
+    def attend_packed(self, Q: torch.Tensor, cu: torch.Tensor, lens: torch.Tensor, max_nq: int,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """attend_tokens with a query count per sequence (qmha_attend_cached_packed): Q is [total, d_model] with no batch
+        axis, rows [cu[b], cu[b + 1]) are sequence b's, and each sequence gets the rows attend_tokens writes for a batch
+        of its own count.  max_nq: an upper bound of the counts, 1 <= max_nq <= min(total, cap).  An empty sequence sits
+        out; one with more than max_nq rows or an invalid lens[b] gets zeros; rows outside every range are not written."""
+        Qc = self._packed_rows(Q, "Q", self.d_model)
+        cu, lens = self._cu(cu), self._per_seq(lens, "lens")
+        out = self._packed_out(out, Qc)
+        with _current_stream(self.device) as stream:
+            st = _lib.load().qmha_attend_cached_packed(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[0], int(max_nq),
+                                                       cu.data_ptr(), lens.data_ptr(), _lib.QMHA_FLAG_CAUSAL, stream)
+        _lib.check(st, f"KVCache.attend_packed({self.kernel})")
+        return out
+
 
 class GroupedKVCache(KVCache):
     """KVCache for grouped-query attention (qmha_kv_cache_create_gqa): the cache holds num_kv_heads K/V heads shared
@@ -510,6 +574,37 @@ class PagedKVCache:
                                                             self.split_scratch.numel(), _lib.QMHA_FLAG_CAUSAL, stream)
         _lib.check(st, f"PagedKVCache.attend_paged_split({self.kernel})")
         return out.view(Q.shape) if out.numel() == Q.numel() and out.dim() != Q.dim() else out
+
+    _packed_rows = KVCache._packed_rows
+    _cu = KVCache._cu
+    _packed_out = KVCache._packed_out
+
+    def append_paged_packed(self, K: torch.Tensor, V: torch.Tensor, cu: torch.Tensor, pos: torch.Tensor, table: torch.Tensor,
+                            max_n: int) -> None:
+        """append_packed through the table (qmha_kv_cache_append_paged_packed): K, V [total, num_kv_heads * d], sequence
+        b's rows [cu[b], cu[b + 1]) go to its logical rows [pos[b], ...); append_paged's rules per sequence."""
+        Kc, Vc = self._packed_rows(K, "K", self.kv_model), self._packed_rows(V, "V", self.kv_model)
+        if Kc.shape != Vc.shape:
+            raise RuntimeError("K and V must have the same shape")
+        cu, pos, table = self._cu(cu), self._per_seq(pos, "pos"), self._table(table)
+        with _current_stream(self.device) as stream:
+            st = _lib.load().qmha_kv_cache_append_paged_packed(self._handle, Kc.data_ptr(), Vc.data_ptr(), Kc.shape[0], int(max_n),
+                                                               cu.data_ptr(), pos.data_ptr(), table.data_ptr(), stream)
+        _lib.check(st, f"PagedKVCache.append_paged_packed({self.kernel})")
+
+    def attend_paged_packed(self, Q: torch.Tensor, cu: torch.Tensor, lens: torch.Tensor, table: torch.Tensor, max_nq: int,
+                            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """attend_packed through the table (qmha_attend_cached_paged_packed): Q [total, d_model], rows [cu[b], cu[b + 1])
+        are sequence b's; attend_paged's rules per sequence."""
+        Qc = self._packed_rows(Q, "Q", self.d_model)
+        cu, lens, table = self._cu(cu), self._per_seq(lens, "lens"), self._table(table)
+        out = self._packed_out(out, Qc)
+        with _current_stream(self.device) as stream:
+            st = _lib.load().qmha_attend_cached_paged_packed(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[0], int(max_nq),
+                                                             cu.data_ptr(), lens.data_ptr(), table.data_ptr(), _lib.QMHA_FLAG_CAUSAL,
+                                                             stream)
+        _lib.check(st, f"PagedKVCache.attend_paged_packed({self.kernel})")
+        return out
 
 
 def quantize_int8(X: torch.Tensor, d_model: int, num_heads: int, layout: int = 0):

@@ -31,7 +31,8 @@ BIN = os.path.join(ROOT, "quantizedmha_amd", "bin")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-KERNEL_SOURCES = ["qmha_fa_int8.hip", "qmha_fa_f16.hip", "qmha_fa_masked.hip", "qmha_fa_split.hip", "qmha_prepass.hip",
+KERNEL_SOURCES = ["qmha_fa_int8.hip", "qmha_fa_f16.hip", "qmha_fa_masked.hip", "qmha_fa_split.hip", "qmha_fa_packed.hip",
+                  "qmha_prepass.hip",
                   "qmha_fa_f32.hip", "qmha_unfused.hip", "qmha_api.cpp"]
 # profiling builds (QMHA_EXTRA_FLAGS=-DQMHA_ABLATION) enable the tuning alternatives of the fp16 / fp32 / api
 # sources.  The r01-r03 int8 experiment source (ablation perturbations, ring / DMA-split / TSHADOW / ACC1
@@ -40,7 +41,7 @@ KERNEL_SOURCES = ["qmha_fa_int8.hip", "qmha_fa_f16.hip", "qmha_fa_masked.hip", "
 # (tools/ablation/qmha_fa_int8_ablation.hip).  Int8 ablation builds compile the production source.
 VARIANTS = {"fa": 0, "fa_tc_v1a": 1, "fa_tc_int8_b": 2, "unfused": 3, "fa_mfma": 4, "fa_tc_int8_pt": 5}
 DRIVER_SOURCES = ["driver/main.cpp", "driver/data.cpp", "driver/verify.cpp"]
-# (qmha_fa_masked.hip: qmha_fa_split.hip includes its text)
+# (qmha_fa_masked.hip: qmha_fa_split.hip and qmha_fa_packed.hip include its text)
 HEADERS = ["qmha_common.hpp", "qmha_kernels.hpp", "qmha_fa_masked.hip", "qmha_fa_masked_int8.inc", "qmha_fa_masked_f16.inc",
            "qmha_kv_append_int8.inc", "qmha_kv_append_f16.inc", "driver/data.h", "driver/verify.h"]
 
@@ -83,6 +84,7 @@ FILE_FLAGS = {"qmha_fa_int8.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + os
               "qmha_fa_f16.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + os.environ.get("QMHA_F16_FLAGS", "").split(),
               "qmha_fa_masked.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + os.environ.get("QMHA_CAUSAL_FLAGS", "").split(),
               "qmha_fa_split.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + os.environ.get("QMHA_CAUSAL_FLAGS", "").split(),
+              "qmha_fa_packed.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + os.environ.get("QMHA_CAUSAL_FLAGS", "").split(),
               "qmha_fa_f32.hip": os.environ.get("QMHA_F32_FLAGS", "").split()}
 
 

@@ -572,6 +572,82 @@ int check_cache_kind(const qmha_kv_cache* c, bool paged_call, const char* what) 
                                                                     "qmha_kv_cache_append_paged / qmha_attend_cached_paged"));
 }
 
+// One token-granular call on a cache: the entry point's name in messages, and whether it is one of the
+// paged kind (then `table` is an argument and cap reads "max_pages * page_rows").  Each check of these entry points is
+// written once here; an entry point strings them in the order they win.
+struct CacheCall {
+    qmha_kv_cache* c;
+    const char* what;
+    bool paged;
+    int bad(const std::string& why) const { return fail(QMHA_ERR_INVALID, std::string(what) + ": " + why); }
+    std::string cap() const { return std::string("cap = ") + (paged ? "max_pages * page_rows = " : "") + std::to_string(c->cap); }
+    std::string label() const { return std::string("kv_cache ") + what + " launch"; }
+    // the cache, its kind and the call's two tensors
+    int operands(const void* a, const void* b) const {
+        if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+        if (int ck = check_cache_kind(c, paged, what)) return ck;
+        if (!a || !b) return fail(QMHA_ERR_INVALID, "null tensor pointer");
+        return QMHA_OK;
+    }
+    // a device array: `name` is "pos (a device int32[B])"
+    int words(const int32_t* p, const char* name) const { return p ? (int)QMHA_OK : bad(std::string("null ") + name); }
+    int table(const int32_t* t) const { return paged ? words(t, "table (a device int32[B][max_pages])") : (int)QMHA_OK; }
+    // an attend's lens, table and flags
+    int attend_words(const int32_t* lens, const int32_t* t, unsigned flags) const {
+        if (int st = words(lens, "lens (a device int32[B])")) return st;
+        if (int st = table(t)) return st;
+        if (flags != QMHA_FLAG_CAUSAL) return bad("flags must be QMHA_FLAG_CAUSAL (the kernels have no mask but the diagonal)");
+        return QMHA_OK;
+    }
+    // a row count every sequence shares (n, Nq): 1 <= rows <= cap
+    int rows(const char* name, int n) const {
+        if (n >= 1 && n <= c->cap) return QMHA_OK;
+        return bad(std::string(name) + " = " + std::to_string(n) + " rows, needs 1 <= " + name + " <= " + cap());
+    }
+    // a packed call's rows and the bound its grid is sized for: 1 <= bound <= min(total, cap)
+    int bound(const char* name, int total, int b) const {
+        if (total < 1) return bad("total = " + std::to_string(total) + " rows, needs total >= 1");
+        if (b >= 1 && b <= total && b <= c->cap) return QMHA_OK;
+        return bad(std::string(name) + " = " + std::to_string(b) + ", needs 1 <= " + name + " <= min(total = " + std::to_string(total) + ", " +
+                   cap() + ")");
+    }
+    // an append, under the mutex (attach_tail writes `tail` under it)
+    int tail() const {
+        if (c->variant == QMHA_FA_TC_INT8_B && !c->tail) return bad("an int8 cache needs its tail (qmha_kv_cache_attach_tail)");
+        return QMHA_OK;
+    }
+    // the token-granular attend's call, over the cache's pages when it has some (Nq: the rows, or a packed call's bound)
+    qmha::MaskedCall attend(int Nq, const int32_t* lens, const int32_t* t) const {
+        return {c->B, Nq, c->cap, c->h, c->h_kv, c->D, c->d_model, true, -1, lens, true, c->pages(t)};
+    }
+};
+
+// The uniform-count append (qmha_kv_cache_append_tokens / _paged): `table` null is the contiguous one
+int append_rows(const CacheCall& k, const float* K, const float* V, int n, const int32_t* pos, const int32_t* table, void* stream) {
+    if (int st = k.operands(K, V)) return st;
+    if (int st = k.words(pos, "pos (a device int32[B])")) return st;
+    if (int st = k.table(table)) return st;
+    if (int st = k.rows("n", n)) return st;
+    const qmha_kv_cache* c = k.c;
+    return cache_enqueue(
+        k.c, &ProfRec::pre, stream, k.label().c_str(), [&](int) { return k.tail(); },
+        [&](const auto& w, int) {
+            return qmha::launch_kv_tokens(K, V, w, static_cast<float*>(c->tail), c->B, n, c->cap, pos, c->h_kv, c->D, c->h_kv * c->D,
+                                          (hipStream_t)stream, c->pages(table));
+        });
+}
+
+// The uniform-count attend (qmha_attend_cached_tokens / _paged)
+int attend_rows(const CacheCall& k, const float* Q, float* O, int Nq, const int32_t* lens, const int32_t* table, unsigned flags,
+                void* stream) {
+    if (int st = k.operands(Q, O)) return st;
+    if (int st = k.attend_words(lens, table, flags)) return st;
+    if (int st = k.rows("Nq", Nq)) return st;
+    return cache_enqueue(k.c, &ProfRec::main, stream, k.label().c_str(), kNoLenCheck, [&](const auto& w, int) {
+        return qmha::launch_fa_masked(w, Q, O, k.attend(Nq, lens, table), (hipStream_t)stream);
+    });
+}
+
 }  // namespace
 
 int qmha::tune_config(const char* env_name) {
@@ -786,39 +862,12 @@ int qmha_kv_cache_attach_tail(qmha_kv_cache_t* c, void* mem, size_t bytes) {
 }
 
 int qmha_kv_cache_append_tokens(qmha_kv_cache_t* c, const float* K, const float* V, int n, const int32_t* pos, void* stream) {
-    if (!c) return fail(QMHA_ERR_INVALID, "null cache");
-    if (int ck = check_cache_kind(c, false, "append_tokens")) return ck;
-    if (!K || !V) return fail(QMHA_ERR_INVALID, "null tensor pointer");
-    if (!pos) return fail(QMHA_ERR_INVALID, "append_tokens: null pos (a device int32[B])");
-    if (n < 1 || n > c->cap)
-        return fail(QMHA_ERR_INVALID, "append_tokens: n = " + std::to_string(n) + " rows, needs 1 <= n <= cap = " + std::to_string(c->cap));
-    return cache_enqueue(
-        c, &ProfRec::pre, stream, "kv_cache append_tokens launch",
-        [&](int) {  // under the mutex: attach_tail writes `tail` under it
-            if (c->variant == QMHA_FA_TC_INT8_B && !c->tail)
-                return fail(QMHA_ERR_INVALID, "append_tokens: an int8 cache needs its tail (qmha_kv_cache_attach_tail)");
-            return (int)QMHA_OK;
-        },
-        [&](const auto& w, int) {
-            return qmha::launch_kv_tokens(K, V, w, static_cast<float*>(c->tail), c->B, n, c->cap, pos, c->h_kv, c->D, c->h_kv * c->D,
-                                          (hipStream_t)stream);
-        });
+    return append_rows({c, "append_tokens", false}, K, V, n, pos, nullptr, stream);
 }
 
 int qmha_attend_cached_tokens(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, const int32_t* lens, unsigned flags,
                               void* stream) {
-    if (!c) return fail(QMHA_ERR_INVALID, "null cache");
-    if (int ck = check_cache_kind(c, false, "attend_tokens")) return ck;
-    if (!Q || !O) return fail(QMHA_ERR_INVALID, "null tensor pointer");
-    if (!lens) return fail(QMHA_ERR_INVALID, "attend_tokens: null lens (a device int32[B])");
-    if (flags != QMHA_FLAG_CAUSAL)
-        return fail(QMHA_ERR_INVALID, "attend_tokens: flags must be QMHA_FLAG_CAUSAL (the kernels have no mask but the diagonal)");
-    if (Nq < 1 || Nq > c->cap)
-        return fail(QMHA_ERR_INVALID, "attend_tokens: Nq = " + std::to_string(Nq) + " rows, needs 1 <= Nq <= cap = " + std::to_string(c->cap));
-    return cache_enqueue(c, &ProfRec::main, stream, "kv_cache attend_tokens launch", kNoLenCheck, [&](const auto& w, int) {
-        return qmha::launch_fa_masked(w, Q, O, {c->B, Nq, c->cap, c->h, c->h_kv, c->D, c->d_model, true, -1, lens, true},
-                                      (hipStream_t)stream);
-    });
+    return attend_rows({c, "attend_tokens", false}, Q, O, Nq, lens, nullptr, flags, stream);
 }
 
 // ---- paged caches: a pool of pages and a block table read on the device --------------------
@@ -861,43 +910,12 @@ int qmha_kv_cache_create_paged(qmha_kv_cache_t** out, void* mem, size_t bytes, i
 
 int qmha_kv_cache_append_paged(qmha_kv_cache_t* c, const float* K, const float* V, int n, const int32_t* pos, const int32_t* table,
                                void* stream) {
-    if (!c) return fail(QMHA_ERR_INVALID, "null cache");
-    if (int ck = check_cache_kind(c, true, "append_paged")) return ck;
-    if (!K || !V) return fail(QMHA_ERR_INVALID, "null tensor pointer");
-    if (!pos) return fail(QMHA_ERR_INVALID, "append_paged: null pos (a device int32[B])");
-    if (!table) return fail(QMHA_ERR_INVALID, "append_paged: null table (a device int32[B][max_pages])");
-    if (n < 1 || n > c->cap)
-        return fail(QMHA_ERR_INVALID, "append_paged: n = " + std::to_string(n) + " rows, needs 1 <= n <= cap = max_pages * page_rows = " +
-                                          std::to_string(c->cap));
-    return cache_enqueue(
-        c, &ProfRec::pre, stream, "kv_cache append_paged launch",
-        [&](int) {  // under the mutex: attach_tail writes `tail` under it
-            if (c->variant == QMHA_FA_TC_INT8_B && !c->tail)
-                return fail(QMHA_ERR_INVALID, "append_paged: an int8 cache needs its tail (qmha_kv_cache_attach_tail)");
-            return (int)QMHA_OK;
-        },
-        [&](const auto& w, int) {
-            return qmha::launch_kv_tokens(K, V, w, static_cast<float*>(c->tail), c->B, n, c->cap, pos, c->h_kv, c->D, c->h_kv * c->D,
-                                          (hipStream_t)stream, c->pages(table));
-        });
+    return append_rows({c, "append_paged", true}, K, V, n, pos, table, stream);
 }
 
 int qmha_attend_cached_paged(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, const int32_t* lens, const int32_t* table,
                              unsigned flags, void* stream) {
-    if (!c) return fail(QMHA_ERR_INVALID, "null cache");
-    if (int ck = check_cache_kind(c, true, "attend_paged")) return ck;
-    if (!Q || !O) return fail(QMHA_ERR_INVALID, "null tensor pointer");
-    if (!lens) return fail(QMHA_ERR_INVALID, "attend_paged: null lens (a device int32[B])");
-    if (!table) return fail(QMHA_ERR_INVALID, "attend_paged: null table (a device int32[B][max_pages])");
-    if (flags != QMHA_FLAG_CAUSAL)
-        return fail(QMHA_ERR_INVALID, "attend_paged: flags must be QMHA_FLAG_CAUSAL (the kernels have no mask but the diagonal)");
-    if (Nq < 1 || Nq > c->cap)
-        return fail(QMHA_ERR_INVALID, "attend_paged: Nq = " + std::to_string(Nq) + " rows, needs 1 <= Nq <= cap = max_pages * page_rows = " +
-                                          std::to_string(c->cap));
-    return cache_enqueue(c, &ProfRec::main, stream, "kv_cache attend_paged launch", kNoLenCheck, [&](const auto& w, int) {
-        return qmha::launch_fa_masked(w, Q, O, {c->B, Nq, c->cap, c->h, c->h_kv, c->D, c->d_model, true, -1, lens, true, c->pages(table)},
-                                      (hipStream_t)stream);
-    });
+    return attend_rows({c, "attend_paged", true}, Q, O, Nq, lens, table, flags, stream);
 }
 
 // ---- split-KV: the token-granular and the paged attend with the key sweep cut into chunks -----------
@@ -911,30 +929,20 @@ size_t split_bytes(const qmha_kv_cache* c, int Nq, int chunk_rows) {
 // both entry points: `table` null is the contiguous one
 int attend_split(qmha_kv_cache_t* c, const char* what, const float* Q, float* O, int Nq, const int32_t* lens, const int32_t* table,
                  bool paged, int chunk_rows, void* scratch, size_t scratch_bytes, unsigned flags, void* stream) {
-    const std::string w = what;
-    if (!c) return fail(QMHA_ERR_INVALID, "null cache");
-    if (int ck = check_cache_kind(c, paged, what)) return ck;
-    if (!Q || !O) return fail(QMHA_ERR_INVALID, "null tensor pointer");
-    if (!lens) return fail(QMHA_ERR_INVALID, w + ": null lens (a device int32[B])");
-    if (paged && !table) return fail(QMHA_ERR_INVALID, w + ": null table (a device int32[B][max_pages])");
-    if (flags != QMHA_FLAG_CAUSAL)
-        return fail(QMHA_ERR_INVALID, w + ": flags must be QMHA_FLAG_CAUSAL (the kernels have no mask but the diagonal)");
-    if (Nq < 1 || Nq > c->cap)
-        return fail(QMHA_ERR_INVALID, w + ": Nq = " + std::to_string(Nq) + " rows, needs 1 <= Nq <= cap = " +
-                                          (paged ? "max_pages * page_rows = " : "") + std::to_string(c->cap));
+    const CacheCall k{c, what, paged};
+    if (int st = k.operands(Q, O)) return st;
+    if (int st = k.attend_words(lens, table, flags)) return st;
+    if (int st = k.rows("Nq", Nq)) return st;
     if (!split_chunk_ok(c, chunk_rows))
-        return fail(QMHA_ERR_INVALID, w + ": chunk_rows = " + std::to_string(chunk_rows) + " must be a multiple of 64 with 64 <= chunk_rows <= cap = " +
-                                          std::to_string(c->cap) + " (a chunk is a whole number of two-tile stages)");
-    if (!scratch) return fail(QMHA_ERR_INVALID, w + ": null scratch (qmha_attend_split_bytes bytes of device memory)");
-    if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return fail(QMHA_ERR_INVALID, w + ": scratch must be 256-byte aligned");
+        return k.bad("chunk_rows = " + std::to_string(chunk_rows) + " must be a multiple of 64 with 64 <= chunk_rows <= cap = " +
+                     std::to_string(c->cap) + " (a chunk is a whole number of two-tile stages)");
+    if (!scratch) return k.bad("null scratch (qmha_attend_split_bytes bytes of device memory)");
+    if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return k.bad("scratch must be 256-byte aligned");
     const size_t need = split_bytes(c, Nq, chunk_rows);
     if (scratch_bytes < need)
-        return fail(QMHA_ERR_INVALID, w + ": scratch too small: " + std::to_string(scratch_bytes) + " bytes, qmha_attend_split_bytes is " +
-                                          std::to_string(need));
-    const std::string launch = "kv_cache " + w + " launch";
-    return cache_enqueue(c, &ProfRec::main, stream, launch.c_str(), kNoLenCheck, [&](const auto& ws, int) {  // one pair around both launches
-        return qmha::launch_fa_split(ws, Q, O, {c->B, Nq, c->cap, c->h, c->h_kv, c->D, c->d_model, true, -1, lens, true, c->pages(table)},
-                                     chunk_rows, scratch, (hipStream_t)stream);
+        return k.bad("scratch too small: " + std::to_string(scratch_bytes) + " bytes, qmha_attend_split_bytes is " + std::to_string(need));
+    return cache_enqueue(c, &ProfRec::main, stream, k.label().c_str(), kNoLenCheck, [&](const auto& ws, int) {  // one pair around both launches
+        return qmha::launch_fa_split(ws, Q, O, k.attend(Nq, lens, table), chunk_rows, scratch, (hipStream_t)stream);
     });
 }
 
@@ -958,35 +966,17 @@ int qmha_attend_cached_paged_split(qmha_kv_cache_t* c, const float* Q, float* O,
 // ---- packed batches: a query / append count per sequence from a device cu[B + 1], no batch axis -----------
 namespace {
 
-// the bound a packed call's grid is sized for: 1 <= bound <= min(total, cap)
-int packed_bound_check(const qmha_kv_cache* c, const std::string& w, const char* name, int total, int bound, bool paged) {
-    if (total < 1) return fail(QMHA_ERR_INVALID, w + ": total = " + std::to_string(total) + " rows, needs total >= 1");
-    if (bound < 1 || bound > total || bound > c->cap)
-        return fail(QMHA_ERR_INVALID, w + ": " + name + " = " + std::to_string(bound) + ", needs 1 <= " + name + " <= min(total = " +
-                                          std::to_string(total) + ", cap = " + (paged ? "max_pages * page_rows = " : "") +
-                                          std::to_string(c->cap) + ")");
-    return QMHA_OK;
-}
-
 // both append entry points: `table` null is the contiguous one
 int append_packed(qmha_kv_cache_t* c, const char* what, const float* K, const float* V, int total, int max_n, const int32_t* cu,
                   const int32_t* pos, const int32_t* table, bool paged, void* stream) {
-    const std::string w = what;
-    if (!c) return fail(QMHA_ERR_INVALID, "null cache");
-    if (int ck = check_cache_kind(c, paged, what)) return ck;
-    if (!K || !V) return fail(QMHA_ERR_INVALID, "null tensor pointer");
-    if (!cu) return fail(QMHA_ERR_INVALID, w + ": null cu (a device int32[B + 1])");
-    if (!pos) return fail(QMHA_ERR_INVALID, w + ": null pos (a device int32[B])");
-    if (paged && !table) return fail(QMHA_ERR_INVALID, w + ": null table (a device int32[B][max_pages])");
-    if (int st = packed_bound_check(c, w, "max_n", total, max_n, paged)) return st;
-    const std::string launch = "kv_cache " + w + " launch";
+    const CacheCall k{c, what, paged};
+    if (int st = k.operands(K, V)) return st;
+    if (int st = k.words(cu, "cu (a device int32[B + 1])")) return st;
+    if (int st = k.words(pos, "pos (a device int32[B])")) return st;
+    if (int st = k.table(table)) return st;
+    if (int st = k.bound("max_n", total, max_n)) return st;
     return cache_enqueue(
-        c, &ProfRec::pre, stream, launch.c_str(),
-        [&](int) {  // under the mutex: attach_tail writes `tail` under it
-            if (c->variant == QMHA_FA_TC_INT8_B && !c->tail)
-                return fail(QMHA_ERR_INVALID, w + ": an int8 cache needs its tail (qmha_kv_cache_attach_tail)");
-            return (int)QMHA_OK;
-        },
+        c, &ProfRec::pre, stream, k.label().c_str(), [&](int) { return k.tail(); },
         [&](const auto& ws, int) {
             return qmha::launch_kv_packed(K, V, ws, static_cast<float*>(c->tail), c->B, total, max_n, c->cap, cu, pos, c->h_kv, c->D,
                                           c->h_kv * c->D, (hipStream_t)stream, c->pages(table));
@@ -995,20 +985,13 @@ int append_packed(qmha_kv_cache_t* c, const char* what, const float* K, const fl
 
 int attend_packed(qmha_kv_cache_t* c, const char* what, const float* Q, float* O, int total, int max_nq, const int32_t* cu,
                   const int32_t* lens, const int32_t* table, bool paged, unsigned flags, void* stream) {
-    const std::string w = what;
-    if (!c) return fail(QMHA_ERR_INVALID, "null cache");
-    if (int ck = check_cache_kind(c, paged, what)) return ck;
-    if (!Q || !O) return fail(QMHA_ERR_INVALID, "null tensor pointer");
-    if (!cu) return fail(QMHA_ERR_INVALID, w + ": null cu (a device int32[B + 1])");
-    if (!lens) return fail(QMHA_ERR_INVALID, w + ": null lens (a device int32[B])");
-    if (paged && !table) return fail(QMHA_ERR_INVALID, w + ": null table (a device int32[B][max_pages])");
-    if (flags != QMHA_FLAG_CAUSAL)
-        return fail(QMHA_ERR_INVALID, w + ": flags must be QMHA_FLAG_CAUSAL (the kernels have no mask but the diagonal)");
-    if (int st = packed_bound_check(c, w, "max_nq", total, max_nq, paged)) return st;
-    const std::string launch = "kv_cache " + w + " launch";
-    return cache_enqueue(c, &ProfRec::main, stream, launch.c_str(), kNoLenCheck, [&](const auto& ws, int) {
-        return qmha::launch_fa_packed(ws, Q, O, {c->B, max_nq, c->cap, c->h, c->h_kv, c->D, c->d_model, true, -1, lens, true, c->pages(table)},
-                                      cu, total, (hipStream_t)stream);
+    const CacheCall k{c, what, paged};
+    if (int st = k.operands(Q, O)) return st;
+    if (int st = k.words(cu, "cu (a device int32[B + 1])")) return st;
+    if (int st = k.attend_words(lens, table, flags)) return st;
+    if (int st = k.bound("max_nq", total, max_nq)) return st;
+    return cache_enqueue(c, &ProfRec::main, stream, k.label().c_str(), kNoLenCheck, [&](const auto& ws, int) {
+        return qmha::launch_fa_packed(ws, Q, O, k.attend(max_nq, lens, table), cu, total, (hipStream_t)stream);
     });
 }
 

@@ -2,21 +2,22 @@
 // (MI355X): the key sweep of a decode step cut into chunks of whole stages, a workgroup per (K/V slice, unit block,
 // chunk), and a combine pass.  The partial kernels are the bodies of qmha_fa_masked.hip's kernels once more
 // (qmha_fa_masked_{int8,f16}.inc), over Split<Ragged> and Split<Paged>; the geometries, the stager and masked_geo are
-// that file's text, included without its kernels.
-#define QMHA_FA_SPLIT_TU
-#include "qmha_fa_masked.hip"
+// the shared header's.
+#include "qmha_fa_masked.hpp"
 
 namespace qmha {
 
 // ---------------------------------------------------------------------------------------
-// Split-KV (Split, above): the ragged / paged prologue over the same bodies, a workgroup per (K/V slice,
-// unit block, chunk).  The partial kernels write the scratch only; an invalid sequence (its length, or a used table
-// entry outside the pool) leaves at once -- workgroup-uniform, before the body's first barrier or DMA issue -- and the
-// combine kernel writes its zeros.  Two plain launches on one stream: no atomics, no flags, no waiting on a workgroup.
+// Split-KV (Split, qmha_fa_masked.hpp): the ragged / paged prologue over the same bodies, a workgroup per
+// (K/V slice, unit block, chunk); one template per precision over Base = Ragged or Paged.  A template of its own beside
+// the cache kernels: it has no O argument (adding one would move every kernarg offset).  The partial kernels write the
+// scratch only; an invalid sequence (its length, or a used table entry outside the pool) leaves at once --
+// workgroup-uniform, before the body's first barrier or DMA issue -- and the combine kernel writes its zeros.  Two plain
+// launches on one stream: no atomics, no flags, no waiting on a workgroup.
 // The launch bounds are the ragged siblings', but for int8 d = 32: at the siblings' seven waves per SIMD (72 VGPRs) the
 // paged instance spilled 12 bytes; with six it needs no scratch.
 // ---------------------------------------------------------------------------------------
-template <int D, class Base = Ragged>
+template <int D, class Base>
 __global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : D > 32 ? 4 : 6) void qmha_fa_int8_split_kernel(
     const float* __restrict__ Qf, const int8_t* __restrict__ Ki, const _Float16* __restrict__ Vh,
     const float* __restrict__ sK, const float* __restrict__ sV, Split<Base> any, const int32_t* __restrict__ lens, int H,
@@ -34,45 +35,8 @@ __global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : D > 32 ? 4 : 6) void qmha
 #include "qmha_fa_masked_int8.inc"
 }
 
-template <int D, class Base = Ragged>
+template <int D, class Base>
 __global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_f16_split_kernel(
-    const float* __restrict__ Qf, const _Float16* __restrict__ Kh, const _Float16* __restrict__ Vt, Split<Base> any,
-    const int32_t* __restrict__ lens, int H, int d_model, int nqb, float c_log2) {
-    using Geo = Split<Base>;
-    float* const O = nullptr;  // the body's stores go to out_base(geo, O): the scratch
-    int bh_, qb_, c_;
-    split_wg(nqb, any.NC, bh_, qb_, c_);  // the body forms the same triple again
-    const int L = lens[bh_ / H];
-    if (!any.valid(L)) return;
-    if constexpr (kPagedGeo<Base>) {
-        if (!any.used_pages_ok(bh_ / H, L)) return;
-    }
-    const Geo geo = any.of(L, c_);
-#include "qmha_fa_masked_f16.inc"
-}
-
-// A paged cache: the same two kernels under names of their own, as the ragged and the paged kernels are (every kernel
-// template of the library has one instance per head size)
-template <int D, class Base = Paged>
-__global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : D > 32 ? 4 : 6) void qmha_fa_int8_split_pages_kernel(
-    const float* __restrict__ Qf, const int8_t* __restrict__ Ki, const _Float16* __restrict__ Vh,
-    const float* __restrict__ sK, const float* __restrict__ sV, Split<Base> any, const int32_t* __restrict__ lens, int H,
-    int d_model, int nqb, float c_log2) {
-    using Geo = Split<Base>;
-    float* const O = nullptr;  // the body's stores go to out_base(geo, O): the scratch
-    int bh_, qb_, c_;
-    split_wg(nqb, any.NC, bh_, qb_, c_);  // the body forms the same triple again
-    const int L = lens[bh_ / H];
-    if (!any.valid(L)) return;
-    if constexpr (kPagedGeo<Base>) {
-        if (!any.used_pages_ok(bh_ / H, L)) return;
-    }
-    const Geo geo = any.of(L, c_);
-#include "qmha_fa_masked_int8.inc"
-}
-
-template <int D, class Base = Paged>
-__global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_f16_split_pages_kernel(
     const float* __restrict__ Qf, const _Float16* __restrict__ Kh, const _Float16* __restrict__ Vt, Split<Base> any,
     const int32_t* __restrict__ lens, int H, int d_model, int nqb, float c_log2) {
     using Geo = Split<Base>;
@@ -154,12 +118,8 @@ static hipError_t fa_split_launch(const Int8Workspace& w, const float* Qf, float
     const Split<Geo> sg(geo, s, chunk_rows / QMHA_GROUP, NC);
     const dim3 grid(c.B * c.Hkv * nqb * NC), block(kWaves * 64);
     const hipError_t e = int8_masked_d(c.D, [&](auto d) {
-        if constexpr (kPagedGeo<Geo>)
-            hipLaunchKernelGGL((qmha_fa_int8_split_pages_kernel<decltype(d)::value>), grid, block, 0, stream, Qf, w.Ki, w.Vh, w.sK, w.sV, sg,
-                               c.lens, c.Hkv, c.d_model, nqb, softmax_scale_log2(c.D));
-        else
-            hipLaunchKernelGGL((qmha_fa_int8_split_kernel<decltype(d)::value>), grid, block, 0, stream, Qf, w.Ki, w.Vh, w.sK, w.sV, sg,
-                               c.lens, c.Hkv, c.d_model, nqb, softmax_scale_log2(c.D));
+        hipLaunchKernelGGL((qmha_fa_int8_split_kernel<decltype(d)::value, Geo>), grid, block, 0, stream, Qf, w.Ki, w.Vh, w.sK, w.sV, sg,
+                           c.lens, c.Hkv, c.d_model, nqb, softmax_scale_log2(c.D));
         return hipGetLastError();
     });
     if (e != hipSuccess) return e;
@@ -176,12 +136,8 @@ static hipError_t fa_split_launch(const F16Workspace& w, const float* Qf, float*
     const Split<Geo> sg(geo, s, chunk_rows / QMHA_GROUP, NC);
     const dim3 grid(c.B * c.Hkv * nqb * NC), block(kWaves * 64);
     const hipError_t e = f16_masked_d(c.D, [&](auto d) {
-        if constexpr (kPagedGeo<Geo>)
-            hipLaunchKernelGGL((qmha_fa_f16_split_pages_kernel<decltype(d)::value>), grid, block, 0, stream, Qf, w.Kh, w.Vt, sg, c.lens,
-                               c.Hkv, c.d_model, nqb, softmax_scale_log2(c.D));
-        else
-            hipLaunchKernelGGL((qmha_fa_f16_split_kernel<decltype(d)::value>), grid, block, 0, stream, Qf, w.Kh, w.Vt, sg, c.lens,
-                               c.Hkv, c.d_model, nqb, softmax_scale_log2(c.D));
+        hipLaunchKernelGGL((qmha_fa_f16_split_kernel<decltype(d)::value, Geo>), grid, block, 0, stream, Qf, w.Kh, w.Vt, sg, c.lens,
+                           c.Hkv, c.d_model, nqb, softmax_scale_log2(c.D));
         return hipGetLastError();
     });
     if (e != hipSuccess) return e;

@@ -3,7 +3,7 @@ and the yardstick builders that define what a packed call must return.
 
 The restatement follows the kernels line by line -- tests/test_packed_cpu.py ties its formulas to the source with
 verbatim line checks -- and never touches a GPU:
-  * packed_seq / ragged_geo: the attend prologue (qmha_fa_packed.hip's packed_seq, Ragged::of): the validity rules, nq_b,
+  * packed_seq / ragged_geo: the attend prologue (qmha_fa_masked.hpp's packed_seq, Ragged::of): the validity rules, nq_b,
     s, Nq', Ga, GL, diag_off, and the memory row of a lane;
   * packed_item / item_groups: the append's items (qmha_prepass.hip's packed_item, token_groups_*): g0, g1, the source
     row, and maxg from max_n.
@@ -41,7 +41,7 @@ def ragged_geo(nq, L):
 
 
 def packed_seq(c0, c1, total, max_nq, L, cap, pages_ok=True):
-    """packed_seq of qmha_fa_packed.hip for a sequence with cu[b] = c0, cu[b + 1] = c1: (verdict, row0, nq_b).  L is looked
+    """packed_seq of qmha_fa_masked.hpp for a sequence with cu[b] = c0, cu[b + 1] = c1: (verdict, row0, nq_b).  L is looked
     at only when the range is in bounds, not empty and within max_nq; pages_ok: the paged kernels' table scan."""
     if c0 < 0 or c1 < c0 or c1 > total:
         return SKIP, 0, 0

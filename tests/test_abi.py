@@ -199,6 +199,11 @@ def test_production_library_has_one_kernel_per_variant_and_d(built):
                 masked_dumps.append((f"{name}[{twin.group(1)}]", d))
                 continue
             name += "[%s]" % re.match(r"NS_\d+([A-Za-z]+?)E", rest).group(1)
+        if re.fullmatch(r"qmha_fa_(int8|f16)_(cache|split)_kernel", name):  # <D, geometry>, as the masked templates
+            # the attends of a persistent K/V cache are one template per precision: one instance per geometry and
+            # head size (Ragged, Paged, Packed<Ragged>, Packed<Paged>; the split template: its base, Ragged or Paged)
+            g = re.match(r"NS_\d+([A-Za-z]+?)(?:INS_\d+([A-Za-z]+?)EE)?E", rest)
+            name += "[%s]" % (g.group(1) if g.group(2) is None else "%s<%s>" % g.groups())
         if name == "qmha_fa_int8_pipe_kernel":  # <D, WAVES, FL>
             m, fl = re.match(r"Li(\d+)ELi(\d+)E", rest), 2
         elif name == "qmha_fa_int8_kernel":  # <D, FL> (the one-tile kernel: N = 32, and d outside 32/64/128)
@@ -223,6 +228,11 @@ def test_production_library_has_one_kernel_per_variant_and_d(built):
     assert sorted(masked_dumps) == sorted(k for k in per if k[0] in plain), masked_dumps
     assert len(masked_dumps) == 6, masked_dumps
     assert sorted(d for n, d in per if n == "qmha_fa_int8_masked_kernel[Grouped]") == ["128", "32", "64"], sorted(per)
+    # the cache and split templates: exactly their geometries at every built head size, no dumping twin
+    for stem, ds in (("int8", ["128", "32", "64"]), ("f16", ["128", "64"])):
+        for family, geos in (("cache", ("Ragged", "Paged", "Packed<Ragged>", "Packed<Paged>")), ("split", ("Ragged", "Paged"))):
+            got = sorted(k for k in per if k[0].startswith(f"qmha_fa_{stem}_{family}_kernel"))
+            assert got == sorted((f"qmha_fa_{stem}_{family}_kernel[{g}]", d) for g in geos for d in ds), got
     for name, d, twin in dumps:  # exactly the production schedule (same WAVES, flags, PAD) plus the stores
         if name == "qmha_fa_int8_pt_v3_kernel":  # the 8-wave production instance (the 4-wave one has no twin)
             assert twin in per[(name, d)], (name, d, twin)

@@ -115,6 +115,68 @@ def test_attend_varlen_unknown_flags_win_over_null_lens(lib, cache):
     assert st == INVALID and "unknown flag bits 2" in msg and "lens" not in msg, (st, msg)
 
 
+@pytest.fixture
+def paged(lib):
+    handle = ctypes.c_void_p()  # 12 pages of 64 rows, 5 per sequence: cap = 320
+    st = lib.qmha_kv_cache_create_paged(ctypes.byref(handle), ctypes.c_void_p(MEM), 1 << 30, 2, 12, 64, 5, 256, 4, 2, INT8)
+    assert st == 0, lib.qmha_last_error()
+    yield handle
+    lib.qmha_kv_cache_destroy(handle)
+
+
+# The uniform-count token-granular entry points, wrong in two ways: (entry point, which cache, the
+# arguments behind the handle, the winner's fragment, the loser's fragment).  Neither int8 cache has its tail attached.
+TOKEN_FAULTS = [
+    ("qmha_kv_cache_append_tokens", "paged", (None, DUMMY, 3, DUMMY, None), "append_tokens: the cache is paged", "null tensor"),
+    ("qmha_kv_cache_append_tokens", "cache", (None, DUMMY, 3, None, None), "null tensor pointer", "pos"),
+    ("qmha_kv_cache_append_tokens", "cache", (DUMMY, DUMMY, 257, None, None), "append_tokens: null pos (a device int32[B])", "rows"),
+    ("qmha_kv_cache_append_tokens", "cache", (DUMMY, DUMMY, 0, DUMMY, None), "append_tokens: n = 0 rows, needs 1 <= n <= cap = 256",
+     "tail"),
+    ("qmha_kv_cache_append_tokens", "cache", (DUMMY, DUMMY, 256, DUMMY, None), "append_tokens: an int8 cache needs its tail", "rows"),
+    ("qmha_attend_cached_tokens", "paged", (DUMMY, DUMMY, 3, None, CAUSAL, None), "attend_tokens: the cache is paged", "lens"),
+    ("qmha_attend_cached_tokens", "cache", (DUMMY, None, 3, None, CAUSAL, None), "null tensor pointer", "lens"),
+    ("qmha_attend_cached_tokens", "cache", (DUMMY, DUMMY, 3, None, 0, None), "attend_tokens: null lens (a device int32[B])", "flags"),
+    ("qmha_attend_cached_tokens", "cache", (DUMMY, DUMMY, 257, DUMMY, 0, None), "attend_tokens: flags must be QMHA_FLAG_CAUSAL",
+     "rows"),
+    ("qmha_attend_cached_tokens", "cache", (DUMMY, DUMMY, 0, DUMMY, CAUSAL, None),
+     "attend_tokens: Nq = 0 rows, needs 1 <= Nq <= cap = 256", "flags"),
+    ("qmha_kv_cache_append_paged", "cache", (DUMMY, DUMMY, 3, None, DUMMY, None), "append_paged: the cache is contiguous", "pos"),
+    ("qmha_kv_cache_append_paged", "paged", (DUMMY, None, 3, None, DUMMY, None), "null tensor pointer", "pos"),
+    ("qmha_kv_cache_append_paged", "paged", (DUMMY, DUMMY, 3, None, None, None), "append_paged: null pos (a device int32[B])", "table"),
+    ("qmha_kv_cache_append_paged", "paged", (DUMMY, DUMMY, 321, DUMMY, None, None),
+     "append_paged: null table (a device int32[B][max_pages])", "rows"),
+    ("qmha_kv_cache_append_paged", "paged", (DUMMY, DUMMY, 321, DUMMY, DUMMY, None),
+     "append_paged: n = 321 rows, needs 1 <= n <= cap = max_pages * page_rows = 320", "tail"),
+    ("qmha_kv_cache_append_paged", "paged", (DUMMY, DUMMY, 320, DUMMY, DUMMY, None), "append_paged: an int8 cache needs its tail", "rows"),
+    ("qmha_attend_cached_paged", "cache", (DUMMY, DUMMY, 3, None, DUMMY, CAUSAL, None), "attend_paged: the cache is contiguous", "lens"),
+    ("qmha_attend_cached_paged", "paged", (None, DUMMY, 3, None, DUMMY, CAUSAL, None), "null tensor pointer", "lens"),
+    ("qmha_attend_cached_paged", "paged", (DUMMY, DUMMY, 3, None, None, CAUSAL, None), "attend_paged: null lens (a device int32[B])",
+     "table"),
+    ("qmha_attend_cached_paged", "paged", (DUMMY, DUMMY, 3, DUMMY, None, 0, None),
+     "attend_paged: null table (a device int32[B][max_pages])", "flags"),
+    ("qmha_attend_cached_paged", "paged", (DUMMY, DUMMY, 321, DUMMY, DUMMY, 3, None), "attend_paged: flags must be QMHA_FLAG_CAUSAL",
+     "rows"),
+    ("qmha_attend_cached_paged", "paged", (DUMMY, DUMMY, 321, DUMMY, DUMMY, CAUSAL, None),
+     "attend_paged: Nq = 321 rows, needs 1 <= Nq <= cap = max_pages * page_rows = 320", "flags"),
+]
+
+
+@pytest.mark.parametrize("entry,which,args,winner,loser", TOKEN_FAULTS)
+def test_first_failure_of_a_token_granular_call(lib, cache, paged, entry, which, args, winner, loser):
+    st = getattr(lib, entry)({"cache": cache, "paged": paged}[which], *args)
+    msg = lib.qmha_last_error().decode()
+    assert st == INVALID and winner in msg and loser not in msg, (st, msg)
+
+
+@pytest.mark.parametrize("entry,args", [("qmha_kv_cache_append_tokens", (DUMMY, DUMMY, 0, None, None)),
+                                        ("qmha_attend_cached_tokens", (DUMMY, DUMMY, 0, None, 0, None)),
+                                        ("qmha_kv_cache_append_paged", (DUMMY, DUMMY, 0, None, None, None)),
+                                        ("qmha_attend_cached_paged", (DUMMY, DUMMY, 0, None, None, 0, None))])
+def test_a_null_cache_wins_over_everything_else(lib, entry, args):
+    st = getattr(lib, entry)(None, *args)
+    assert st == INVALID and lib.qmha_last_error().decode() == "null cache", (st, lib.qmha_last_error())
+
+
 def test_solve_ws_null_workspace_holds_no_bytes(lib):
     st = lib.qmha_solve_ws(DUMMY, DUMMY, DUMMY, DUMMY, 2, 64, 256, 4, INT8, None, 1 << 30, None)
     assert st == INVALID and lib.qmha_last_error().decode() == "workspace too small", (st, lib.qmha_last_error())

@@ -189,21 +189,24 @@ def test_library_has_the_twenty_packed_kernels_beside_the_old(lib):
     path = os.path.join(ROOT, "quantizedmha_amd", "lib", "libqmha.so")
     syms = subprocess.run(["nm", path], capture_output=True, text=True, check=True).stdout
     sizes = {"int8": ["128", "32", "64"], "f16": ["128", "64"]}
-    for family, pattern in (("qmha_fa_{}_packed_kernel", r"__device_stub__(qmha_fa_(?:int8|f16)_packed_kernel)ILi(\d+)ENS_6RaggedE"),
-                            ("qmha_fa_{}_packed_pages_kernel", r"__device_stub__(qmha_fa_(?:int8|f16)_packed_pages_kernel)ILi(\d+)ENS_5PagedE"),
+    # the cache kernel template over Packed<Ragged> and Packed<Paged>
+    for family, pattern in (("qmha_fa_{}_cache_kernel", r"__device_stub__(qmha_fa_(?:int8|f16)_cache_kernel)ILi(\d+)ENS_6PackedINS_6RaggedEEEEEv"),
+                            ("qmha_fa_{}_cache_kernel", r"__device_stub__(qmha_fa_(?:int8|f16)_cache_kernel)ILi(\d+)ENS_6PackedINS_5PagedEEEEEv"),
                             ("qmha_kv_packed_{}_kernel", r"__device_stub__(qmha_kv_packed_(?:int8|f16)_kernel)ILi(\d+)EEEv"),
                             ("qmha_kv_packed_pages_{}_kernel", r"__device_stub__(qmha_kv_packed_pages_(?:int8|f16)_kernel)ILi(\d+)EEEv")):
         got = sorted(set(re.findall(pattern, syms)))
         want = sorted((family.format(p), d) for p, ds in sizes.items() for d in ds)
         assert got == want, (family, got)
     # one instance of each per head size: no second geometry, no dumping twin
-    assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_packed_(?:pages_)?kernel\w*)", syms))) == 10
+    assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_cache_kernelILi\d+ENS_6Packed\w*)", syms))) == 10
+    assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_cache_kernel\w*)", syms))) == 20  # four geometries, nothing else
     assert len(set(re.findall(r"__device_stub__(qmha_kv_packed_\w+)", syms))) == 10
     # what the library held before
     masked = set(re.findall(r"__device_stub__(qmha_fa_\w+?_masked_kernel)ILi(\d+)ENS_\d+([A-Za-z]+?)E(\w*)", syms))
     assert len(masked) == 15 and {m[2] for m in masked} == {"SquareCausal", "Rect", "Grouped"}, sorted(masked)
-    for family, n in ((r"qmha_fa_\w+?_varlen_kernel\w*", 5), (r"qmha_fa_\w+?_ragged_kernel\w*", 5), (r"qmha_fa_\w+?_paged_kernel\w*", 5),
-                      (r"qmha_fa_\w+?_split_kernel\w*", 5), (r"qmha_fa_\w+?_split_pages_kernel\w*", 5), (r"qmha_split_combine_kernel\w*", 1),
+    for family, n in ((r"qmha_fa_\w+?_varlen_kernel\w*", 5), (r"qmha_fa_\w+?_cache_kernelILi\d+ENS_6Ragged\w*", 5),
+                      (r"qmha_fa_\w+?_cache_kernelILi\d+ENS_5Paged\w*", 5), (r"qmha_fa_\w+?_split_kernelILi\d+ENS_6Ragged\w*", 5),
+                      (r"qmha_fa_\w+?_split_kernelILi\d+ENS_5Paged\w*", 5), (r"qmha_split_combine_kernel\w*", 1),
                       (r"qmha_kv_token_\w+", 5), (r"qmha_kv_paged_\w+", 5), (r"qmha_kv_place_\w+", 5)):
         assert len(set(re.findall(rf"__device_stub__({family})", syms))) == n, family
     assert len(set(re.findall(r"__device_stub__(qmha_kv_append_\w+?_kernel)ILi(\d+)EEEv", syms))) == 5
@@ -252,7 +255,7 @@ def test_the_restated_formulas_stand_in_the_source():
     def lines(name):
         return {ln.strip() for ln in open(os.path.join(CSRC, name)).read().splitlines()}
     for name, wanted in (
-            ("qmha_fa_masked.hip", (
+            ("qmha_fa_masked.hpp", (
                 "__host__ __device__ int max_units() const { return G * ((Nq + 2 * QMHA_GROUP - 2) / QMHA_GROUP); }",
                 "v.s = (L - Nq) & (QMHA_GROUP - 1);",
                 "const int Lp = (L + QMHA_GROUP - 1) & ~(QMHA_GROUP - 1), Nqp = (v.s + Nq + QMHA_GROUP - 1) & ~(QMHA_GROUP - 1);",
@@ -267,8 +270,7 @@ def test_the_restated_formulas_stand_in_the_source():
                 "v.row0 = first;",
                 "__device__ __forceinline__ bool row_real(const Packed<Geo>& g, int row) { return (unsigned)(row - g.s) < (unsigned)g.Nq; }",
                 "__device__ __forceinline__ int row_shift(const Packed<Geo>& g) { return g.s; }",
-                "__device__ __forceinline__ size_t seq_row0(const Packed<Geo>& g, int) { return (size_t)g.row0; }")),
-            ("qmha_fa_packed.hip", (
+                "__device__ __forceinline__ size_t seq_row0(const Packed<Geo>& g, int) { return (size_t)g.row0; }",
                 "const int r0 = __builtin_amdgcn_readfirstlane(any.cu[b]), r1 = __builtin_amdgcn_readfirstlane(any.cu[b + 1]);",
                 "if (r0 < 0 || r1 < r0 || r1 > any.total) return q;  // the range never becomes an address",
                 "if (r1 == r0) return q;                             // an empty sequence sits out",
@@ -276,9 +278,10 @@ def test_the_restated_formulas_stand_in_the_source():
                 "if (q.nq > any.Nq) return q;  // beyond what the grid was sized for",
                 "if (q.L < q.nq || q.L > any.Nk) return q;",
                 "if (!any.used_pages_ok(b, q.L)) return q;",
-                "const Geo geo = any.of(q.row0, q.nq, q.L);",
-                "float* o = O + (size_t)q.row0 * d_model + (size_t)kvh * G * D;",
-                "const int nqb = masked_nqb(grid_units(geo));")),
+                "if constexpr (kPackedGeo<Geo>) return any.of(q.row0, q.nq, q.L);",
+                "float* o = O + (size_t)q.row0 * d_model + (size_t)kvh * G * D;")),
+            ("qmha_fa_packed.hip", (
+                "const int nqb = masked_nqb(grid_units(geo));",)),
             ("qmha_fa_masked_int8.inc", (
                 "if constexpr (kPackedGeo<decltype(geo)>) qrow = Qf + (seq_row0(geo, b) + (size_t)qg * QMHA_GROUP + col) * d_model + (size_t)k * D;",
                 "if constexpr (kPackedGeo<decltype(geo)>) orow = O + (seq_row0(geo, b) + (size_t)qg * QMHA_GROUP + col) * d_model + (size_t)k * D + 4 * half;",

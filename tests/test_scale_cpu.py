@@ -172,7 +172,8 @@ AFTER_SHAPES = [(96, 160, True), (160, 96, False)]
 
 # =========================================================================================================================
 def test_the_restated_formulas_are_the_sources():
-    src = open(os.path.join(ROOT, "quantizedmha_amd", "csrc", "qmha_fa_masked.hip")).read()
+    src = "".join(open(os.path.join(ROOT, "quantizedmha_amd", "csrc", n)).read()  # the geometries' header, then the launchers
+                  for n in ("qmha_fa_masked.hpp", "qmha_fa_masked.hip"))
     common = open(os.path.join(ROOT, "quantizedmha_amd", "csrc", "qmha_common.hpp")).read()
     for text in ("constexpr int kWaves = 4, kSG = 2;",
                  "constexpr int masked_pairs(int nqb) { return (nqb + 1) / 2; }",

@@ -171,21 +171,23 @@ def test_calls_that_pass_the_checks_reach_the_launch(lib, cache):
 def test_library_has_the_eleven_split_kernels_beside_the_old(lib):
     path = os.path.join(ROOT, "quantizedmha_amd", "lib", "libqmha.so")
     syms = subprocess.run(["nm", path], capture_output=True, text=True, check=True).stdout
-    main = sorted(set(re.findall(r"__device_stub__(qmha_fa_(?:int8|f16)_split(?:_pages)?_kernel)ILi(\d+)ENS_\d+(Ragged|Paged)E", syms)))
+    # one split template per precision, over Ragged and over Paged
+    main = sorted(set(re.findall(r"__device_stub__(qmha_fa_(?:int8|f16)_split_kernel)ILi(\d+)ENS_\d+(Ragged|Paged)EEEv", syms)))
     stem = lambda v: "int8" if v == "fa_tc_int8_b" else "f16"  # noqa: E731
     want = sorted([(f"qmha_fa_{stem(v)}_split_kernel", str(d), "Ragged") for v, d in BUILT] +
-                  [(f"qmha_fa_{stem(v)}_split_pages_kernel", str(d), "Paged") for v, d in BUILT])
+                  [(f"qmha_fa_{stem(v)}_split_kernel", str(d), "Paged") for v, d in BUILT])
     assert main == want and len(main) == 10, main
-    # one instance of each per head size: no second geometry, no dumping twin
-    assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_split_kernel\w*)", syms))) == 5
-    assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_split_pages_kernel\w*)", syms))) == 5
+    # one instance of each per head size: no third geometry, no dumping twin
+    assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_split_kernelILi\d+ENS_6Ragged\w*)", syms))) == 5
+    assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_split_kernelILi\d+ENS_5Paged\w*)", syms))) == 5
+    assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_split\w*_kernel\w*)", syms))) == 10
     assert len(set(re.findall(r"__device_stub__(qmha_split_combine_kernel\w*)", syms))) == 1
     # what the library held before
     masked = set(re.findall(r"__device_stub__(qmha_fa_\w+?_masked_kernel)ILi(\d+)ENS_\d+([A-Za-z]+?)E(\w*)", syms))
     assert len(masked) == 15 and {m[2] for m in masked} == {"SquareCausal", "Rect", "Grouped"}, sorted(masked)
     assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_varlen_kernel\w*)", syms))) == 5
-    assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_ragged_kernel\w*)", syms))) == 5
-    assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_paged_kernel\w*)", syms))) == 5
+    assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_cache_kernelILi\d+ENS_6Ragged\w*)", syms))) == 5
+    assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_cache_kernelILi\d+ENS_5Paged\w*)", syms))) == 5
     assert len(set(re.findall(r"__device_stub__(qmha_kv_token_\w+)", syms))) == 5
     assert len(set(re.findall(r"__device_stub__(qmha_kv_paged_\w+)", syms))) == 5
 

@@ -164,16 +164,18 @@ def test_calls_that_pass_the_checks_reach_the_launch(lib, cache):
 def test_library_has_the_ten_new_kernels_beside_the_old(lib):
     path = os.path.join(ROOT, "quantizedmha_amd", "lib", "libqmha.so")
     syms = subprocess.run(["nm", path], capture_output=True, text=True, check=True).stdout
-    main = sorted(set(re.findall(r"__device_stub__(qmha_fa_(?:int8|f16)_ragged_kernel)ILi(\d+)E", syms)))
-    assert main == [("qmha_fa_f16_ragged_kernel", "128"), ("qmha_fa_f16_ragged_kernel", "64"),
-                    ("qmha_fa_int8_ragged_kernel", "128"), ("qmha_fa_int8_ragged_kernel", "32"),
-                    ("qmha_fa_int8_ragged_kernel", "64")], main
+    # the cache kernel template over Ragged (its other geometries: test_paged_cpu.py, test_packed_cpu.py)
+    main = sorted(set(re.findall(r"__device_stub__(qmha_fa_(?:int8|f16)_cache_kernel)ILi(\d+)ENS_6RaggedEEEv", syms)))
+    assert main == [("qmha_fa_f16_cache_kernel", "128"), ("qmha_fa_f16_cache_kernel", "64"),
+                    ("qmha_fa_int8_cache_kernel", "128"), ("qmha_fa_int8_cache_kernel", "32"),
+                    ("qmha_fa_int8_cache_kernel", "64")], main
     token = sorted(set(re.findall(r"__device_stub__(qmha_kv_token_(?:int8|f16)_kernel)ILi(\d+)EEEv", syms)))
     assert token == [("qmha_kv_token_f16_kernel", "128"), ("qmha_kv_token_f16_kernel", "64"),
                      ("qmha_kv_token_int8_kernel", "128"), ("qmha_kv_token_int8_kernel", "32"),
                      ("qmha_kv_token_int8_kernel", "64")], token
     # one instance of each: no second geometry, no dumping twin
-    assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_ragged_kernel\w*)", syms))) == 5
+    assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_cache_kernelILi\d+ENS_6Ragged\w*)", syms))) == 5
+    assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_cache_kernel\w*)", syms))) == 20  # four geometries, nothing else
     assert len(set(re.findall(r"__device_stub__(qmha_kv_token_\w+)", syms))) == 5
     # what the library held before: fifteen masked and five varlen main kernels, five append and five place kernels
     masked = set(re.findall(r"__device_stub__(qmha_fa_\w+?_masked_kernel)ILi(\d+)ENS_\d+([A-Za-z]+?)E(\w*)", syms))

@@ -24,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 # the shipped query groups per workgroup, read from the kernel source
-with open(os.path.join(ROOT, "quantizedmha_amd", "csrc", "qmha_fa_masked.hip")) as _f:
+with open(os.path.join(ROOT, "quantizedmha_amd", "csrc", "qmha_fa_masked.hpp")) as _f:
     CAUSAL_WAVES = int(re.search(r"constexpr int kWaves = (\d+)", _f.read()).group(1))
 
 

@@ -165,8 +165,8 @@ def main():
            "step_ratio": round(med["packed"][2] / med["tokens"][2], 4), "ref_step_spread": spread(2),
            "per_round": {s: [[round(x, 5) for x in row] for row in per[s]] for s in per},
            "clock_probe": bench.clock_probe(dev),
-           "isa_sha16": {"ragged_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_ragged_kernelILi{a.d}E"),
-                         "packed_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_packed_kernelILi{a.d}E")},
+           "isa_sha16": {"ragged_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_cache_kernelILi{a.d}ENS_6RaggedEEEv"),
+                         "packed_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_cache_kernelILi{a.d}ENS_6PackedINS_6RaggedEEEEEv")},
            "device": torch.cuda.get_device_properties(dev).name}
     print(json.dumps(res), flush=True)
     if not same:

@@ -166,8 +166,8 @@ def main():
                 "memory": memory,
                 "not_measured": ["prefill through pages", "other head sizes", "grouped caches", "a captured step against an eager one"],
                 "clock_probe": bench.clock_probe(dev),
-                "isa_sha16": {"ragged_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_ragged_kernelILi{a.d}E"),
-                              "paged_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_paged_kernelILi{a.d}E"),
+                "isa_sha16": {"ragged_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_cache_kernelILi{a.d}ENS_6RaggedEEEv"),
+                              "paged_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_cache_kernelILi{a.d}ENS_5PagedEEEv"),
                               "token_append": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_kv_token_{stem}_kernelILi{a.d}E"),
                               "paged_append": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_kv_paged_{stem}_kernelILi{a.d}E")},
                 "device": torch.cuda.get_device_properties(dev).name})

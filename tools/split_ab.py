@@ -178,7 +178,7 @@ def main():
            "ref_attend_spread": round(spread(ref_main, med["ref"][0]), 4), "ref_step_spread": round(spread(ref_step_ms, med["ref"][2]), 4),
            "split": {}, "per_round": {s: [[round(x, 5) for x in row] for row in per[s]] for s in per},
            "clock_probe": bench.clock_probe(dev),
-           "isa_sha16": {"ragged_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_ragged_kernelILi{a.d}E"),
+           "isa_sha16": {"ragged_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_cache_kernelILi{a.d}ENS_6RaggedEEEv"),
                          "split_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_split_kernelILi{a.d}ENS_6Ragged"),
                          "combine": isa_id.isa_sha16(_lib.LIB_PATH, "qmha_split_combine_kernel")},
            "device": torch.cuda.get_device_properties(dev).name}

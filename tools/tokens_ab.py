@@ -132,7 +132,7 @@ def main():
            "per_round": {s: [[round(x, 5) for x in row] for row in per[s]] for s in per},
            "clock_probe": bench.clock_probe(dev),
            "isa_sha16": {"varlen_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_varlen_kernelILi{a.d}E"),
-                         "ragged_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_ragged_kernelILi{a.d}E")},
+                         "ragged_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_cache_kernelILi{a.d}ENS_6RaggedEEEv")},
            "device": torch.cuda.get_device_properties(dev).name}
     print(json.dumps(res), flush=True)
     if not same:

@@ -395,6 +395,36 @@ int qmha_attend_cached_packed(qmha_kv_cache_t *c, const float *Q, float *O, int 
 int qmha_attend_cached_paged_packed(qmha_kv_cache_t *c, const float *Q, float *O, int total, int max_nq, const int32_t *cu,
                                     const int32_t *lens, const int32_t *table, unsigned flags, void *stream);
 
+/*
+ * Sliding-window attention -- qmha_attend_cached_tokens / qmha_attend_cached_paged in which a query row sees only the
+ * last `window` keys of those the causal mask leaves it (Mistral-style layers, local/global alternation).  Everything
+ * is the unwindowed call's -- Q, O [B, Nq, d_model], any 1 <= Nq <= cap; the DEVICE arrays lens and table; multi-head,
+ * grouped and paged caches of every built (variant, d); flags must be QMHA_FLAG_CAUSAL -- except:
+ *
+ *   the mask       with L = lens[b], real row i of the Nq rows attends the cache rows j with
+ *                  i + L - Nq - window < j <= i + L - Nq: exactly min(window, i + L - Nq + 1) keys.
+ *   window         a host int, a multiple of 32, >= 32, with no upper limit (absolute row positions keep their 32-row
+ *                  groups, so the window's left edge falls on a key tile's diagonal).  A window that reaches the start of
+ *                  every sequence (window >= cap) gives the unwindowed call's O bit for bit.
+ *   the sweep      query group qg (the 32-row group of absolute positions) sweeps the key tiles first(qg) ... diag(qg),
+ *                  first(qg) = max(0, diag(qg) - window / 32), from the zero state; tiles before first(qg) are neither
+ *                  staged for that group's sake nor computed, so a decode step costs window / 32 + 1 tiles whatever L is.
+ *                  A ragged call is, as for attend_tokens, the call on the zero-padded block against ceil32(L) rows.
+ *   paged          only the table columns whose pages hold rows [64 * (first(0) / 2), L) of the sequence are used: the
+ *                  window, widened to the two-tile stage that holds its first tile.  Columns behind them are not loaded --
+ *                  they may hold anything, -1 for instance, and their pages may have been given to another sequence.  A
+ *                  used entry outside [0, num_pages): the sequence's rows of O are positive zeros, none of its K/V is read.
+ *
+ * Validity on the device is the unwindowed call's: Nq <= lens[b] <= cap, any other length gives positive zeros and
+ * nothing read.  Host checks, all before any HIP call, QMHA_ERR_INVALID: those of the unwindowed call in their order,
+ * then window < 32 or window % 32 != 0.  No allocation, no synchronisation (the calls can be captured in a hipGraph);
+ * the cache's mutex is held across the enqueue; the qmha_profile record is attend's.
+ */
+int qmha_attend_cached_tokens_window(qmha_kv_cache_t *c, const float *Q, float *O, int Nq, const int32_t *lens, int window,
+                                     unsigned flags, void *stream);
+int qmha_attend_cached_paged_window(qmha_kv_cache_t *c, const float *Q, float *O, int Nq, const int32_t *lens,
+                                    const int32_t *table, int window, unsigned flags, void *stream);
+
 /* Blocking convenience used by the per-variant `solve` shims and the JAX raw-pointer
  * binding (extensions/jax/jax_ext.cpp:12-28): batch 1, synchronises the device stream. */
 int qmha_solve_variant(const float *Q, const float *K, const float *V, float *O, int N, int d_model, int h,

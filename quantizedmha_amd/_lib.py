@@ -52,6 +52,9 @@ SIGNATURES = {
     "qmha_attend_split_bytes": (_sz, [_vp, _i, _i]),
     "qmha_attend_cached_tokens_split": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _sz, ctypes.c_uint, _vp]),
     "qmha_attend_cached_paged_split": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _sz, ctypes.c_uint, _vp]),
+    # a sliding window: the two attends over the last `window` keys of a row (a host int, a multiple of 32)
+    "qmha_attend_cached_tokens_window": (_i, [_vp, _vp, _vp, _i, _vp, _i, ctypes.c_uint, _vp]),
+    "qmha_attend_cached_paged_window": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, ctypes.c_uint, _vp]),
     # packed batches: operands without a batch axis and a device int32[B + 1] cu beside pos / lens / table
     "qmha_kv_cache_append_packed": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "qmha_kv_cache_append_paged_packed": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),

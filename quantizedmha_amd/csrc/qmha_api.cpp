@@ -604,6 +604,12 @@ struct CacheCall {
         if (n >= 1 && n <= c->cap) return QMHA_OK;
         return bad(std::string(name) + " = " + std::to_string(n) + " rows, needs 1 <= " + name + " <= " + cap());
     }
+    // a sliding window: whole 32-row tiles, at least one
+    int window(int w) const {
+        if (w >= 32 && w % 32 == 0) return QMHA_OK;
+        return bad("window = " + std::to_string(w) + " rows, needs a multiple of 32 with window >= 32 (the window's left edge falls on a "
+                   "32-row key tile's diagonal)");
+    }
     // a packed call's rows and the bound its grid is sized for: 1 <= bound <= min(total, cap)
     int bound(const char* name, int total, int b) const {
         if (total < 1) return bad("total = " + std::to_string(total) + " rows, needs total >= 1");
@@ -637,13 +643,18 @@ int append_rows(const CacheCall& k, const float* K, const float* V, int n, const
         });
 }
 
-// The uniform-count attend (qmha_attend_cached_tokens / _paged)
+// The uniform-count attend (qmha_attend_cached_tokens / _paged); window non-null: its windowed form (_tokens_window /
+// _paged_window)
 int attend_rows(const CacheCall& k, const float* Q, float* O, int Nq, const int32_t* lens, const int32_t* table, unsigned flags,
-                void* stream) {
+                void* stream, const int* window = nullptr) {
     if (int st = k.operands(Q, O)) return st;
     if (int st = k.attend_words(lens, table, flags)) return st;
     if (int st = k.rows("Nq", Nq)) return st;
+    if (window) {
+        if (int st = k.window(*window)) return st;
+    }
     return cache_enqueue(k.c, &ProfRec::main, stream, k.label().c_str(), kNoLenCheck, [&](const auto& w, int) {
+        if (window) return qmha::launch_fa_window(w, Q, O, k.attend(Nq, lens, table), *window, (hipStream_t)stream);
         return qmha::launch_fa_masked(w, Q, O, k.attend(Nq, lens, table), (hipStream_t)stream);
     });
 }
@@ -916,6 +927,17 @@ int qmha_kv_cache_append_paged(qmha_kv_cache_t* c, const float* K, const float* 
 int qmha_attend_cached_paged(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, const int32_t* lens, const int32_t* table,
                              unsigned flags, void* stream) {
     return attend_rows({c, "attend_paged", true}, Q, O, Nq, lens, table, flags, stream);
+}
+
+// ---- a sliding window: the token-granular and the paged attend over the last `window` keys of a row -------
+int qmha_attend_cached_tokens_window(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, const int32_t* lens, int window,
+                                     unsigned flags, void* stream) {
+    return attend_rows({c, "attend_tokens_window", false}, Q, O, Nq, lens, nullptr, flags, stream, &window);
+}
+
+int qmha_attend_cached_paged_window(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, const int32_t* lens, const int32_t* table,
+                                    int window, unsigned flags, void* stream) {
+    return attend_rows({c, "attend_paged_window", true}, Q, O, Nq, lens, table, flags, stream, &window);
 }
 
 // ---- split-KV: the token-granular and the paged attend with the key sweep cut into chunks -----------

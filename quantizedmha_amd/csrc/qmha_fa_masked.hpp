@@ -1,5 +1,5 @@
 // qmha_fa_masked.hpp -- what the translation units of the masked kernel bodies share (qmha_fa_masked.hip,
-// qmha_fa_split.hip, qmha_fa_packed.hip; the modes are described at the top of the first): the geometries of a launch,
+// qmha_fa_split.hip, qmha_fa_packed.hip, qmha_fa_window.hip; the modes are described at the top of the first): the geometries of a launch,
 // the launch-index maps, the K/V stager, the zeroing helpers, the attend kernels of a persistent K/V cache
 // (qmha_fa_{int8,f16}_cache_kernel) and the checked geometry of a call (masked_geo).  The three files stay three
 // translation units: the dumping twins of qmha_fa_masked.hip reach their out-of-line dump lambdas PC-relative, so a
@@ -142,6 +142,15 @@ struct Paged : Ragged {
             if (c * (PG * QMHA_GROUP) < L) bad |= (unsigned)table[(size_t)b * max_pages + c] >= (unsigned)num_pages;
         return __builtin_amdgcn_ballot_w64(bad) == 0;
     }
+    // the windowed form: the pages that hold rows [lo, L) of sequence b, lo a stage's first row.  Columns
+    // wholly behind row lo are not loaded either.
+    __device__ bool used_pages_ok(int b, int lo, int L) const {
+        const int lane = threadIdx.x & 63;
+        bool bad = false;
+        for (int c = lane; c < max_pages; c += 64)
+            if (c * (PG * QMHA_GROUP) < L && (c + 1) * (PG * QMHA_GROUP) > lo) bad |= (unsigned)table[(size_t)b * max_pages + c] >= (unsigned)num_pages;
+        return __builtin_amdgcn_ballot_w64(bad) == 0;
+    }
     // column c of sequence b's table row, wave-uniform; the column and the id are clamped to the row and the pool.  Read
     // through the constant address space -- no kernel writes a table --, which makes it a scalar load: a vector load
     // would be waited for with vmcnt(0), together with the stage's DMA that was just issued.
@@ -228,6 +237,32 @@ struct IsPacked : std::false_type {};
 template <class Base>
 struct IsPacked<Packed<Base>> : std::true_type {};
 
+// A sliding window: Ragged's or Paged's call in which a query row sees only the last `window` = 32 w keys of
+// those the causal mask leaves it (w >= 1).  Absolute row positions keep their 32-row groups, so the window's left edge of
+// query group qg falls in tile left(qg) = diag(qg) - w with the complement of the diagonal's in-tile mask (key column c is
+// visible to row r iff c > r), the tiles strictly between the two are unmasked, and the sweep of the group is tiles
+// first(qg) = max(0, left(qg)) ... diag(qg) from the zero state.  left(qg) < 0: no left tile.  A workgroup is one unit
+// block (no pair: a band has no triangle to balance); t0, set by of() for unit block qb, is the first tile of its first
+// stage -- first() is monotone in the unit, so that of the block's first unit, rounded down to a stage.
+template <class Base>
+struct Window : Base {
+    int w;   // tiles of the window
+    int t0;  // device: the first tile of the workgroup's first stage (even)
+    Window(Base g, int tiles) : Base(g), w(tiles), t0(0) {}
+    __device__ int left(int qg) const { return this->diag(qg) - w; }
+    __device__ int first(int qg) const { return max(left(qg), 0); }
+    __device__ Window of(int L, int qb) const {
+        Window v = *this;
+        static_cast<Base&>(v) = Base::of(L);
+        v.t0 = v.first(v.group(qb * kWaves)) & ~(kSG - 1);
+        return v;
+    }
+};
+template <class T>
+struct IsWindow : std::false_type {};
+template <class Base>
+struct IsWindow<Window<Base>> : std::true_type {};
+
 // A lane's row of Q / O in memory is its row of the (padded) block less row_shift; row_real: that row exists.
 // Constants for every geometry but Ragged (and Paged over it), so the other instances carry no trace of them.
 template <class Geo>
@@ -255,6 +290,12 @@ template <class Geo>
 __device__ __forceinline__ int row_shift(const Packed<Geo>& g) { return g.s; }
 template <class Geo>
 __device__ __forceinline__ bool row_real(const Packed<Geo>& g, int row) { return (unsigned)(row - g.s) < (unsigned)g.Nq; }
+template <class Geo>
+__device__ __forceinline__ int row_shift(const Window<Geo>& g) { return g.s; }
+template <class Geo>
+__device__ __forceinline__ bool row_real(const Window<Geo>& g, int row) { return (unsigned)(row - g.s) < (unsigned)g.Nq; }
+template <class Geo>
+constexpr bool kWindowGeo = IsWindow<std::remove_cv_t<Geo>>::value;
 // The first row of a sequence in Q and O: slice * Nq where the operands have a batch axis (slice: b, or Split's
 // (b, chunk) slice of the scratch); a packed sequence's cu[b].  kPackedGeo: the int8 body takes the second under
 // `if constexpr`, as it takes row_shift and row_real.
@@ -282,6 +323,9 @@ template <class Geo>
 __device__ __forceinline__ float* out_base(const Split<Geo>& g, float*) { return g.Oc; }
 template <class Geo>
 __device__ __forceinline__ int out_slice(const Split<Geo>& g, int b) { return b * g.NC + g.c; }
+// Window: the workgroup's sweep starts at its first stage; where a wave's own tiles start is first(qg), in the bodies
+template <class Geo>
+__device__ __forceinline__ int tile_first(const Window<Geo>& g) { return g.t0; }
 
 // A geometry that also carries the buffers of a dumping instance (int8 kernel; QkDump and PDump in
 // qmha_kernels.hpp): the debug hook's twin of a shipped instance, whose own arguments stay as they are.

@@ -22,6 +22,9 @@
     const int Nq = geo.nq(), Nk = geo.nk();
     const int U = geo.units();
     constexpr bool SPLIT = kSplitGeo<decltype(geo)>;
+    // Window<Geo> (DESIGN.md 22): the sweep starts at the stage of tile_first(geo), a wave computes tiles first(qg) ...
+    // last(qg) from the zero state, and tile left(qg) takes the complement of the diagonal's mask
+    constexpr bool WINDOW = kWindowGeo<decltype(geo)>;
     int bh, qb0;
     if constexpr (SPLIT) {  // the chunk is geo.c
         int c_;
@@ -45,6 +48,8 @@
     const int nst = wg_last / SG + 1, st0 = tile_first(geo) / SG;  // the workgroup runs stages st0 ... nst - 1
     const int my_diag = geo.diag(qg);  // this wave's diagonal tile
     const int my_last = active ? tile_end(geo, geo.last(qg)) : -1;
+    int my_first = 0, my_left = -1;  // Window: this wave's first tile and its left tile (negative: none).  Wave-uniform
+    if constexpr (WINDOW) my_first = geo.first(qg), my_left = geo.left(qg);
 
     // Q converted in-kernel (RNE) into the QK B operand: query 16 qb + r16, d = 32 ks + 8 grp .. +7
     v8h qop[2][KS];
@@ -91,6 +96,8 @@
     // Paged: the stage's page slice is the buffer (base formed in 64 bits, records of one page slice), the stage offset
     // the stage's place in its page
     std::conditional_t<kPagedGeo<decltype(geo)>, PageWalk, NoWalk> walk;
+    if constexpr (kPagedGeo<decltype(geo)> && WINDOW) walk.start_at(geo, b, tile_first(geo));  // the first stage's first tile
+    else
     if constexpr (kPagedGeo<decltype(geo)> && kSplitGeo<decltype(geo)>) walk.start_at(geo, b, tile_first(geo));
     else if constexpr (kPagedGeo<decltype(geo)>) walk.start(geo, b);
     auto issue = [&](int buf, int st) {
@@ -125,7 +132,8 @@
     };
     const int key0 = kap16(0, 4 * grp);  // this lane's keys of the tile: key0 + i + 8 kb
     // online softmax of one tile (fa_tc_v1a.cu:101-220) and O += P V, the lazy base as
-    // qmha_fa_f16_v3_kernel; diag: the diagonal tile
+    // qmha_fa_f16_v3_kernel; diag: the diagonal tile (Window: and left_tile says the tile is that of the window's left edge)
+    bool left_tile = false;
     auto tile = [&](const char* L, int gi, S4 s, bool diag) {
         v8h vop[DB];  // V^T rows 16 m + r16, slots 8 grp .. +7 (read before the softmax)
 #pragma unroll
@@ -141,6 +149,19 @@
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
                         s.v[kb][qb][i] = key0 + i + 8 * kb > 16 * qb + r16 ? -__builtin_huge_valf() : s.v[kb][qb][i];
+        }
+        if constexpr (WINDOW) {
+            // The complement of the diagonal's select: key c is visible to row r iff c > r.  w >= 1 (window >= 32, checked
+            // by the host), so left(qg) = diag(qg) - w < diag(qg): a tile takes one select or the other, never both.
+            if (left_tile) {  // wave-uniform
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            s.v[kb][qb][i] = key0 + i + 8 * kb <= 16 * qb + r16 ? -__builtin_huge_valf() : s.v[kb][qb][i];
+            }
         }
         float p[2][8];
         float ts[2];
@@ -163,7 +184,9 @@
                 const uint64_t over = qb ? over1 : over0;
                 float mx = fmaxf(fmaxf(s.v[0][qb][0], s.v[0][qb][1]), fmaxf(s.v[0][qb][2], s.v[0][qb][3]));
                 mx = fmaxf(mx, fmaxf(fmaxf(s.v[1][qb][0], s.v[1][qb][1]), fmaxf(s.v[1][qb][2], s.v[1][qb][3])));
-                mx = fmaxf(mx, __shfl_xor(mx, 16));  // the query's four lane groups (key 0 is never masked: finite)
+                // the query's four lane groups (key 0 is never masked: finite -- but in a window's left tile, where row 31
+                // sees no key: its mx is -inf, its ts is 0 in all four lanes, so its `rows` bit is clear and mx goes unused)
+                mx = fmaxf(mx, __shfl_xor(mx, 16));
                 mx = fmaxf(mx, __shfl_xor(mx, 32));
                 const uint32_t q16 = (uint32_t)(over | (over >> 32));
                 const uint32_t rows = (q16 | (q16 >> 16)) & 0xffffu;
@@ -202,6 +225,10 @@
 #pragma unroll
             for (int gi = 0; gi < SG; ++gi) {
                 const int t = t0 + gi;
+                if constexpr (WINDOW) {
+                    left_tile = t == my_left;
+                    if (t >= my_first && t <= my_last) tile(L, gi, qk(L, gi), t == my_diag);
+                } else
                 if (t <= my_last) tile(L, gi, qk(L, gi), t == my_diag);
                 __builtin_amdgcn_sched_barrier(0);  // one tile's registers at a time
             }

@@ -13,6 +13,9 @@
     constexpr int KCH = KBYTES / 16, VCH = VBYTES / 16;
     constexpr bool DUMP = Geo::kDump;  // also store what the kernel computed (Dumping<Geo>), per tile a wave runs
     constexpr bool SPLIT = kSplitGeo<decltype(geo)>;
+    // Window<Geo> (DESIGN.md 22): one unit block per workgroup; the sweep starts at the stage of tile_first(geo), a wave
+    // computes tiles first(qg) ... last(qg) from the zero state, and tile left(qg) takes the complement of the diagonal's mask
+    constexpr bool WINDOW = kWindowGeo<decltype(geo)>;
     static_assert(D == 32 || D == 64 || D == 128, "masked int8: d in {32, 64, 128}");
     static_assert(KCH % 64 == 0 && VCH % 64 == 0 && (KCH / SG) % 64 == 0, "whole KiB LDS-DMA pieces");
     __shared__ __attribute__((aligned(16))) char lds[2][KBYTES + VBYTES];
@@ -24,6 +27,8 @@
         int c_;
         split_wg(nqb, geo.NC, bh, pi, c_);
     } else
+    if constexpr (WINDOW) masked_wg_single(nqb, bh, pi);  // no pair either: a band has no triangle; pi is the unit block
+    else
     masked_wg(nqb, bh, pi);
     const int b = bh / H, kvh = bh % H;  // bh: the K/V slice (H K/V heads)
     const int lane = threadIdx.x & 63;
@@ -31,8 +36,8 @@
     const int half = lane >> 5, col = lane & 31;
 #pragma nounroll
     for (int pass = 0; pass < 2; ++pass) {  // the pair's large q-block, then its mirror (uniform)
-    const int qb = SPLIT ? pi : pass == 0 ? nqb - 1 - pi : pi;
-    if (pass == 1 && (SPLIT || pi == nqb - 1 - pi)) break;  // odd nqb: the middle q-block has no partner
+    const int qb = (SPLIT || WINDOW) ? pi : pass == 0 ? nqb - 1 - pi : pi;
+    if (pass == 1 && (SPLIT || WINDOW || pi == nqb - 1 - pi)) break;  // odd nqb: the middle q-block has no partner
     if constexpr (kRaggedGeo<decltype(geo)>) {  // its grid follows the host's Nq, U the sequence's length: a pass with no
         if (qb * WAVES >= U) continue;          // active unit leaves before any barrier or DMA issue (workgroup-uniform)
     }
@@ -48,6 +53,8 @@
     const int nst = wg_last / SG + 1, st0 = tile_first(geo) / SG;  // the pass runs stages st0 ... nst - 1
     const int my_diag = geo.diag(qg);              // this wave's diagonal tile
     const int my_last = active ? tile_end(geo, geo.last(qg)) : -1;  // this wave computes tiles t <= my_last
+    int my_first = 0, my_left = -1;  // Window: ... and t >= my_first; its left tile (negative: none).  Wave-uniform
+    if constexpr (WINDOW) my_first = geo.first(qg), my_left = geo.left(qg);
 
     // in-register Q quantisation (fa_tc_int8_b.cu:33-152) into the Q^T operand: lane (col, half) holds
     // bytes [32 s + 16 half, +16) of query row col for every k-step s
@@ -128,6 +135,8 @@
     // Paged: the stage's page slice is the buffer (base formed in 64 bits, records of one page slice), the stage offset
     // the stage's place in its page; skb / svb follow the page a stage was issued with (the head of `stage` below)
     std::conditional_t<kPagedGeo<decltype(geo)>, PageWalk, NoWalk> walk;
+    if constexpr (kPagedGeo<decltype(geo)> && WINDOW) walk.start_at(geo, b, tile_first(geo));  // the first stage's first tile
+    else
     if constexpr (kPagedGeo<decltype(geo)> && kSplitGeo<decltype(geo)>) walk.start_at(geo, b, tile_first(geo));
     else if constexpr (kPagedGeo<decltype(geo)>) walk.start(geo, b);
     auto issue = [&](int buf, int st) {
@@ -156,7 +165,7 @@
     const int mask_col = col - 4 * half;  // key acc_row(r, half) > col  <=>  acc_row(r, 0) > mask_col
 
     // one tile: online softmax (fa_tc_int8_b.cu:281-346), P quantisation (:359), P@V (:366-371);
-    // diag: the diagonal tile
+    // diag: the diagonal tile (Window: and t == my_left is the tile of the window's left edge)
     auto tile = [&](const char* L, int gi, int t, const v16i& s, bool diag) {
         const float skt = skb[t], svt = svb[t];
         const float c = cq * skt;  // sQ*sK*log2(e)/sqrt(d) > 0
@@ -172,10 +181,21 @@
 #pragma unroll
             for (int r = 0; r < 16; ++r) sf[r] = acc_row(r, 0) > mask_col ? -__builtin_huge_valf() : sf[r];
         }
+        if constexpr (WINDOW) {
+            // The complement of the diagonal's select: key c is visible to row r iff c > r.  w >= 1 (window >= 32, checked
+            // by the host), so left(qg) = diag(qg) - w < diag(qg): a tile takes one select or the other, never both.
+            if (t == my_left) {  // wave-uniform
+#pragma unroll
+                for (int r = 0; r < 16; ++r) sf[r] = acc_row(r, 0) <= mask_col ? -__builtin_huge_valf() : sf[r];
+            }
+        }
         float mx = fmaxf(fmaxf(sf[0], sf[1]), sf[2]);
 #pragma unroll
         for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, sf[r]), sf[r + 1]);
-        mx = half_swap_max(fmaxf(mx, sf[15]));  // finite: key 0 of the tile is never masked
+        // finite: key 0 of the tile is never masked -- but in a window's left tile, where key 0 is always masked and row 31
+        // sees nothing: mx = -inf, mx * c = -inf (c > 0), m_new = m_run (finite from m0 = 0), every p of the row is
+        // exp2(-inf) = 0, and pmax comes from the rows that see a key (row 30 always does).  No NaN is formed.
+        mx = half_swap_max(fmaxf(mx, sf[15]));
         const float m_new = fmaxf(m_run, mx * c);
         // tile max of p = exp(row max - m), then the max over the 32 query rows (:359)
         const float pmax = half_max32_nonneg(__builtin_amdgcn_exp2f(fmaf(mx, c, -m_new)));
@@ -249,6 +269,9 @@
 #pragma unroll
             for (int gi = 0; gi < SG; ++gi) {
                 const int t = t0 + gi;
+                if constexpr (WINDOW) {
+                    if (t >= my_first && t <= my_last) tile(L, gi, t, qk(L, gi), t == my_diag);
+                } else
                 if (t <= my_last) tile(L, gi, t, qk(L, gi), t == my_diag);
                 __builtin_amdgcn_sched_barrier(0);  // one tile's registers at a time
             }

@@ -248,6 +248,16 @@ hipError_t launch_fa_split(const Int8Workspace& w, const float* Qf, float* O, co
 hipError_t launch_fa_split(const F16Workspace& w, const float* Qf, float* O, const MaskedCall& c, int chunk_rows, void* scratch,
                            hipStream_t stream);
 
+// ---- a sliding window over a cache's token-granular and paged calls (qmha_fa_window.hip) -----------
+// c: a token-granular call (ragged, with lens; a table: paged) as launch_fa_masked takes it.  window: a multiple of 32,
+// >= 32, no upper limit.  With L = lens[b], real row i of the Nq rows attends the cache rows j with
+// i + L - Nq - window < j <= i + L - Nq: the last min(window, i + L - Nq + 1) of those launch_fa_masked gives it; a window
+// that reaches row 0 of every sequence gives launch_fa_masked's bits.  A paged call loads only the table columns whose
+// pages hold rows [64 * (first / 2), L), first = max(0, (ceil32(L) - ceil32(s + Nq) - window) / 32) the first tile of the
+// first query group; an entry outside the pool among them, or lens[b] outside [Nq, Nk]: the sequence's rows of O are zeros.
+hipError_t launch_fa_window(const Int8Workspace& w, const float* Qf, float* O, const MaskedCall& c, int window, hipStream_t stream);
+hipError_t launch_fa_window(const F16Workspace& w, const float* Qf, float* O, const MaskedCall& c, int window, hipStream_t stream);
+
 // ---- K/V cache append (qmha_prepass.hip) ----------------------------------------
 // w: the variant's carve of H heads at N = cap, in caller-owned memory.  The pre-pass of the n new rows K, V
 // [B, n, d_model = H * D] into rows [len, len + n) of every slice, byte for byte what the pre-pass of a whole call writes

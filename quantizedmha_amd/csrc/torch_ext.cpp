@@ -26,6 +26,8 @@
 //     the key sweep in chunks over a scratch the object owns (qmha_attend_cached_tokens_split / _paged_split);
 //   * all three caches' `append_packed` / `attend_packed` (`append_paged_packed` / `attend_paged_packed`): a count per
 //     sequence from a device cu[B + 1] over operands without a batch axis (qmha_kv_cache_append_packed / ..._paged_packed);
+//   * all three caches' `attend_tokens_window` (`attend_paged_window`): the attend over the last `window` keys of a row
+//     (qmha_attend_cached_tokens_window / _paged_window);
 //   * a rejected shape raises (TORCH_CHECK on the C-ABI status) instead of a device assert.
 #include <torch/extension.h>
 // ROCm PyTorch reports HIP devices as device type "cuda": the guard / current-stream
@@ -33,6 +35,7 @@
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
+#include <climits>
 #include <optional>
 #include <string>
 #include <tuple>
@@ -350,6 +353,19 @@ public:
         return out_opt ? out : out.view(Q.sizes());
     }
 
+    // attend_tokens over the last `window` keys of a row (qmha_attend_cached_tokens_window)
+    Tensor attend_tokens_window(const Tensor& Q, const Tensor& lens, int64_t window, std::optional<Tensor> out_opt) {
+        auto Qc = rows(Q, "Q", d_model_);
+        per_seq(lens, "lens");
+        TORCH_CHECK(window >= INT_MIN && window <= INT_MAX, "attend_tokens_window: window = ", window, " does not fit an int");
+        Tensor out = out_for(out_opt, Qc);
+        const OnStream on = current_stream(mem_.device());
+        const int st = qmha_attend_cached_tokens_window(handle_, Qc.data_ptr<float>(), out.data_ptr<float>(), static_cast<int>(Qc.size(1)),
+                                                        lens.data_ptr<int32_t>(), static_cast<int>(window), QMHA_FLAG_CAUSAL, on.stream);
+        TORCH_CHECK(st == QMHA_OK, "KVCache.attend_tokens_window", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+        return out_opt ? out : out.view(Q.sizes());
+    }
+
     // allocate the scratch of the split-KV attend (qmha_attend_split_bytes at Nq = max_nq); once, outside a capture
     void enable_split(int64_t chunk_rows, int64_t max_nq) { split_.enable(handle_, chunk_rows, max_nq, cap_, mem_.device()); }
     std::optional<Tensor> split_scratch() const { return split_.tensor(); }
@@ -480,6 +496,21 @@ public:
         return out_opt ? out : out.view(Q.sizes());
     }
 
+    // attend_tokens_window through the block table (qmha_attend_cached_paged_window)
+    Tensor attend_paged_window(const Tensor& Q, const Tensor& lens, const Tensor& table, int64_t window, std::optional<Tensor> out_opt) {
+        auto Qc = cache_rows(Q, "Q", d_model_, B_, mem_.device());
+        cache_per_seq(lens, "lens", B_, mem_.device());
+        check_table(table);
+        TORCH_CHECK(window >= INT_MIN && window <= INT_MAX, "attend_paged_window: window = ", window, " does not fit an int");
+        Tensor out = out_for(out_opt, Qc);
+        const OnStream on = current_stream(mem_.device());
+        const int st = qmha_attend_cached_paged_window(handle_, Qc.data_ptr<float>(), out.data_ptr<float>(), static_cast<int>(Qc.size(1)),
+                                                       lens.data_ptr<int32_t>(), table.data_ptr<int32_t>(), static_cast<int>(window),
+                                                       QMHA_FLAG_CAUSAL, on.stream);
+        TORCH_CHECK(st == QMHA_OK, "PagedKVCache.attend_paged_window", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+        return out_opt ? out : out.view(Q.sizes());
+    }
+
     // the split-KV scratch, as KVCache's
     void enable_split(int64_t chunk_rows, int64_t max_nq) { split_.enable(handle_, chunk_rows, max_nq, cap_, mem_.device()); }
     std::optional<Tensor> split_scratch() const { return split_.tensor(); }
@@ -568,6 +599,9 @@ PYBIND11_MODULE(torch_ext, m) {
         .def("attend_paged", &PagedKVCache::attend_paged, pybind11::arg("Q"), pybind11::arg("lens"), pybind11::arg("table"),
              pybind11::arg("out") = pybind11::none(),
              "attend_tokens through the table; an invalid lens[b] or a used table entry outside [0, num_pages) gives zeros.")
+        .def("attend_paged_window", &PagedKVCache::attend_paged_window, pybind11::arg("Q"), pybind11::arg("lens"), pybind11::arg("table"),
+             pybind11::arg("window"), pybind11::arg("out") = pybind11::none(),
+             "attend_tokens_window through the table, bit for bit; table columns behind the window's pages are not read.")
         .def("enable_split", &PagedKVCache::enable_split, pybind11::arg("chunk_rows"), pybind11::arg("max_nq") = 32,
              "allocate the scratch of attend_paged_split for chunks of chunk_rows key rows (a multiple of 64) and up to max_nq\n"
              "query rows; once, outside a graph capture.")
@@ -611,6 +645,9 @@ PYBIND11_MODULE(torch_ext, m) {
              "for their rows so far, zero-padded; an invalid pos[b] writes nothing for that sequence.")
         .def("attend_tokens", &KVCache::attend_tokens, pybind11::arg("Q"), pybind11::arg("lens"), pybind11::arg("out") = pybind11::none(),
              "causal attend_varlen for any Nq >= 1 and any lens[b] in [Nq, cap]; an invalid lens[b] gives zeros.")
+        .def("attend_tokens_window", &KVCache::attend_tokens_window, pybind11::arg("Q"), pybind11::arg("lens"), pybind11::arg("window"),
+             pybind11::arg("out") = pybind11::none(),
+             "attend_tokens over the last `window` keys of a row (a multiple of 32, >= 32); window >= cap gives attend_tokens' bits.")
         .def("enable_split", &KVCache::enable_split, pybind11::arg("chunk_rows"), pybind11::arg("max_nq") = 32,
              "allocate the scratch of attend_tokens_split for chunks of chunk_rows key rows (a multiple of 64) and up to max_nq\n"
              "query rows; once, outside a graph capture.")

@@ -342,6 +342,19 @@ class KVCache:
         _lib.check(st, f"KVCache.attend_tokens({self.kernel})")
         return out.view(Q.shape) if out.numel() == Q.numel() and out.dim() != Q.dim() else out
 
+    def attend_tokens_window(self, Q: torch.Tensor, lens: torch.Tensor, window: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """attend_tokens under a sliding window (qmha_attend_cached_tokens_window): row r of sequence b attends the cache
+        rows j with r + (lens[b] - Nq) - window < j <= r + (lens[b] - Nq), the last min(window, r + lens[b] - Nq + 1) keys.
+        window: a multiple of 32, >= 32; window >= cap gives attend_tokens' bits.  Validity rules are attend_tokens'."""
+        Qc = self._rows(Q, "Q")
+        lens = self._per_seq(lens, "lens")
+        out = _out_for(out, Qc, "size")
+        with _current_stream(self.device) as stream:
+            st = _lib.load().qmha_attend_cached_tokens_window(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[1], lens.data_ptr(),
+                                                              int(window), _lib.QMHA_FLAG_CAUSAL, stream)
+        _lib.check(st, f"KVCache.attend_tokens_window({self.kernel})")
+        return out.view(Q.shape) if out.numel() == Q.numel() and out.dim() != Q.dim() else out
+
     def enable_split(self, chunk_rows: int, max_nq: int = 32) -> None:
         """Allocate the scratch of the split-KV attend (qmha_attend_split_bytes at Nq = max_nq), `.split_scratch`, for
         chunks of chunk_rows key rows: a multiple of 64 with 64 <= chunk_rows <= cap.  Once (a second call replaces the
@@ -560,6 +573,20 @@ class PagedKVCache:
             st = _lib.load().qmha_attend_cached_paged(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[1], lens.data_ptr(),
                                                       table.data_ptr(), _lib.QMHA_FLAG_CAUSAL, stream)
         _lib.check(st, f"PagedKVCache.attend_paged({self.kernel})")
+        return out.view(Q.shape) if out.numel() == Q.numel() and out.dim() != Q.dim() else out
+
+    def attend_paged_window(self, Q: torch.Tensor, lens: torch.Tensor, table: torch.Tensor, window: int,
+                            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """attend_tokens_window through the table (qmha_attend_cached_paged_window), bit for bit.  Only the table columns
+        whose pages hold rows of the window (widened to its first two-tile stage) are read: columns behind them may hold
+        anything, and their pages may belong to another sequence.  A used entry outside [0, num_pages) gives zeros."""
+        Qc = self._rows(Q, "Q")
+        lens, table = self._per_seq(lens, "lens"), self._table(table)
+        out = _out_for(out, Qc, "size")
+        with _current_stream(self.device) as stream:
+            st = _lib.load().qmha_attend_cached_paged_window(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[1], lens.data_ptr(),
+                                                             table.data_ptr(), int(window), _lib.QMHA_FLAG_CAUSAL, stream)
+        _lib.check(st, f"PagedKVCache.attend_paged_window({self.kernel})")
         return out.view(Q.shape) if out.numel() == Q.numel() and out.dim() != Q.dim() else out
 
     def attend_paged_split(self, Q: torch.Tensor, lens: torch.Tensor, table: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:

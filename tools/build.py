@@ -32,6 +32,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
 KERNEL_SOURCES = ["qmha_fa_int8.hip", "qmha_fa_f16.hip", "qmha_fa_masked.hip", "qmha_fa_split.hip", "qmha_fa_packed.hip",
+                  "qmha_fa_window.hip",
                   "qmha_prepass.hip",
                   "qmha_fa_f32.hip", "qmha_unfused.hip", "qmha_api.cpp"]
 # profiling builds (QMHA_EXTRA_FLAGS=-DQMHA_ABLATION) enable the tuning alternatives of the fp16 / fp32 / api
@@ -84,6 +85,7 @@ FILE_FLAGS = {"qmha_fa_int8.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + os
               "qmha_fa_masked.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + os.environ.get("QMHA_CAUSAL_FLAGS", "").split(),
               "qmha_fa_split.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + os.environ.get("QMHA_CAUSAL_FLAGS", "").split(),
               "qmha_fa_packed.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + os.environ.get("QMHA_CAUSAL_FLAGS", "").split(),
+              "qmha_fa_window.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + os.environ.get("QMHA_CAUSAL_FLAGS", "").split(),
               "qmha_fa_f32.hip": os.environ.get("QMHA_F32_FLAGS", "").split()}
 
 

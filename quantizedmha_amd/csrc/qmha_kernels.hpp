@@ -264,10 +264,9 @@ hipError_t launch_fa_window(const F16Workspace& w, const float* Qf, float* O, co
 // there; n, cap, len multiples of 32, len + n <= cap.  pos non-null (DEVICE int32[B], read by the kernel; len ignored):
 // sequence b's rows go to [pos[b], pos[b] + n); pos[b] < 0, pos[b] % 32 != 0 or pos[b] + n > cap: that sequence writes
 // nothing.  Bad host arguments: hipErrorInvalidValue.
-hipError_t launch_kv_append(const float* K, const float* V, const Int8Workspace& w, int B, int n, int cap, int len,
-                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream);
-hipError_t launch_kv_append(const float* K, const float* V, const F16Workspace& w, int B, int n, int cap, int len,
-                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream);
+template <class W>  // Int8Workspace or F16Workspace, as for the two below
+hipError_t launch_kv_append(const float* K, const float* V, const W& w, int B, int n, int cap, int len, const int32_t* pos, int H, int D,
+                            int d_model, hipStream_t stream);
 
 // Token-granular append: any 1 <= n <= cap rows per sequence at any row pos[b] (DEVICE int32[B], non-null);
 // every 32-row group that rows [pos[b], pos[b] + n) touch is written as the append kernels write that group's rows so
@@ -278,10 +277,9 @@ hipError_t launch_kv_append(const float* K, const float* V, const F16Workspace& 
 // b goes to group g % (page_rows / 32) of page table[b][g / (page_rows / 32)]; an entry of a touched page outside
 // [0, num_pages) is an invalid pos[b].  The tail stays per sequence.
 inline size_t kv_tail_bytes(int B, int H, int D) { return align_up((size_t)2 * B * 32 * H * D * sizeof(float), 256); }
-hipError_t launch_kv_tokens(const float* K, const float* V, const Int8Workspace& w, float* tail, int B, int n, int cap,
-                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream, const PageTable& pt = {});
-hipError_t launch_kv_tokens(const float* K, const float* V, const F16Workspace& w, float* tail, int B, int n, int cap,
-                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream, const PageTable& pt = {});
+template <class W>
+hipError_t launch_kv_tokens(const float* K, const float* V, const W& w, float* tail, int B, int n, int cap, const int32_t* pos, int H, int D,
+                            int d_model, hipStream_t stream, const PageTable& pt = {});
 
 // ---- packed batches (qmha_fa_packed.hip, qmha_prepass.hip) ---------------------------------
 // The token-granular / paged attend and append on operands without a batch axis: Q, O [total, d_model], K, V
@@ -297,12 +295,9 @@ hipError_t launch_fa_packed(const Int8Workspace& w, const float* Qf, float* O, c
                             hipStream_t stream);
 hipError_t launch_fa_packed(const F16Workspace& w, const float* Qf, float* O, const MaskedCall& c, const int32_t* cu, int total,
                             hipStream_t stream);
-hipError_t launch_kv_packed(const float* K, const float* V, const Int8Workspace& w, float* tail, int B, int rows, int max_n, int cap,
-                            const int32_t* cu, const int32_t* pos, int H, int D, int d_model, hipStream_t stream,
-                            const PageTable& pt = {});
-hipError_t launch_kv_packed(const float* K, const float* V, const F16Workspace& w, float* tail, int B, int rows, int max_n, int cap,
-                            const int32_t* cu, const int32_t* pos, int H, int D, int d_model, hipStream_t stream,
-                            const PageTable& pt = {});
+template <class W>
+hipError_t launch_kv_packed(const float* K, const float* V, const W& w, float* tail, int B, int rows, int max_n, int cap, const int32_t* cu,
+                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream, const PageTable& pt = {});
 
 // ---- FP32 (fa: scalar VALU kernel; fa_mfma: the same contract on v_mfma_f32_32x32x2_f32) -----
 hipError_t launch_fa_f32(const float* Q, const float* K, const float* V, float* O, int B, int N, int H, int D,

@@ -5,18 +5,18 @@
 //                           head, sc = max(absmax/127, 1e-8), x_i8 = clamp(rint(x * (1/sc))) --
 //                           K as int8 rows, V as f16-valued integers in the MFMA V^T operand order
 //   qmha_convert_f16_kernel fa_tc_v1a.cu:300-330: K as f16 rows, V in the f16 V^T operand order (RNE)
-//   qmha_kv_append_{int8,f16}_kernel  the same per-group work for the new rows of a persistent K/V cache
-//                           (qmha_kv_cache_append), written behind the cache's valid rows
-//   qmha_kv_place_{int8,f16}_kernel   the append kernels' body with a row per sequence, read from device memory
-//                           (qmha_kv_cache_append_at)
-//   qmha_kv_token_{int8,f16}_kernel   any number of rows at any row of a sequence: the open 32-row group is written
-//                           again from its raw rows (qmha_kv_cache_append_tokens)
-//   qmha_kv_paged_{int8,f16}_kernel   the token kernels' groups in the pages of a pool, found through a block table
-//                           on the device (qmha_kv_cache_append_paged)
-//   qmha_kv_packed_{int8,f16}_kernel, qmha_kv_packed_pages_{int8,f16}_kernel   the token / paged kernels with a row
-//                           count per sequence, read from a device cu[B + 1] over K / V without a batch axis
-//                           (qmha_kv_cache_append_packed / _paged_packed)
+//   qmha_kv_append_{int8,f16}_kernel<D, Row>  the same per-group work for the new rows of a persistent K/V cache,
+//                           whole 32-row groups: behind the cache's valid rows (Row = HostRow, qmha_kv_cache_append,
+//                           DESIGN.md 13) or at a row per sequence read from device memory (PlacedRow,
+//                           qmha_kv_cache_append_at)
+//   qmha_kv_rows_{int8,f16}_kernel<D, Src, Dst>  any number of rows at any row of a sequence: the open 32-row group is
+//                           written again from its raw rows.  Src: the same count for every sequence (UniformRows) or a
+//                           count per sequence read from a device cu[B + 1] over K / V without a batch axis
+//                           (PackedRows); Dst: a contiguous cache (ContiguousRows) or the pages of a pool, found
+//                           through a block table on the device (PagedTable) -- qmha_kv_cache_append_tokens, _paged,
+//                           _packed, _paged_packed (the names before the fold: DESIGN.md 23)
 #include <atomic>
+#include <type_traits>
 
 #include "qmha_common.hpp"
 #include "qmha_kernels.hpp"
@@ -31,12 +31,6 @@ namespace qmha {
 #else
 #define QMHA_PRE_LOAD(p) (*(p))
 #endif
-// ---------------------------------------------------------------------------------------
-// Pre-pass: quantise Q, K, V (fa_tc_int8_b.cu:33-152, fp32_to_int8sram).
-// One wave per (tensor, bh, group); blockIdx.y = tensor (0 Q, 1 K, 2 V).
-// v_mode 0: V as int8 in the i8 V^T operand order (qmha_quantize_int8 layout 1)
-// v_mode 1: V as f16-valued integers in the f16 V^T operand order (main kernel input)
-// ---------------------------------------------------------------------------------------
 // One wave quantises one 32-row group of V (b, k, g) into the V^T operand order through its
 // LDS tile `vtr` (D * QMHA_VT_PITCH bytes): coalesced 16-byte loads (instruction i covers rows
 // i, NI+i, ...: 256-byte row segments), so lane (rq, c4) holds NI CONSECUTIVE rows of columns
@@ -185,83 +179,209 @@ __global__ __launch_bounds__(256) void qmha_convert_f16_kernel(
 // fp16 kernel the loads, the RNE conversion and the vt_group_store of qmha_convert_f16_kernel.
 // Nothing outside groups [len / 32, (len + n) / 32) of a slice is written.
 // ---------------------------------------------------------------------------------------
-// The bodies are qmha_kv_append_{int8,f16}.inc, included inside the __global__ with `len` in scope (why a text
-// include: DESIGN.md 15.3): the append kernels' `len` is their argument, the place kernels' (qmha_kv_cache_append_at,
-// DESIGN.md 15) is their wave's place_row().
-template <int D>
+// One template per precision over a row policy, which sits in the argument slot of the row it stands for and gives a
+// wave the first cache row `len` its sequence writes, or -1: the wave returns, having written nothing (it is per wave
+// and no workgroup barrier follows).  kCanFail: whether a wave has to test its row at all.
+// HostRow (qmha_kv_cache_append): the host's len, the same for every sequence, checked by the launchers.
+struct HostRow {
+    int len;
+    static constexpr bool kCanFail = false;
+    __device__ __forceinline__ int first_row(int, int, int, int) const { return len; }
+};
+// PlacedRow (qmha_kv_cache_append_at): pos[b] of the sequence b the wave's item (the body's (bh, g))
+// belongs to.  The wave returns for an item past the grid's and for an invalid pos[b]: pos[b] < 0, pos[b] % 32 != 0
+// (two's complement: of a negative value too) or pos[b] + n > cap (n <= cap, checked by the launchers).
+struct PlacedRow {
+    const int32_t* __restrict__ pos;  // DEVICE int32 [B]
+    static constexpr bool kCanFail = true;
+    __device__ __forceinline__ int first_row(int n, int cap, int H, int total_groups) const {
+        const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
+        if (item >= total_groups) return -1;
+        const int p = pos[item / (n / QMHA_GROUP) / H];
+        return p >= 0 && (p & (QMHA_GROUP - 1)) == 0 && p <= cap - n ? p : -1;
+    }
+};
+
+template <int D, class Row>
 __global__ __launch_bounds__(256) void qmha_kv_append_int8_kernel(
     const float* __restrict__ K, const float* __restrict__ V, int8_t* __restrict__ Ki, _Float16* __restrict__ Vh,
-    float* __restrict__ sK, float* __restrict__ sV, int n, int cap, int len, int H, int d_model, int total_groups) {
-#include "qmha_kv_append_int8.inc"
+    float* __restrict__ sK, float* __restrict__ sV, int n, int cap, Row row, int H, int d_model, int total_groups) {
+    __shared__ __attribute__((aligned(16))) char vtr[4][D * QMHA_VT_PITCH];
+    const int len = row.first_row(n, cap, H, total_groups);
+    if (Row::kCanFail && len < 0) return;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int item = blockIdx.x * 4 + wave;  // (bh, g)
+    if (item >= total_groups) return;        // wave-uniform
+    const int Gn = n / QMHA_GROUP, Gc = cap / QMHA_GROUP;
+    const int bh = item / Gn, g = item % Gn;
+    const int b = bh / H, k = bh % H;
+    // quant_row_group / quant_v_group index source and destination by ONE row count: group g of n-row arrays,
+    // element (bh n + 32 g) D of the rows, entry bh Gn + g of the scales and of the 64 D-byte V blocks.  They are
+    // called with the chunk's n, which is right for the source; every destination pointer is moved ahead by what
+    // the cache's index of the same group has more: group (bh Gc + len / 32 + g) - (bh Gn + g) = bh (Gc - Gn) +
+    // len / 32 (>= 0, wave-uniform), so the functions -- and the pre-pass kernels built from them -- stay as they are.
+    const size_t ahead = (size_t)bh * (Gc - Gn) + len / QMHA_GROUP;  // in groups
+    if (blockIdx.y == 1)
+        quant_v_group<D, 1>(V, Vh + ahead * (size_t)(32 * D), sV + ahead, vtr[wave], lane, b, k, g, bh, n, Gn, d_model);
+    else
+        quant_row_group<D>(K, Ki + ahead * (size_t)(QMHA_GROUP * D), sK + ahead, lane, b, k, g, bh, n, Gn, d_model);
 }
 
-template <int D>
+template <int D, class Row>
 __global__ __launch_bounds__(256) void qmha_kv_append_f16_kernel(
     const float* __restrict__ K, const float* __restrict__ V, _Float16* __restrict__ Kh, _Float16* __restrict__ Vt,
-    int n, int cap, int len, int H, int d_model, int total_groups) {
-#include "qmha_kv_append_f16.inc"
-}
-
-// The row of its sequence's slices at which a wave of a place kernel writes: pos[b] of the sequence b its item (the
-// bodies' (bh, g)) belongs to, or -1 -- the wave returns, having written nothing; b is per wave and no workgroup
-// barrier follows -- for an item past the grid's and for an invalid pos[b]: pos[b] < 0, pos[b] % 32 != 0 (two's
-// complement: of a negative value too) or pos[b] + n > cap (n <= cap, checked by the launchers).
-__device__ __forceinline__ int place_row(const int32_t* __restrict__ pos, int n, int cap, int H, int total_groups) {
-    const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (item >= total_groups) return -1;
-    const int p = pos[item / (n / QMHA_GROUP) / H];
-    return p >= 0 && (p & (QMHA_GROUP - 1)) == 0 && p <= cap - n ? p : -1;
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void qmha_kv_place_int8_kernel(
-    const float* __restrict__ K, const float* __restrict__ V, int8_t* __restrict__ Ki, _Float16* __restrict__ Vh,
-    float* __restrict__ sK, float* __restrict__ sV, int n, int cap, const int32_t* __restrict__ pos, int H, int d_model,
-    int total_groups) {
-    const int len = place_row(pos, n, cap, H, total_groups);
-    if (len < 0) return;
-#include "qmha_kv_append_int8.inc"
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void qmha_kv_place_f16_kernel(
-    const float* __restrict__ K, const float* __restrict__ V, _Float16* __restrict__ Kh, _Float16* __restrict__ Vt,
-    int n, int cap, const int32_t* __restrict__ pos, int H, int d_model, int total_groups) {
-    const int len = place_row(pos, n, cap, H, total_groups);
-    if (len < 0) return;
-#include "qmha_kv_append_f16.inc"
+    int n, int cap, Row row, int H, int d_model, int total_groups) {
+    constexpr int C4 = D / 4, RPI = 64 / C4, NI = 32 / RPI;
+    __shared__ __attribute__((aligned(16))) char vtr[4][D * QMHA_VT_PITCH];
+    const int len = row.first_row(n, cap, H, total_groups);
+    if (Row::kCanFail && len < 0) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int item = blockIdx.x * 4 + wave;
+    if (item >= total_groups) return;  // wave-uniform; the LDS tile is per wave, no workgroup barrier follows
+    const int Gn = n / QMHA_GROUP, Gc = cap / QMHA_GROUP;
+    const int bh = item / Gn, g = item % Gn;
+    const int b = bh / H, k = bh % H;
+    const int gd = len / QMHA_GROUP + g;
+    v4f x[NI];
+    if (blockIdx.y == 1) {  // V^T operand order: NI consecutive rows per lane (the vt_group_store map)
+        const int rq = lane / C4, c4 = lane % C4;
+        const float* base = V + ((size_t)b * n + (size_t)g * QMHA_GROUP) * d_model + (size_t)k * D + 4 * c4;
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+            x[i] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(base + (size_t)(NI * rq + i) * d_model));
+        vt_group_store<D, false>(vtr[wave], x, 1.0f, lane, reinterpret_cast<char*>(Vt + ((size_t)bh * Gc + gd) * (size_t)(32 * D)));
+        return;
+    }
+    const int ri = lane / C4, ci = lane % C4;  // K: f16 rows
+    const float* base = K + ((size_t)b * n + (size_t)g * QMHA_GROUP) * d_model + (size_t)k * D + 4 * ci;
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+        x[i] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(base + (size_t)(i * RPI + ri) * d_model));
+    _Float16* dst = Kh + ((size_t)bh * cap + (size_t)gd * QMHA_GROUP) * D + 4 * ci;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        v4h hv;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) hv[c] = (_Float16)x[i][c];  // RNE (= __float2half)
+        *reinterpret_cast<v4h*>(dst + (size_t)(i * RPI + ri) * D) = hv;
+    }
 }
 
 // ---------------------------------------------------------------------------------------
-// Token-granular append (qmha_kv_cache_append_tokens): any 1 <= n <= cap rows per sequence at any
-// row pos[b].  A cache that holds L rows of a sequence holds the bytes the append kernels write for those rows
-// zero-padded to ceil32(L), so a touched 32-row group is written whole from its 32 assembled rows.
-// One wave per (tensor, K/V slice, touched group): rows [pos[b], pos[b] + n) touch groups g0 = pos[b] / 32 ..
-// g1 = (pos[b] + n - 1) / 32, at most (n + 30) / 32 + 1 of them.  Item j of a slice: j == 0 runs group g0 and then, if
-// it is another one, group g1; 0 < j < g1 - g0 runs group g0 + j; any other item returns -- so a slice has
-// `maxg` = max(1, (n + 30) / 32) items.  pos[b] < 0 or pos[b] + n > cap: every item of the sequence returns, nothing is written.
+// Token-granular append (qmha_kv_cache_append_tokens, _paged, _packed, _paged_packed): any
+// 1 <= n_b <= cap rows of sequence b at any row pos[b].  A cache that holds L rows of a sequence holds the bytes the
+// append kernels write for those rows zero-padded to ceil32(L), so a touched 32-row group is written whole from its 32
+// assembled rows.  One wave per (tensor, K/V slice, touched group): rows [pos[b], pos[b] + n_b) touch groups
+// g0 = pos[b] / 32 .. g1 = (pos[b] + n_b - 1) / 32, at most (n_b + 30) / 32 + 1 of them.  Item j of a slice: j == 0 runs
+// group g0 and then, if it is another one, group g1 -- reading the tail before it rewrites it --; 0 < j < g1 - g0 runs
+// group g0 + j; any other item returns -- so a slice has `maxg` = max(1, (n + 30) / 32) items, n the host's count or its
+// bound max_n (token_items is monotone, so they suffice for every n_b <= max_n).  pos[b] < 0 or pos[b] + n_b > cap: every
+// item of the sequence returns, nothing is written.  One template per precision over two policies: Src, where a
+// sequence's row count and its first source row come from, and Dst, how a group of the cache is found.
 // ---------------------------------------------------------------------------------------
 // This wave's item: the slice bh, the sequence's first row p (-1: nothing to do) and the groups g0, g1
 struct TokenItem {
     int bh, j, p, g0, g1;
 };
-__device__ __forceinline__ TokenItem token_item(const int32_t* __restrict__ pos, int n, int cap, int H, int maxg, int total) {
-    TokenItem it{0, 0, -1, 0, 0};
-    const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (item >= total) return it;
-    it.bh = item / maxg, it.j = item % maxg;
-    const int p = pos[it.bh / H];
-    if (p < 0 || p > cap - n) return it;
-    it.g0 = p / QMHA_GROUP, it.g1 = (p + n - 1) / QMHA_GROUP;
-    if (it.j == 0 || it.j < it.g1 - it.g0) it.p = p;
-    return it;
+
+// Src: sequence b brings n_b rows of K / V, the first of them row0; false: the wave returns.
+// UniformRows: K and V are [B][n][H * D], the host's n for every sequence.
+struct UniformRows {
+    int n;
+    __device__ __forceinline__ bool rows_of(int b, int& n_b, size_t& row0) const { return n_b = n, row0 = (size_t)b * n, true; }
+};
+// PackedRows: K and V are [rows, H * D] with no batch axis, and sequence b brings the n_b = cu[b + 1] -
+// cu[b] rows [cu[b], cu[b + 1]) (cu: DEVICE int32 [B + 1]).  A wave returns with nothing written, the tail included,
+// when the range is not 0 <= cu[b] <= cu[b + 1] <= rows (it never becomes an address), when n_b == 0 (pos[b] is not
+// looked at) or n_b > max_n, the host's bound; every wave of a sequence reads the same words, so they agree.
+struct PackedRows {
+    const int32_t* __restrict__ cu;
+    int rows, max_n;
+    __device__ __forceinline__ bool rows_of(int b, int& n_b, size_t& row0) const {
+        const int c0 = __builtin_amdgcn_readfirstlane(cu[b]), c1 = __builtin_amdgcn_readfirstlane(cu[b + 1]);
+        if (c0 < 0 || c1 < c0 || c1 > rows) return false;
+        const int n = c1 - c0;
+        if (n == 0 || n > max_n) return false;
+        return n_b = n, row0 = c0, true;
+    }
+};
+
+// Dst: the capacity of a sequence, and the index of group g of slice bh in the cache's arrays.
+// ContiguousRows: `cap` rows a slice, and the lookup itself.
+struct ContiguousRows {
+    int cap;
+    __device__ __forceinline__ int capacity() const { return cap; }
+    __device__ __forceinline__ size_t operator()(int bh, int g) const { return (size_t)bh * (cap / QMHA_GROUP) + g; }
+};
+// PagedTable: a pool of pages.  max_pages * page_rows is the logical capacity; group g of sequence b,
+// K/V head k is group g % PG of slice page * H + k, page = table[b][g / PG], PG = page_rows / 32 (PagedGroups).  The
+// tail belongs to the sequence slot b, not to a page.
+struct PagedTable {
+    const int32_t* table;  // DEVICE int32 [B][max_pages]
+    int PG, max_pages, num_pages;
+    __device__ __forceinline__ int capacity() const { return max_pages * PG * QMHA_GROUP; }
+};
+// The pool indices of the (at most two) groups a wave's item runs, looked up once, ahead of the group loop: scalar
+// arithmetic (the item is per wave) that is over before a group's rows are held in registers.
+struct PagedGroups {
+    int g_last;             // it.g1: the group of the second pass, or of the only one
+    size_t first, last;     // the index of group it.g0 + it.j, and of group it.g1
+    __device__ __forceinline__ size_t operator()(int, int g) const { return g == g_last ? last : first; }
+};
+__device__ __forceinline__ PagedGroups paged_groups(const PagedTable& t, const TokenItem& it, int H) {
+    const int32_t* row = t.table + (size_t)(it.bh / H) * t.max_pages;
+    auto index = [&](int g) {
+        const unsigned c = (unsigned)g / (unsigned)t.PG;
+        // valid (rows_item's scan); clamped all the same, so that no table content leaves the pool
+        const unsigned page = min((unsigned)__builtin_amdgcn_readfirstlane(row[c]), (unsigned)(t.num_pages - 1));
+        return ((size_t)page * H + (unsigned)(it.bh % H)) * t.PG + ((unsigned)g - c * (unsigned)t.PG);
+    };
+    return {it.g1, index(it.g0 + it.j), index(it.g1)};
 }
 
-// The index of group g of slice bh in the cache's arrays: the token kernels' contiguous rows, the paged kernels' lookup
-struct ContiguousGroups {
-    int Gc;  // groups of a slice: cap / 32
-    __device__ __forceinline__ size_t operator()(int bh, int g) const { return (size_t)bh * Gc + g; }
+// The prologue of a wave: its item, its sequence's rows and the lookup of its groups (it.p < 0: the wave returns, and
+// the rest means nothing).  The item is per wave and is held in scalar registers.
+template <class Dst>
+struct RowsItem {
+    TokenItem it;
+    int n;  // the sequence's rows, and the first of them in K / V:
+    size_t row0;
+    std::conditional_t<std::is_same_v<Dst, PagedTable>, PagedGroups, ContiguousRows> groups;
 };
+template <class Src, class Dst>
+__device__ __forceinline__ RowsItem<Dst> rows_item(const Src& src, const int32_t* __restrict__ pos, const Dst& dst, int H, int maxg,
+                                                   int total) {
+    RowsItem<Dst> r{{0, 0, -1, 0, 0}, 0, 0, {}};
+    TokenItem& it = r.it;
+    const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (item >= total) return r;
+    it.bh = item / maxg, it.j = item % maxg;
+    const int b = it.bh / H, cap = dst.capacity();
+    if (!src.rows_of(b, r.n, r.row0)) return r;
+    const int n = r.n, p = __builtin_amdgcn_readfirstlane(pos[b]);
+    if (p < 0 || p > cap - n) return r;
+    it.g0 = p / QMHA_GROUP, it.g1 = (p + n - 1) / QMHA_GROUP;
+    if (it.j == 0 || it.j < it.g1 - it.g0) it.p = p;
+    if constexpr (!std::is_same_v<Dst, PagedTable>) {
+        r.groups = dst;
+    } else {
+        // the table entries of the pages that rows [pos[b], pos[b] + n_b) touch are looked at by the wave's lanes: one
+        // outside [0, num_pages) and every item of the sequence returns with nothing written, the tail included (each of
+        // them scans the same entries)
+        if (it.p < 0) return r;
+        const int32_t* row = dst.table + (size_t)b * dst.max_pages;
+        const int c0 = (unsigned)it.g0 / (unsigned)dst.PG, c1 = (unsigned)it.g1 / (unsigned)dst.PG;  // <= max_pages - 1: p + n <= cap
+        bool bad = false;
+        for (int c = c0 + (threadIdx.x & 63); c <= c1; c += 64) bad |= (unsigned)row[c] >= (unsigned)dst.num_pages;
+        if (__builtin_amdgcn_ballot_w64(bad)) it.p = -1;
+        // the item is per wave: in scalar registers the page arithmetic costs the int8 d = 32 kernel no occupancy step
+        it.bh = __builtin_amdgcn_readfirstlane(it.bh), it.j = __builtin_amdgcn_readfirstlane(it.j), it.p = __builtin_amdgcn_readfirstlane(it.p);
+        it.g0 = __builtin_amdgcn_readfirstlane(it.g0), it.g1 = __builtin_amdgcn_readfirstlane(it.g1);
+        if (it.p >= 0) r.groups = paged_groups(dst, it, H);
+    }
+    return r;
+}
 
 // int8.  The open group's scale comes from the rows present (zero rows do not move an absmax), and the group is
 // quantised again from its raw rows whenever rows are added: `tail` ([2][B][32][H * D] fp32, K then V) keeps the raw
@@ -323,23 +443,23 @@ __device__ __forceinline__ void token_groups_int8(const float* __restrict__ X, f
     }
 }
 
-template <int D>
-__global__ __launch_bounds__(256) void qmha_kv_token_int8_kernel(
+template <int D, class Src, class Dst>
+__global__ __launch_bounds__(256) void qmha_kv_rows_int8_kernel(
     const float* __restrict__ K, const float* __restrict__ V, int8_t* __restrict__ Ki, _Float16* __restrict__ Vh,
-    float* __restrict__ sK, float* __restrict__ sV, float* __restrict__ tail, int B, int n, int cap,
-    const int32_t* __restrict__ pos, int H, int d_model, int maxg, int total) {
+    float* __restrict__ sK, float* __restrict__ sV, float* __restrict__ tail, int B, Src rows, const int32_t* __restrict__ pos,
+    Dst dst, int H, int d_model, int maxg, int total) {
     __shared__ __attribute__((aligned(16))) char vtr[4][D * QMHA_VT_PITCH];
-    const TokenItem it = token_item(pos, n, cap, H, maxg, total);
+    const RowsItem<Dst> r = rows_item(rows, pos, dst, H, maxg, total);
+    const TokenItem& it = r.it;
     if (it.p < 0) return;  // wave-uniform; the LDS tile is per wave, no workgroup barrier follows
     const int b = it.bh / H, k = it.bh % H;
     const size_t col = (size_t)k * D + 4 * ((threadIdx.x & 63) % (D / 4));  // this lane's columns of a row
-    const size_t src = (size_t)b * n * d_model + col, trow = (size_t)b * QMHA_GROUP * d_model + col;
+    const size_t src = r.row0 * d_model + col, trow = (size_t)b * QMHA_GROUP * d_model + col;
     if (blockIdx.y == 1)
-        token_groups_int8<D, true>(V + src, tail + (size_t)B * QMHA_GROUP * d_model + trow, Ki, Vh, sV, vtr[threadIdx.x >> 6], it, n,
-                                   ContiguousGroups{cap / QMHA_GROUP}, d_model);
+        token_groups_int8<D, true>(V + src, tail + (size_t)B * QMHA_GROUP * d_model + trow, Ki, Vh, sV, vtr[threadIdx.x >> 6], it, r.n,
+                                   r.groups, d_model);
     else
-        token_groups_int8<D, false>(K + src, tail + trow, Ki, Vh, sK, vtr[threadIdx.x >> 6], it, n, ContiguousGroups{cap / QMHA_GROUP},
-                                    d_model);
+        token_groups_int8<D, false>(K + src, tail + trow, Ki, Vh, sK, vtr[threadIdx.x >> 6], it, r.n, r.groups, d_model);
 }
 
 // fp16: a row converts on its own, so there is no tail.  A group this call opens (a group behind g0, or g0 when pos[b]
@@ -393,208 +513,17 @@ __device__ __forceinline__ void token_groups_f16(const float* __restrict__ X, _F
     }
 }
 
-template <int D>
-__global__ __launch_bounds__(256) void qmha_kv_token_f16_kernel(
-    const float* __restrict__ K, const float* __restrict__ V, _Float16* __restrict__ Kh, _Float16* __restrict__ Vt,
-    int n, int cap, const int32_t* __restrict__ pos, int H, int d_model, int maxg, int total) {
+template <int D, class Src, class Dst>
+__global__ __launch_bounds__(256) void qmha_kv_rows_f16_kernel(
+    const float* __restrict__ K, const float* __restrict__ V, _Float16* __restrict__ Kh, _Float16* __restrict__ Vt, Src rows,
+    const int32_t* __restrict__ pos, Dst dst, int H, int d_model, int maxg, int total) {
     __shared__ __attribute__((aligned(16))) char vtr[4][D * QMHA_VT_PITCH];
-    const TokenItem it = token_item(pos, n, cap, H, maxg, total);
+    const RowsItem<Dst> r = rows_item(rows, pos, dst, H, maxg, total);
+    const TokenItem& it = r.it;
     if (it.p < 0) return;  // wave-uniform; the LDS tile is per wave, no workgroup barrier follows
-    const size_t src = (size_t)(it.bh / H) * n * d_model + (size_t)(it.bh % H) * D;
-    if (blockIdx.y == 1) token_groups_f16<D, true>(V + src, Kh, Vt, vtr[threadIdx.x >> 6], it, n, ContiguousGroups{cap / QMHA_GROUP}, d_model);
-    else token_groups_f16<D, false>(K + src, Kh, Vt, vtr[threadIdx.x >> 6], it, n, ContiguousGroups{cap / QMHA_GROUP}, d_model);
-}
-
-// ---------------------------------------------------------------------------------------
-// Paged append (qmha_kv_cache_append_paged): the token kernels' items, groups and tail protocol over a
-// pool of pages.  cap = max_pages * page_rows is the logical capacity; group g of sequence b, K/V head k is group
-// g % PG of slice page * H + k, page = table[b][g / PG], PG = page_rows / 32 -- the one thing that differs (PagedGroups).
-// A wave's item is decided as token_item decides it, and then the table entries of the pages that rows
-// [pos[b], pos[b] + n) touch are looked at by the wave's lanes: one outside [0, num_pages) and every item of the sequence
-// returns with nothing written, the tail included (each of them scans the same entries).  The tail belongs to the
-// sequence slot b, not to a page.
-// ---------------------------------------------------------------------------------------
-struct PagedTable {
-    const int32_t* table;  // DEVICE int32 [B][max_pages]
-    int PG, max_pages, num_pages;
-};
-// The pool indices of the (at most two) groups a wave's item runs, looked up once, ahead of the group loop: scalar
-// arithmetic (the item is per wave) that is over before a group's rows are held in registers.
-struct PagedGroups {
-    int g_last;             // it.g1: the group of the second pass, or of the only one
-    size_t first, last;     // the index of group it.g0 + it.j, and of group it.g1
-    __device__ __forceinline__ size_t operator()(int, int g) const { return g == g_last ? last : first; }
-};
-__device__ __forceinline__ TokenItem paged_item(const int32_t* __restrict__ pos, const PagedTable& t, int n, int H, int maxg, int total) {
-    TokenItem it = token_item(pos, n, t.max_pages * t.PG * QMHA_GROUP, H, maxg, total);
-    if (it.p < 0) return it;
-    const int32_t* row = t.table + (size_t)(it.bh / H) * t.max_pages;
-    const int c0 = (unsigned)it.g0 / (unsigned)t.PG, c1 = (unsigned)it.g1 / (unsigned)t.PG;  // <= max_pages - 1: p + n <= cap
-    bool bad = false;
-    for (int c = c0 + (threadIdx.x & 63); c <= c1; c += 64) bad |= (unsigned)row[c] >= (unsigned)t.num_pages;
-    if (__builtin_amdgcn_ballot_w64(bad)) it.p = -1;
-    // the item is per wave: in scalar registers the page arithmetic costs the int8 d = 32 kernel no occupancy step
-    it.bh = __builtin_amdgcn_readfirstlane(it.bh), it.j = __builtin_amdgcn_readfirstlane(it.j), it.p = __builtin_amdgcn_readfirstlane(it.p);
-    it.g0 = __builtin_amdgcn_readfirstlane(it.g0), it.g1 = __builtin_amdgcn_readfirstlane(it.g1);
-    return it;
-}
-
-__device__ __forceinline__ PagedGroups paged_groups(const PagedTable& t, const TokenItem& it, int H) {
-    const int32_t* row = t.table + (size_t)(it.bh / H) * t.max_pages;
-    auto index = [&](int g) {
-        const unsigned c = (unsigned)g / (unsigned)t.PG;
-        // valid (paged_item); clamped all the same, so that no table content leaves the pool
-        const unsigned page = min((unsigned)__builtin_amdgcn_readfirstlane(row[c]), (unsigned)(t.num_pages - 1));
-        return ((size_t)page * H + (unsigned)(it.bh % H)) * t.PG + ((unsigned)g - c * (unsigned)t.PG);
-    };
-    return {it.g1, index(it.g0 + it.j), index(it.g1)};
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void qmha_kv_paged_int8_kernel(
-    const float* __restrict__ K, const float* __restrict__ V, int8_t* __restrict__ Ki, _Float16* __restrict__ Vh,
-    float* __restrict__ sK, float* __restrict__ sV, float* __restrict__ tail, int B, int n, const int32_t* __restrict__ pos,
-    PagedTable t, int H, int d_model, int maxg, int total) {
-    __shared__ __attribute__((aligned(16))) char vtr[4][D * QMHA_VT_PITCH];
-    const TokenItem it = paged_item(pos, t, n, H, maxg, total);
-    if (it.p < 0) return;  // wave-uniform; the LDS tile is per wave, no workgroup barrier follows
-    const int b = it.bh / H, k = it.bh % H;
-    const PagedGroups groups = paged_groups(t, it, H);
-    const size_t col = (size_t)k * D + 4 * ((threadIdx.x & 63) % (D / 4));  // this lane's columns of a row
-    const size_t src = (size_t)b * n * d_model + col, trow = (size_t)b * QMHA_GROUP * d_model + col;
-    if (blockIdx.y == 1)
-        token_groups_int8<D, true>(V + src, tail + (size_t)B * QMHA_GROUP * d_model + trow, Ki, Vh, sV, vtr[threadIdx.x >> 6], it, n,
-                                   groups, d_model);
-    else
-        token_groups_int8<D, false>(K + src, tail + trow, Ki, Vh, sK, vtr[threadIdx.x >> 6], it, n, groups, d_model);
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void qmha_kv_paged_f16_kernel(
-    const float* __restrict__ K, const float* __restrict__ V, _Float16* __restrict__ Kh, _Float16* __restrict__ Vt,
-    int n, const int32_t* __restrict__ pos, PagedTable t, int H, int d_model, int maxg, int total) {
-    __shared__ __attribute__((aligned(16))) char vtr[4][D * QMHA_VT_PITCH];
-    const TokenItem it = paged_item(pos, t, n, H, maxg, total);
-    if (it.p < 0) return;  // wave-uniform; the LDS tile is per wave, no workgroup barrier follows
-    const PagedGroups groups = paged_groups(t, it, H);
-    const size_t src = (size_t)(it.bh / H) * n * d_model + (size_t)(it.bh % H) * D;
-    if (blockIdx.y == 1) token_groups_f16<D, true>(V + src, Kh, Vt, vtr[threadIdx.x >> 6], it, n, groups, d_model);
-    else token_groups_f16<D, false>(K + src, Kh, Vt, vtr[threadIdx.x >> 6], it, n, groups, d_model);
-}
-
-// ---------------------------------------------------------------------------------------
-// Packed append (qmha_kv_cache_append_packed / _paged_packed): K and V are [total, H * D] with no batch
-// axis, and sequence b brings the n_b = cu[b + 1] - cu[b] rows [cu[b], cu[b + 1]) (cu: DEVICE int32 [B + 1]) to cache
-// rows [pos[b], pos[b] + n_b).  The token kernels' items, groups and tail protocol, with n and the source row taken
-// from the device: a slice has `maxg` items sized for the host's bound max_n (token_items is monotone, so they suffice
-// for every n_b <= max_n), item 0 runs group g0 and then g1 -- reading the tail before it rewrites it --, and the items
-// beyond a sequence's own groups return.  A wave returns with nothing written, the tail included, when the range is not
-// 0 <= cu[b] <= cu[b + 1] <= total (it never becomes an address), when n_b == 0 (pos[b] is not looked at), n_b > max_n,
-// pos[b] < 0 or pos[b] + n_b > cap; every wave of a sequence reads the same words, so they agree.  The item is per wave
-// and is held in scalar registers, as paged_item's.
-// ---------------------------------------------------------------------------------------
-struct PackedItem {
-    TokenItem it;
-    int n, row0;  // the sequence's rows, and the first of them in K / V
-};
-__device__ __forceinline__ PackedItem packed_item(const int32_t* __restrict__ cu, const int32_t* __restrict__ pos, int rows, int max_n,
-                                                  int cap, int H, int maxg, int total) {
-    PackedItem r{{0, 0, -1, 0, 0}, 0, 0};
-    const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
-    if (item >= total) return r;
-    r.it.bh = item / maxg, r.it.j = item % maxg;
-    const int b = r.it.bh / H;
-    const int c0 = __builtin_amdgcn_readfirstlane(cu[b]), c1 = __builtin_amdgcn_readfirstlane(cu[b + 1]);
-    if (c0 < 0 || c1 < c0 || c1 > rows) return r;
-    const int n = c1 - c0;
-    if (n == 0 || n > max_n) return r;
-    const int p = __builtin_amdgcn_readfirstlane(pos[b]);
-    if (p < 0 || p > cap - n) return r;
-    r.n = n, r.row0 = c0;
-    r.it.g0 = p / QMHA_GROUP, r.it.g1 = (p + n - 1) / QMHA_GROUP;
-    if (r.it.j == 0 || r.it.j < r.it.g1 - r.it.g0) r.it.p = p;
-    return r;
-}
-// paged_item's scan of the table entries that rows [pos[b], pos[b] + n_b) touch: one outside the pool and the item returns
-__device__ __forceinline__ void packed_scan(TokenItem& it, const PagedTable& t, int H) {
-    if (it.p < 0) return;
-    const int32_t* row = t.table + (size_t)(it.bh / H) * t.max_pages;
-    const int c0 = (unsigned)it.g0 / (unsigned)t.PG, c1 = (unsigned)it.g1 / (unsigned)t.PG;  // <= max_pages - 1: p + n_b <= cap
-    bool bad = false;
-    for (int c = c0 + (threadIdx.x & 63); c <= c1; c += 64) bad |= (unsigned)row[c] >= (unsigned)t.num_pages;
-    if (__builtin_amdgcn_ballot_w64(bad)) it.p = -1;
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void qmha_kv_packed_int8_kernel(
-    const float* __restrict__ K, const float* __restrict__ V, int8_t* __restrict__ Ki, _Float16* __restrict__ Vh,
-    float* __restrict__ sK, float* __restrict__ sV, float* __restrict__ tail, int B, int rows, int max_n, int cap,
-    const int32_t* __restrict__ cu, const int32_t* __restrict__ pos, int H, int d_model, int maxg, int total) {
-    __shared__ __attribute__((aligned(16))) char vtr[4][D * QMHA_VT_PITCH];
-    const PackedItem pk = packed_item(cu, pos, rows, max_n, cap, H, maxg, total);
-    const TokenItem it = pk.it;
-    if (it.p < 0) return;  // wave-uniform; the LDS tile is per wave, no workgroup barrier follows
-    const int b = it.bh / H, k = it.bh % H;
-    const size_t col = (size_t)k * D + 4 * ((threadIdx.x & 63) % (D / 4));  // this lane's columns of a row
-    const size_t src = (size_t)pk.row0 * d_model + col, trow = (size_t)b * QMHA_GROUP * d_model + col;
-    if (blockIdx.y == 1)
-        token_groups_int8<D, true>(V + src, tail + (size_t)B * QMHA_GROUP * d_model + trow, Ki, Vh, sV, vtr[threadIdx.x >> 6], it, pk.n,
-                                   ContiguousGroups{cap / QMHA_GROUP}, d_model);
-    else
-        token_groups_int8<D, false>(K + src, tail + trow, Ki, Vh, sK, vtr[threadIdx.x >> 6], it, pk.n, ContiguousGroups{cap / QMHA_GROUP},
-                                    d_model);
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void qmha_kv_packed_f16_kernel(
-    const float* __restrict__ K, const float* __restrict__ V, _Float16* __restrict__ Kh, _Float16* __restrict__ Vt,
-    int rows, int max_n, int cap, const int32_t* __restrict__ cu, const int32_t* __restrict__ pos, int H, int d_model, int maxg,
-    int total) {
-    __shared__ __attribute__((aligned(16))) char vtr[4][D * QMHA_VT_PITCH];
-    const PackedItem pk = packed_item(cu, pos, rows, max_n, cap, H, maxg, total);
-    const TokenItem it = pk.it;
-    if (it.p < 0) return;  // wave-uniform; the LDS tile is per wave, no workgroup barrier follows
-    const size_t src = (size_t)pk.row0 * d_model + (size_t)(it.bh % H) * D;
-    if (blockIdx.y == 1) token_groups_f16<D, true>(V + src, Kh, Vt, vtr[threadIdx.x >> 6], it, pk.n, ContiguousGroups{cap / QMHA_GROUP}, d_model);
-    else token_groups_f16<D, false>(K + src, Kh, Vt, vtr[threadIdx.x >> 6], it, pk.n, ContiguousGroups{cap / QMHA_GROUP}, d_model);
-}
-
-// Over a pool of pages: the logical capacity is max_pages * page_rows, the touched entries are scanned, the groups looked up
-template <int D>
-__global__ __launch_bounds__(256) void qmha_kv_packed_pages_int8_kernel(
-    const float* __restrict__ K, const float* __restrict__ V, int8_t* __restrict__ Ki, _Float16* __restrict__ Vh,
-    float* __restrict__ sK, float* __restrict__ sV, float* __restrict__ tail, int B, int rows, int max_n,
-    const int32_t* __restrict__ cu, const int32_t* __restrict__ pos, PagedTable t, int H, int d_model, int maxg, int total) {
-    __shared__ __attribute__((aligned(16))) char vtr[4][D * QMHA_VT_PITCH];
-    const PackedItem pk = packed_item(cu, pos, rows, max_n, t.max_pages * t.PG * QMHA_GROUP, H, maxg, total);
-    TokenItem it = pk.it;
-    packed_scan(it, t, H);
-    if (it.p < 0) return;  // wave-uniform; the LDS tile is per wave, no workgroup barrier follows
-    const int b = it.bh / H, k = it.bh % H;
-    const PagedGroups groups = paged_groups(t, it, H);
-    const size_t col = (size_t)k * D + 4 * ((threadIdx.x & 63) % (D / 4));  // this lane's columns of a row
-    const size_t src = (size_t)pk.row0 * d_model + col, trow = (size_t)b * QMHA_GROUP * d_model + col;
-    if (blockIdx.y == 1)
-        token_groups_int8<D, true>(V + src, tail + (size_t)B * QMHA_GROUP * d_model + trow, Ki, Vh, sV, vtr[threadIdx.x >> 6], it, pk.n,
-                                   groups, d_model);
-    else
-        token_groups_int8<D, false>(K + src, tail + trow, Ki, Vh, sK, vtr[threadIdx.x >> 6], it, pk.n, groups, d_model);
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void qmha_kv_packed_pages_f16_kernel(
-    const float* __restrict__ K, const float* __restrict__ V, _Float16* __restrict__ Kh, _Float16* __restrict__ Vt,
-    int rows, int max_n, const int32_t* __restrict__ cu, const int32_t* __restrict__ pos, PagedTable t, int H, int d_model, int maxg,
-    int total) {
-    __shared__ __attribute__((aligned(16))) char vtr[4][D * QMHA_VT_PITCH];
-    const PackedItem pk = packed_item(cu, pos, rows, max_n, t.max_pages * t.PG * QMHA_GROUP, H, maxg, total);
-    TokenItem it = pk.it;
-    packed_scan(it, t, H);
-    if (it.p < 0) return;  // wave-uniform; the LDS tile is per wave, no workgroup barrier follows
-    const PagedGroups groups = paged_groups(t, it, H);
-    const size_t src = (size_t)pk.row0 * d_model + (size_t)(it.bh % H) * D;
-    if (blockIdx.y == 1) token_groups_f16<D, true>(V + src, Kh, Vt, vtr[threadIdx.x >> 6], it, pk.n, groups, d_model);
-    else token_groups_f16<D, false>(K + src, Kh, Vt, vtr[threadIdx.x >> 6], it, pk.n, groups, d_model);
+    const size_t src = r.row0 * d_model + (size_t)(it.bh % H) * D;
+    if (blockIdx.y == 1) token_groups_f16<D, true>(V + src, Kh, Vt, vtr[threadIdx.x >> 6], it, r.n, r.groups, d_model);
+    else token_groups_f16<D, false>(K + src, Kh, Vt, vtr[threadIdx.x >> 6], it, r.n, r.groups, d_model);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1046,41 +975,50 @@ hipError_t launch_convert_f16(const float* Q, const float* K, const float* V, co
     }
 }
 
+// ---- the append launches, each written once over the workspace type.  What a precision brings: its head sizes (cache_d),
+// whether it keeps raw rows in a tail (tail_ok), and its kernels with the cache arrays they take ahead of the shared
+// arguments `a` (append_kernel, rows_kernel) ----
+template <class F> static hipError_t cache_d(const Int8Workspace&, int D, F&& f) { return int8_masked_d(D, f); }
+template <class F> static hipError_t cache_d(const F16Workspace&, int D, F&& f) { return f16_masked_d(D, f); }
+static bool tail_ok(const Int8Workspace&, const float* tail) { return tail != nullptr; }
+static bool tail_ok(const F16Workspace&, const float*) { return true; }
+
+template <int D, class Row, class... A>
+static void append_kernel(const Int8Workspace& w, dim3 grid, hipStream_t stream, const float* K, const float* V, int n, int cap, Row row, A... a) {
+    hipLaunchKernelGGL((qmha_kv_append_int8_kernel<D, Row>), grid, dim3(256), 0, stream, K, V, w.Ki, w.Vh, w.sK, w.sV, n, cap, row, a...);
+}
+template <int D, class Row, class... A>
+static void append_kernel(const F16Workspace& w, dim3 grid, hipStream_t stream, const float* K, const float* V, int n, int cap, Row row, A... a) {
+    hipLaunchKernelGGL((qmha_kv_append_f16_kernel<D, Row>), grid, dim3(256), 0, stream, K, V, w.Kh, w.Vt, n, cap, row, a...);
+}
+template <int D, class Src, class Dst, class... A>
+static void rows_kernel(const Int8Workspace& w, float* tail, int B, dim3 grid, hipStream_t stream, const float* K, const float* V, Src src,
+                        const int32_t* pos, Dst dst, A... a) {
+    hipLaunchKernelGGL((qmha_kv_rows_int8_kernel<D, Src, Dst>), grid, dim3(256), 0, stream, K, V, w.Ki, w.Vh, w.sK, w.sV, tail, B, src, pos, dst,
+                       a...);
+}
+template <int D, class Src, class Dst, class... A>
+static void rows_kernel(const F16Workspace& w, float*, int, dim3 grid, hipStream_t stream, const float* K, const float* V, Src src,
+                        const int32_t* pos, Dst dst, A... a) {
+    hipLaunchKernelGGL((qmha_kv_rows_f16_kernel<D, Src, Dst>), grid, dim3(256), 0, stream, K, V, w.Kh, w.Vt, src, pos, dst, a...);
+}
+
 // ---- K/V cache append: w is the carve at N = cap; rows [len, len + n) of every head slice are written, or, with a
-// pos (read on the device), rows [pos[b], pos[b] + n) of sequence b's by the place kernels ----
+// pos (read on the device), rows [pos[b], pos[b] + n) of sequence b's (PlacedRow) ----
 static bool kv_append_shape_ok(int B, int n, int cap, int len, int H) {
     return B >= 1 && H >= 1 && n >= QMHA_GROUP && n % QMHA_GROUP == 0 && cap % QMHA_GROUP == 0 && len >= 0 &&
            len % QMHA_GROUP == 0 && (long long)len + n <= cap;
 }
 
-hipError_t launch_kv_append(const float* K, const float* V, const Int8Workspace& w, int B, int n, int cap, int len,
-                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream) {
+template <class W>
+hipError_t launch_kv_append(const float* K, const float* V, const W& w, int B, int n, int cap, int len, const int32_t* pos, int H, int D,
+                            int d_model, hipStream_t stream) {
     if (!kv_append_shape_ok(B, n, cap, pos ? 0 : len, H)) return hipErrorInvalidValue;
     const int total = B * H * (n / QMHA_GROUP);
     const dim3 grid((total + 3) / 4, 2);
-    return int8_masked_d(D, [&](auto d) {
-        if (pos)
-            hipLaunchKernelGGL((qmha_kv_place_int8_kernel<decltype(d)::value>), grid, dim3(256), 0, stream, K, V, w.Ki, w.Vh, w.sK,
-                               w.sV, n, cap, pos, H, d_model, total);
-        else
-            hipLaunchKernelGGL((qmha_kv_append_int8_kernel<decltype(d)::value>), grid, dim3(256), 0, stream, K, V, w.Ki, w.Vh, w.sK,
-                               w.sV, n, cap, len, H, d_model, total);
-        return hipGetLastError();
-    });
-}
-
-hipError_t launch_kv_append(const float* K, const float* V, const F16Workspace& w, int B, int n, int cap, int len,
-                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream) {
-    if (!kv_append_shape_ok(B, n, cap, pos ? 0 : len, H)) return hipErrorInvalidValue;
-    const int total = B * H * (n / QMHA_GROUP);
-    const dim3 grid((total + 3) / 4, 2);
-    return f16_masked_d(D, [&](auto d) {
-        if (pos)
-            hipLaunchKernelGGL((qmha_kv_place_f16_kernel<decltype(d)::value>), grid, dim3(256), 0, stream, K, V, w.Kh, w.Vt, n, cap,
-                               pos, H, d_model, total);
-        else
-            hipLaunchKernelGGL((qmha_kv_append_f16_kernel<decltype(d)::value>), grid, dim3(256), 0, stream, K, V, w.Kh, w.Vt, n, cap,
-                               len, H, d_model, total);
+    return cache_d(w, D, [&](auto d) {
+        if (pos) append_kernel<decltype(d)::value>(w, grid, stream, K, V, n, cap, PlacedRow{pos}, H, d_model, total);
+        else append_kernel<decltype(d)::value>(w, grid, stream, K, V, n, cap, HostRow{len}, H, d_model, total);
         return hipGetLastError();
     });
 }
@@ -1098,38 +1036,27 @@ static bool kv_pages_ok(const PageTable& pt, int cap) {
                          (long long)pt.max_pages * pt.page_rows == cap);
 }
 
-hipError_t launch_kv_tokens(const float* K, const float* V, const Int8Workspace& w, float* tail, int B, int n, int cap,
-                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream, const PageTable& pt) {
-    if (!kv_tokens_shape_ok(B, n, cap, pos, H) || !tail || !kv_pages_ok(pt, cap)) return hipErrorInvalidValue;
-    const int maxg = token_items(n), total = B * H * maxg;
-    return int8_masked_d(D, [&](auto d) {
-        if (pt.table) {
-            hipLaunchKernelGGL((qmha_kv_paged_int8_kernel<decltype(d)::value>), dim3((total + 3) / 4, 2), dim3(256), 0, stream, K, V, w.Ki,
-                               w.Vh, w.sK, w.sV, tail, B, n, pos, PagedTable{pt.table, pt.page_rows / QMHA_GROUP, pt.max_pages, pt.num_pages},
-                               H, d_model, maxg, total);
-            return hipGetLastError();
-        }
-        hipLaunchKernelGGL((qmha_kv_token_int8_kernel<decltype(d)::value>), dim3((total + 3) / 4, 2), dim3(256), 0, stream, K, V, w.Ki,
-                           w.Vh, w.sK, w.sV, tail, B, n, cap, pos, H, d_model, maxg, total);
+// the launch of the rows kernels: items sized for max_n rows a sequence, the groups in a pool's pages or in `cap` rows a slice
+template <class W, class Src>
+static hipError_t kv_rows(const float* K, const float* V, const W& w, float* tail, int B, Src src, int max_n, int cap, const int32_t* pos,
+                          int H, int D, int d_model, hipStream_t stream, const PageTable& pt) {
+    const int maxg = token_items(max_n), total = B * H * maxg;
+    const dim3 grid((total + 3) / 4, 2);
+    return cache_d(w, D, [&](auto d) {
+        if (pt.table)
+            rows_kernel<decltype(d)::value>(w, tail, B, grid, stream, K, V, src, pos,
+                                            PagedTable{pt.table, pt.page_rows / QMHA_GROUP, pt.max_pages, pt.num_pages}, H, d_model, maxg, total);
+        else
+            rows_kernel<decltype(d)::value>(w, tail, B, grid, stream, K, V, src, pos, ContiguousRows{cap}, H, d_model, maxg, total);
         return hipGetLastError();
     });
 }
 
-hipError_t launch_kv_tokens(const float* K, const float* V, const F16Workspace& w, float*, int B, int n, int cap,
-                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream, const PageTable& pt) {
-    if (!kv_tokens_shape_ok(B, n, cap, pos, H) || !kv_pages_ok(pt, cap)) return hipErrorInvalidValue;
-    const int maxg = token_items(n), total = B * H * maxg;
-    return f16_masked_d(D, [&](auto d) {
-        if (pt.table) {
-            hipLaunchKernelGGL((qmha_kv_paged_f16_kernel<decltype(d)::value>), dim3((total + 3) / 4, 2), dim3(256), 0, stream, K, V, w.Kh,
-                               w.Vt, n, pos, PagedTable{pt.table, pt.page_rows / QMHA_GROUP, pt.max_pages, pt.num_pages}, H, d_model, maxg,
-                               total);
-            return hipGetLastError();
-        }
-        hipLaunchKernelGGL((qmha_kv_token_f16_kernel<decltype(d)::value>), dim3((total + 3) / 4, 2), dim3(256), 0, stream, K, V, w.Kh,
-                           w.Vt, n, cap, pos, H, d_model, maxg, total);
-        return hipGetLastError();
-    });
+template <class W>
+hipError_t launch_kv_tokens(const float* K, const float* V, const W& w, float* tail, int B, int n, int cap, const int32_t* pos, int H, int D,
+                            int d_model, hipStream_t stream, const PageTable& pt) {
+    if (!kv_tokens_shape_ok(B, n, cap, pos, H) || !tail_ok(w, tail) || !kv_pages_ok(pt, cap)) return hipErrorInvalidValue;
+    return kv_rows(K, V, w, tail, B, UniformRows{n}, n, cap, pos, H, D, d_model, stream, pt);
 }
 
 // ---- packed append: rows [cu[b], cu[b + 1]) of K / V to rows [pos[b], ...) of sequence b ----
@@ -1138,38 +1065,19 @@ static bool kv_packed_shape_ok(int B, int rows, int max_n, int cap, const int32_
            (long long)B * H * token_items(max_n) <= 0x7fffffffLL;
 }
 
-hipError_t launch_kv_packed(const float* K, const float* V, const Int8Workspace& w, float* tail, int B, int rows, int max_n, int cap,
-                            const int32_t* cu, const int32_t* pos, int H, int D, int d_model, hipStream_t stream, const PageTable& pt) {
-    if (!kv_packed_shape_ok(B, rows, max_n, cap, cu, pos, H) || !tail || !kv_pages_ok(pt, cap)) return hipErrorInvalidValue;
-    const int maxg = token_items(max_n), total = B * H * maxg;
-    return int8_masked_d(D, [&](auto d) {
-        if (pt.table) {
-            hipLaunchKernelGGL((qmha_kv_packed_pages_int8_kernel<decltype(d)::value>), dim3((total + 3) / 4, 2), dim3(256), 0, stream, K, V,
-                               w.Ki, w.Vh, w.sK, w.sV, tail, B, rows, max_n, cu, pos,
-                               PagedTable{pt.table, pt.page_rows / QMHA_GROUP, pt.max_pages, pt.num_pages}, H, d_model, maxg, total);
-            return hipGetLastError();
-        }
-        hipLaunchKernelGGL((qmha_kv_packed_int8_kernel<decltype(d)::value>), dim3((total + 3) / 4, 2), dim3(256), 0, stream, K, V, w.Ki,
-                           w.Vh, w.sK, w.sV, tail, B, rows, max_n, cap, cu, pos, H, d_model, maxg, total);
-        return hipGetLastError();
-    });
+template <class W>
+hipError_t launch_kv_packed(const float* K, const float* V, const W& w, float* tail, int B, int rows, int max_n, int cap, const int32_t* cu,
+                            const int32_t* pos, int H, int D, int d_model, hipStream_t stream, const PageTable& pt) {
+    if (!kv_packed_shape_ok(B, rows, max_n, cap, cu, pos, H) || !tail_ok(w, tail) || !kv_pages_ok(pt, cap)) return hipErrorInvalidValue;
+    return kv_rows(K, V, w, tail, B, PackedRows{cu, rows, max_n}, max_n, cap, pos, H, D, d_model, stream, pt);
 }
 
-hipError_t launch_kv_packed(const float* K, const float* V, const F16Workspace& w, float*, int B, int rows, int max_n, int cap,
-                            const int32_t* cu, const int32_t* pos, int H, int D, int d_model, hipStream_t stream, const PageTable& pt) {
-    if (!kv_packed_shape_ok(B, rows, max_n, cap, cu, pos, H) || !kv_pages_ok(pt, cap)) return hipErrorInvalidValue;
-    const int maxg = token_items(max_n), total = B * H * maxg;
-    return f16_masked_d(D, [&](auto d) {
-        if (pt.table) {
-            hipLaunchKernelGGL((qmha_kv_packed_pages_f16_kernel<decltype(d)::value>), dim3((total + 3) / 4, 2), dim3(256), 0, stream, K, V,
-                               w.Kh, w.Vt, rows, max_n, cu, pos, PagedTable{pt.table, pt.page_rows / QMHA_GROUP, pt.max_pages, pt.num_pages},
-                               H, d_model, maxg, total);
-            return hipGetLastError();
-        }
-        hipLaunchKernelGGL((qmha_kv_packed_f16_kernel<decltype(d)::value>), dim3((total + 3) / 4, 2), dim3(256), 0, stream, K, V, w.Kh,
-                           w.Vt, rows, max_n, cap, cu, pos, H, d_model, maxg, total);
-        return hipGetLastError();
-    });
-}
+// the two precisions of each (declared in qmha_kernels.hpp)
+template decltype(launch_kv_append<Int8Workspace>) launch_kv_append<Int8Workspace>;
+template decltype(launch_kv_append<F16Workspace>) launch_kv_append<F16Workspace>;
+template decltype(launch_kv_tokens<Int8Workspace>) launch_kv_tokens<Int8Workspace>;
+template decltype(launch_kv_tokens<F16Workspace>) launch_kv_tokens<F16Workspace>;
+template decltype(launch_kv_packed<Int8Workspace>) launch_kv_packed<Int8Workspace>;
+template decltype(launch_kv_packed<F16Workspace>) launch_kv_packed<F16Workspace>;
 
 }  // namespace qmha

@@ -204,6 +204,10 @@ def test_production_library_has_one_kernel_per_variant_and_d(built):
             # head size (Ragged, Paged, Packed<Ragged>, Packed<Paged>; the split template: its base, Ragged or Paged)
             g = re.match(r"NS_\d+([A-Za-z]+?)(?:INS_\d+([A-Za-z]+?)EE)?E", rest)
             name += "[%s]" % (g.group(1) if g.group(2) is None else "%s<%s>" % g.groups())
+        if re.fullmatch(r"qmha_kv_(append|rows)_(int8|f16)_kernel", name):  # <D, Row> and <D, Src, Dst>
+            # the appends of a persistent K/V cache are two templates per precision: one instance per policy
+            # combination and head size
+            name += "[%s]" % ", ".join(p for p in re.match(r"NS_\d+([A-Za-z]+)E(?:NS_\d+([A-Za-z]+)E)?EEv", rest).groups() if p)
         if name == "qmha_fa_int8_pipe_kernel":  # <D, WAVES, FL>
             m, fl = re.match(r"Li(\d+)ELi(\d+)E", rest), 2
         elif name == "qmha_fa_int8_kernel":  # <D, FL> (the one-tile kernel: N = 32, and d outside 32/64/128)
@@ -233,6 +237,13 @@ def test_production_library_has_one_kernel_per_variant_and_d(built):
         for family, geos in (("cache", ("Ragged", "Paged", "Packed<Ragged>", "Packed<Paged>")), ("split", ("Ragged", "Paged"))):
             got = sorted(k for k in per if k[0].startswith(f"qmha_fa_{stem}_{family}_kernel"))
             assert got == sorted((f"qmha_fa_{stem}_{family}_kernel[{g}]", d) for g in geos for d in ds), got
+    # the append and rows templates: exactly their policy combinations at every built head size
+    for stem, ds in (("int8", ["128", "32", "64"]), ("f16", ["128", "64"])):
+        for family, combos in (("append", ("HostRow", "PlacedRow")),
+                               ("rows", ("UniformRows, ContiguousRows", "UniformRows, PagedTable", "PackedRows, ContiguousRows",
+                                         "PackedRows, PagedTable"))):
+            got = sorted(k for k in per if k[0].startswith(f"qmha_kv_{family}_{stem}_kernel"))
+            assert got == sorted((f"qmha_kv_{family}_{stem}_kernel[{c}]", d) for c in combos for d in ds), got
     for name, d, twin in dumps:  # exactly the production schedule (same WAVES, flags, PAD) plus the stores
         if name == "qmha_fa_int8_pt_v3_kernel":  # the 8-wave production instance (the 4-wave one has no twin)
             assert twin in per[(name, d)], (name, d, twin)

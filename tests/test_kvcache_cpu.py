@@ -12,6 +12,8 @@ import subprocess
 
 import pytest
 
+from tests import append_syms
+
 from tests import gpu_support as gs
 from tests.gpu_support import CAUSAL
 
@@ -149,10 +151,12 @@ def test_failed_launch_leaves_the_length(lib, cache):
 def test_library_has_five_append_kernels_and_ten_masked(lib):
     path = os.path.join(ROOT, "quantizedmha_amd", "lib", "libqmha.so")
     syms = subprocess.run(["nm", path], capture_output=True, text=True, check=True).stdout
-    stubs = sorted(set(re.findall(r"__device_stub__(qmha_kv_append_\w+?_kernel)ILi(\d+)EEEv", syms)))
-    assert stubs == [("qmha_kv_append_f16_kernel", "128"), ("qmha_kv_append_f16_kernel", "64"),
-                     ("qmha_kv_append_int8_kernel", "128"), ("qmha_kv_append_int8_kernel", "32"),
-                     ("qmha_kv_append_int8_kernel", "64")], stubs
+    # the append template over HostRow (its other row policy: test_varlen_cpu.py)
+    stubs = append_syms.append(syms, row="HostRow")
+    assert stubs == [("qmha_kv_append_f16_kernel", "HostRow", "128"), ("qmha_kv_append_f16_kernel", "HostRow", "64"),
+                     ("qmha_kv_append_int8_kernel", "HostRow", "128"), ("qmha_kv_append_int8_kernel", "HostRow", "32"),
+                     ("qmha_kv_append_int8_kernel", "HostRow", "64")], stubs
+    append_syms.check_family(syms)
     masked = set(re.findall(r"__device_stub__(qmha_fa_\w+?_masked_kernel)ILi(\d+)ENS_\d+([A-Za-z]+?)E(\w*)", syms))
     # the cache runs the shipped Rect instances: still ten of the SquareCausal and Rect geometries, and beside them
     # nothing but the five grouped-query ones

@@ -16,6 +16,7 @@ import subprocess
 
 import pytest
 
+from tests import append_syms
 from tests import packed_ref as pk
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -191,25 +192,30 @@ def test_library_has_the_twenty_packed_kernels_beside_the_old(lib):
     sizes = {"int8": ["128", "32", "64"], "f16": ["128", "64"]}
     # the cache kernel template over Packed<Ragged> and Packed<Paged>
     for family, pattern in (("qmha_fa_{}_cache_kernel", r"__device_stub__(qmha_fa_(?:int8|f16)_cache_kernel)ILi(\d+)ENS_6PackedINS_6RaggedEEEEEv"),
-                            ("qmha_fa_{}_cache_kernel", r"__device_stub__(qmha_fa_(?:int8|f16)_cache_kernel)ILi(\d+)ENS_6PackedINS_5PagedEEEEEv"),
-                            ("qmha_kv_packed_{}_kernel", r"__device_stub__(qmha_kv_packed_(?:int8|f16)_kernel)ILi(\d+)EEEv"),
-                            ("qmha_kv_packed_pages_{}_kernel", r"__device_stub__(qmha_kv_packed_pages_(?:int8|f16)_kernel)ILi(\d+)EEEv")):
+                            ("qmha_fa_{}_cache_kernel", r"__device_stub__(qmha_fa_(?:int8|f16)_cache_kernel)ILi(\d+)ENS_6PackedINS_5PagedEEEEEv")):
         got = sorted(set(re.findall(pattern, syms)))
         want = sorted((family.format(p), d) for p, ds in sizes.items() for d in ds)
         assert got == want, (family, got)
+    # the rows template over PackedRows, and ContiguousRows or PagedTable
+    for dst in ("ContiguousRows", "PagedTable"):
+        got = append_syms.rows(syms, src="PackedRows", dst=dst)
+        assert got == sorted((f"qmha_kv_rows_{p}_kernel", "PackedRows", dst, d) for p, ds in sizes.items() for d in ds), (dst, got)
     # one instance of each per head size: no second geometry, no dumping twin
     assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_cache_kernelILi\d+ENS_6Packed\w*)", syms))) == 10
     assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_cache_kernel\w*)", syms))) == 20  # four geometries, nothing else
-    assert len(set(re.findall(r"__device_stub__(qmha_kv_packed_\w+)", syms))) == 10
+    assert len(append_syms.rows(syms, src="PackedRows")) == 10
+    append_syms.check_family(syms)
     # what the library held before
     masked = set(re.findall(r"__device_stub__(qmha_fa_\w+?_masked_kernel)ILi(\d+)ENS_\d+([A-Za-z]+?)E(\w*)", syms))
     assert len(masked) == 15 and {m[2] for m in masked} == {"SquareCausal", "Rect", "Grouped"}, sorted(masked)
     for family, n in ((r"qmha_fa_\w+?_varlen_kernel\w*", 5), (r"qmha_fa_\w+?_cache_kernelILi\d+ENS_6Ragged\w*", 5),
                       (r"qmha_fa_\w+?_cache_kernelILi\d+ENS_5Paged\w*", 5), (r"qmha_fa_\w+?_split_kernelILi\d+ENS_6Ragged\w*", 5),
-                      (r"qmha_fa_\w+?_split_kernelILi\d+ENS_5Paged\w*", 5), (r"qmha_split_combine_kernel\w*", 1),
-                      (r"qmha_kv_token_\w+", 5), (r"qmha_kv_paged_\w+", 5), (r"qmha_kv_place_\w+", 5)):
+                      (r"qmha_fa_\w+?_split_kernelILi\d+ENS_5Paged\w*", 5), (r"qmha_split_combine_kernel\w*", 1)):
         assert len(set(re.findall(rf"__device_stub__({family})", syms))) == n, family
-    assert len(set(re.findall(r"__device_stub__(qmha_kv_append_\w+?_kernel)ILi(\d+)EEEv", syms))) == 5
+    for dst in ("ContiguousRows", "PagedTable"):
+        assert append_syms.rows(syms, src="UniformRows", dst=dst) == append_syms.want_rows(("UniformRows",), (dst,)), dst
+    for row in append_syms.ROWS:
+        assert append_syms.append(syms, row=row) == append_syms.want_append((row,)), row
 
 
 # ---- the bindings ----------------------------------------------------------------------------------------------------------
@@ -291,15 +297,16 @@ def test_the_restated_formulas_stand_in_the_source():
                 "if (qb0 * WAVES >= U) return;           // no active unit leaves before any barrier or DMA issue")),
             ("qmha_prepass.hip", (
                 "static int token_items(int n) { return n <= 2 ? 1 : (n + QMHA_GROUP - 2) / QMHA_GROUP; }",
-                "if (c0 < 0 || c1 < c0 || c1 > rows) return r;",
+                "if (c0 < 0 || c1 < c0 || c1 > rows) return false;",
                 "const int n = c1 - c0;",
-                "if (n == 0 || n > max_n) return r;",
+                "if (n == 0 || n > max_n) return false;",
+                "return n_b = n, row0 = c0, true;",
+                "if (!src.rows_of(b, r.n, r.row0)) return r;",
                 "if (p < 0 || p > cap - n) return r;",
-                "r.n = n, r.row0 = c0;",
-                "r.it.g0 = p / QMHA_GROUP, r.it.g1 = (p + n - 1) / QMHA_GROUP;",
-                "if (r.it.j == 0 || r.it.j < r.it.g1 - r.it.g0) r.it.p = p;",
+                "it.g0 = p / QMHA_GROUP, it.g1 = (p + n - 1) / QMHA_GROUP;",
+                "if (it.j == 0 || it.j < it.g1 - it.g0) it.p = p;",
                 "const int lo = p - g * QMHA_GROUP, hi = lo + n;  // the new rows of this group: lo <= r < hi",
-                "const size_t src = (size_t)pk.row0 * d_model + col, trow = (size_t)b * QMHA_GROUP * d_model + col;",
+                "const size_t src = r.row0 * d_model + col, trow = (size_t)b * QMHA_GROUP * d_model + col;",
                 "const int maxg = token_items(max_n), total = B * H * maxg;"))):
         have = lines(name)
         for ln in wanted:

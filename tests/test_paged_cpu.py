@@ -15,6 +15,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import append_syms
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CAUSAL = 1
 V1A, INT8 = 1, 2
@@ -252,22 +254,24 @@ def test_library_has_the_ten_paged_kernels_beside_the_old(lib):
     assert main == [("qmha_fa_f16_cache_kernel", "128"), ("qmha_fa_f16_cache_kernel", "64"),
                     ("qmha_fa_int8_cache_kernel", "128"), ("qmha_fa_int8_cache_kernel", "32"),
                     ("qmha_fa_int8_cache_kernel", "64")], main
-    append = sorted(set(re.findall(r"__device_stub__(qmha_kv_paged_(?:int8|f16)_kernel)ILi(\d+)EEEv", syms)))
-    assert append == [("qmha_kv_paged_f16_kernel", "128"), ("qmha_kv_paged_f16_kernel", "64"),
-                      ("qmha_kv_paged_int8_kernel", "128"), ("qmha_kv_paged_int8_kernel", "32"),
-                      ("qmha_kv_paged_int8_kernel", "64")], append
+    # the rows template over UniformRows and PagedTable
+    append = append_syms.rows(syms, src="UniformRows", dst="PagedTable")
+    u, t = "UniformRows", "PagedTable"
+    assert append == [("qmha_kv_rows_f16_kernel", u, t, "128"), ("qmha_kv_rows_f16_kernel", u, t, "64"),
+                      ("qmha_kv_rows_int8_kernel", u, t, "128"), ("qmha_kv_rows_int8_kernel", u, t, "32"),
+                      ("qmha_kv_rows_int8_kernel", u, t, "64")], append
     # one instance of each: no second geometry, no dumping twin
     assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_cache_kernelILi\d+ENS_5Paged\w*)", syms))) == 5
     assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_cache_kernel\w*)", syms))) == 20  # four geometries, nothing else
-    assert len(set(re.findall(r"__device_stub__(qmha_kv_paged_\w+)", syms))) == 5
+    append_syms.check_family(syms)
     # what the library held before
     masked = set(re.findall(r"__device_stub__(qmha_fa_\w+?_masked_kernel)ILi(\d+)ENS_\d+([A-Za-z]+?)E(\w*)", syms))
     assert len(masked) == 15 and {m[2] for m in masked} == {"SquareCausal", "Rect", "Grouped"}, sorted(masked)
     assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_varlen_kernel\w*)", syms))) == 5
     assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_cache_kernelILi\d+ENS_6Ragged\w*)", syms))) == 5
-    assert len(set(re.findall(r"__device_stub__(qmha_kv_token_\w+)", syms))) == 5
-    assert len(set(re.findall(r"__device_stub__(qmha_kv_append_\w+?_kernel)ILi(\d+)EEEv", syms))) == 5
-    assert len(set(re.findall(r"__device_stub__(qmha_kv_place_\w+)", syms))) == 5
+    assert append_syms.rows(syms, src="UniformRows", dst="ContiguousRows") == append_syms.want_rows(("UniformRows",), ("ContiguousRows",))
+    assert append_syms.append(syms, row="HostRow") == append_syms.want_append(("HostRow",))
+    assert append_syms.append(syms, row="PlacedRow") == append_syms.want_append(("PlacedRow",))
 
 
 # ---- the bindings ----------------------------------------------------------------------------------------------------------

@@ -16,6 +16,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import append_syms
+
 from tests import split_ref as sr
 from tests.gpu_support import BUILT
 
@@ -188,8 +190,9 @@ def test_library_has_the_eleven_split_kernels_beside_the_old(lib):
     assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_varlen_kernel\w*)", syms))) == 5
     assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_cache_kernelILi\d+ENS_6Ragged\w*)", syms))) == 5
     assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_cache_kernelILi\d+ENS_5Paged\w*)", syms))) == 5
-    assert len(set(re.findall(r"__device_stub__(qmha_kv_token_\w+)", syms))) == 5
-    assert len(set(re.findall(r"__device_stub__(qmha_kv_paged_\w+)", syms))) == 5
+    assert append_syms.rows(syms, src="UniformRows", dst="ContiguousRows") == append_syms.want_rows(("UniformRows",), ("ContiguousRows",))
+    assert append_syms.rows(syms, src="UniformRows", dst="PagedTable") == append_syms.want_rows(("UniformRows",), ("PagedTable",))
+    append_syms.check_family(syms)
 
 
 # ---- the bindings ----------------------------------------------------------------------------------------------------------

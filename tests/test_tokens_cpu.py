@@ -16,6 +16,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import append_syms
+
 from tests import rect_ref as rr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -169,20 +171,22 @@ def test_library_has_the_ten_new_kernels_beside_the_old(lib):
     assert main == [("qmha_fa_f16_cache_kernel", "128"), ("qmha_fa_f16_cache_kernel", "64"),
                     ("qmha_fa_int8_cache_kernel", "128"), ("qmha_fa_int8_cache_kernel", "32"),
                     ("qmha_fa_int8_cache_kernel", "64")], main
-    token = sorted(set(re.findall(r"__device_stub__(qmha_kv_token_(?:int8|f16)_kernel)ILi(\d+)EEEv", syms)))
-    assert token == [("qmha_kv_token_f16_kernel", "128"), ("qmha_kv_token_f16_kernel", "64"),
-                     ("qmha_kv_token_int8_kernel", "128"), ("qmha_kv_token_int8_kernel", "32"),
-                     ("qmha_kv_token_int8_kernel", "64")], token
+    # the rows template over UniformRows and ContiguousRows (its other policies: test_paged_cpu.py, test_packed_cpu.py)
+    token = append_syms.rows(syms, src="UniformRows", dst="ContiguousRows")
+    u, c = "UniformRows", "ContiguousRows"
+    assert token == [("qmha_kv_rows_f16_kernel", u, c, "128"), ("qmha_kv_rows_f16_kernel", u, c, "64"),
+                     ("qmha_kv_rows_int8_kernel", u, c, "128"), ("qmha_kv_rows_int8_kernel", u, c, "32"),
+                     ("qmha_kv_rows_int8_kernel", u, c, "64")], token
     # one instance of each: no second geometry, no dumping twin
     assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_cache_kernelILi\d+ENS_6Ragged\w*)", syms))) == 5
     assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_cache_kernel\w*)", syms))) == 20  # four geometries, nothing else
-    assert len(set(re.findall(r"__device_stub__(qmha_kv_token_\w+)", syms))) == 5
+    append_syms.check_family(syms)  # four policy pairs of the rows template, two of the append template, nothing else
     # what the library held before: fifteen masked and five varlen main kernels, five append and five place kernels
     masked = set(re.findall(r"__device_stub__(qmha_fa_\w+?_masked_kernel)ILi(\d+)ENS_\d+([A-Za-z]+?)E(\w*)", syms))
     assert len(masked) == 15 and {m[2] for m in masked} == {"SquareCausal", "Rect", "Grouped"}, sorted(masked)
     assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_varlen_kernel\w*)", syms))) == 5
-    assert len(set(re.findall(r"__device_stub__(qmha_kv_append_\w+?_kernel)ILi(\d+)EEEv", syms))) == 5
-    assert len(set(re.findall(r"__device_stub__(qmha_kv_place_\w+)", syms))) == 5
+    assert append_syms.append(syms, row="HostRow") == append_syms.want_append(("HostRow",))
+    assert append_syms.append(syms, row="PlacedRow") == append_syms.want_append(("PlacedRow",))
 
 
 @pytest.mark.parametrize("cls", ["KVCache", "GroupedKVCache"])

@@ -14,6 +14,8 @@ import subprocess
 
 import pytest
 
+from tests import append_syms
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CAUSAL = 1
 V1A, INT8 = 1, 2
@@ -116,18 +118,19 @@ def test_library_has_the_ten_new_kernels_beside_the_old(lib):
     assert main == [("qmha_fa_f16_varlen_kernel", "128"), ("qmha_fa_f16_varlen_kernel", "64"),
                     ("qmha_fa_int8_varlen_kernel", "128"), ("qmha_fa_int8_varlen_kernel", "32"),
                     ("qmha_fa_int8_varlen_kernel", "64")], main
-    place = sorted(set(re.findall(r"__device_stub__(qmha_kv_place_(?:int8|f16)_kernel)ILi(\d+)EEEv", syms)))
-    assert place == [("qmha_kv_place_f16_kernel", "128"), ("qmha_kv_place_f16_kernel", "64"),
-                     ("qmha_kv_place_int8_kernel", "128"), ("qmha_kv_place_int8_kernel", "32"),
-                     ("qmha_kv_place_int8_kernel", "64")], place
+    # the append template over PlacedRow
+    place = append_syms.append(syms, row="PlacedRow")
+    assert place == [("qmha_kv_append_f16_kernel", "PlacedRow", "128"), ("qmha_kv_append_f16_kernel", "PlacedRow", "64"),
+                     ("qmha_kv_append_int8_kernel", "PlacedRow", "128"), ("qmha_kv_append_int8_kernel", "PlacedRow", "32"),
+                     ("qmha_kv_append_int8_kernel", "PlacedRow", "64")], place
     # one instance of each: no second geometry, no dumping twin
     assert len(set(re.findall(r"__device_stub__(qmha_fa_\w+?_varlen_kernel\w*)", syms))) == 5
-    assert len(set(re.findall(r"__device_stub__(qmha_kv_place_\w+)", syms))) == 5
+    append_syms.check_family(syms)
     # what the library held before: fifteen masked main kernels, five append kernels
     masked = set(re.findall(r"__device_stub__(qmha_fa_\w+?_masked_kernel)ILi(\d+)ENS_\d+([A-Za-z]+?)E(\w*)", syms))
     assert len(masked) == 15 and {m[2] for m in masked} == {"SquareCausal", "Rect", "Grouped"}, sorted(masked)
-    append = set(re.findall(r"__device_stub__(qmha_kv_append_\w+?_kernel)ILi(\d+)EEEv", syms))
-    assert len(append) == 5, sorted(append)
+    append = append_syms.append(syms, row="HostRow")
+    assert append == append_syms.want_append(("HostRow",)) and len(append) == 5, append
 
 
 @pytest.mark.parametrize("cls", ["KVCache", "GroupedKVCache"])

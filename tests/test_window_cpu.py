@@ -16,6 +16,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import append_syms
+
 from tests import window_ref as wr
 from tests.gpu_support import BUILT, F16, INT8
 
@@ -112,10 +114,16 @@ def test_library_has_the_ten_window_kernels_beside_the_old(lib):
                       (r"qmha_fa_\w+?_cache_kernelILi\d+ENS_6Ragged\w*", 5), (r"qmha_fa_\w+?_cache_kernelILi\d+ENS_5Paged\w*", 5),
                       (r"qmha_fa_\w+?_cache_kernelILi\d+ENS_6Packed\w*", 10),
                       (r"qmha_fa_\w+?_split_kernelILi\d+ENS_6Ragged\w*", 5), (r"qmha_fa_\w+?_split_kernelILi\d+ENS_5Paged\w*", 5),
-                      (r"qmha_split_combine_kernel\w*", 1), (r"qmha_kv_token_\w+", 5), (r"qmha_kv_paged_\w+", 5),
-                      (r"qmha_kv_place_\w+", 5), (r"qmha_kv_packed_\w+", 10)):
+                      (r"qmha_split_combine_kernel\w*", 1)):
         assert len(set(re.findall(rf"__device_stub__({family})", syms))) == n, family
-    assert len(set(re.findall(r"__device_stub__(qmha_kv_append_\w+?_kernel)ILi(\d+)EEEv", syms))) == 5
+    # the appends: five instances of each policy pair of the rows template (token, paged, packed, packed pages) and of each
+    # row policy of the append template (append, place)
+    for src in append_syms.SRCS:
+        for dst in append_syms.DSTS:
+            assert append_syms.rows(syms, src=src, dst=dst) == append_syms.want_rows((src,), (dst,)), (src, dst)
+    for row in append_syms.ROWS:
+        assert append_syms.append(syms, row=row) == append_syms.want_append((row,)), row
+    append_syms.check_family(syms)
 
 
 def test_python_binding_has_the_methods():

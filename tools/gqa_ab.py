@@ -139,7 +139,7 @@ def main():
             "clock_probe": bench.clock_probe(dev),
             "isa_sha16": {"ref_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_masked_kernelILi{a.d}ENS_4RectE"),
                           "gqa_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_masked_kernelILi{a.d}ENS_7GroupedE"),
-                          "append": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_kv_append_{stem}_kernelILi{a.d}E")},
+                          "append": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_kv_append_{stem}_kernelILi{a.d}ENS_7HostRowE")},
             "device": torch.cuda.get_device_properties(dev).name,
         }
         print(json.dumps(res), flush=True)

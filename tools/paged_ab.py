@@ -168,8 +168,8 @@ def main():
                 "clock_probe": bench.clock_probe(dev),
                 "isa_sha16": {"ragged_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_cache_kernelILi{a.d}ENS_6RaggedEEEv"),
                               "paged_main": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_fa_{stem}_cache_kernelILi{a.d}ENS_5PagedEEEv"),
-                              "token_append": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_kv_token_{stem}_kernelILi{a.d}E"),
-                              "paged_append": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_kv_paged_{stem}_kernelILi{a.d}E")},
+                              "token_append": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_kv_rows_{stem}_kernelILi{a.d}ENS_11UniformRowsENS_14ContiguousRowsE"),
+                              "paged_append": isa_id.isa_sha16(_lib.LIB_PATH, f"qmha_kv_rows_{stem}_kernelILi{a.d}ENS_11UniformRowsENS_10PagedTableE")},
                 "device": torch.cuda.get_device_properties(dev).name})
     print(json.dumps(res), flush=True)
     if not (all(same.values()) and sane):

@@ -34,10 +34,12 @@ typedef enum {
     QMHA_UNFUSED = 3,      /* mha_kernels/unfused.cu    : QK^T, softmax, PV (3 kernels)   */
     QMHA_FA_MFMA = 4,      /* fa.cu's fp32 contract on v_mfma_f32_32x32x2_f32 (no reference
                               counterpart: the matrix-core sibling of the scalar `fa`)    */
-    QMHA_FA_TC_INT8_PT = 5 /* per-tensor int8 mode (no reference counterpart: BASELINE.json's
+    QMHA_FA_TC_INT8_PT = 5, /* per-tensor int8 mode (no reference counterpart: BASELINE.json's
                               "per-tensor Q/K/V quant", SURVEY 0.2's optional flag): one scale
                               per head slice of Q/K/V, static P scale 1/127, O accumulated on
                               the matrix core                                              */
+    QMHA_FA_TC_FP8 = 6     /* an e4m3 K/V cache on the fp8 matrix cores (no reference counterpart):
+                              a K/V cache variant only, see "fp8 K/V caches" below        */
 } qmha_variant_t;
 
 /* Status codes of the extended entry points. */
@@ -256,6 +258,34 @@ int qmha_attend_cached_varlen(qmha_kv_cache_t *c, const float *Q, float *O, int 
  * calls can be captured in a hipGraph); the cache's mutex is held across the enqueue; qmha_profile records are those of
  * append / attend.
  */
+/*
+ * fp8 K/V caches -- variant QMHA_FA_TC_FP8 ("fa_tc_fp8"), d = 64 and 128: two bytes per cached (K, V) element pair, no
+ * scale arrays in memory and no tail.  The variant lives in the K/V cache only: qmha_solve_* return QMHA_ERR_NOSYS and
+ * qmha_workspace_size is 0.
+ *
+ *   format    OCP e4m3 (e4m3fn: max 448, no infinities).  A cached element is e4m3_rne(clamp(x / scale, -448, 448)), the
+ *             clamp in fp32 ahead of the convert; NaN inputs are unspecified.
+ *   scales    three host floats per cache, q_scale, k_scale and v_scale, 1.0 until qmha_kv_cache_set_scales.  They travel
+ *             as kernel arguments: nothing about them is in device memory.  set_scales is host only and enqueues nothing;
+ *             rows appended earlier keep the bytes of the scale they were appended with.  A scale that is not finite and
+ *             > 0, or a cache of another variant: QMHA_ERR_INVALID.
+ *   layout    qmha_kv_cache_bytes / _paged_bytes: two arrays of slices * rows * d bytes, each starting on a multiple of
+ *             256.  K: e4m3 rows [slice][rows][d].  V: per 32-row group a block of 32 * d bytes in the operand order of
+ *             the P@V MFMA: element (d, kv) at byte ((d >> 5) * 16 + (d & 15)) * 64 + (slot >> 3) * 16 + ((d >> 4) & 1) * 8
+ *             + (slot & 7), slot the f16 V^T block's slot of key kv.  Zero-padding as for fp16: a row converts on its own,
+ *             and an append inside a group relies on the group's later rows being zero.  tail_bytes is 0, attach_tail
+ *             returns QMHA_OK without a buffer.
+ *   attend    Q converts in registers with q_scale; S = (q8 . k8, fp32 accumulate) * q_scale * k_scale * log2(e) / sqrt(d),
+ *             masked before the row maximum; online softmax over the true running maximum m, tile by tile;
+ *             p = exp2(s - m + 8) <= 256 is converted to e4m3 for P@V, the row sum l adds the fp32 p, and
+ *             O = v_scale * o / l (0 unless l > 1e-10, as for fp16).  A ragged call is the call on zero-padded operands.
+ *   built     create, create_gqa, create_paged, append, append_at, append_tokens, append_paged, attend (causal and, at
+ *             len == cap, unmasked), attend_varlen, attend_tokens, attend_paged, truncate, len: every rule of those entry
+ *             points is the one stated with them.
+ *   not built the split, packed and windowed entry points: QMHA_ERR_NOSYS, before any HIP call.
+ */
+int qmha_kv_cache_set_scales(qmha_kv_cache_t *c, float q_scale, float k_scale, float v_scale);
+
 size_t qmha_kv_cache_tail_bytes(const qmha_kv_cache_t *c);
 int qmha_kv_cache_attach_tail(qmha_kv_cache_t *c, void *mem, size_t bytes);
 int qmha_kv_cache_append_tokens(qmha_kv_cache_t *c, const float *K, const float *V, int n, const int32_t *pos, void *stream);

@@ -12,7 +12,8 @@ LIB_DIR = os.path.join(HERE, "lib")
 # QMHA_LIB_PATH: load another build of the same C-ABI (A/B kernel experiments); still no fallback
 LIB_PATH = os.environ.get("QMHA_LIB_PATH") or os.path.join(LIB_DIR, "libqmha.so")
 
-VARIANTS = {"fa": 0, "fa_tc_v1a": 1, "fa_tc_int8_b": 2, "unfused": 3, "fa_mfma": 4, "fa_tc_int8_pt": 5}
+VARIANTS = {"fa": 0, "fa_tc_v1a": 1, "fa_tc_int8_b": 2, "unfused": 3, "fa_mfma": 4, "fa_tc_int8_pt": 5,
+            "fa_tc_fp8": 6}  # fa_tc_fp8: an e4m3 K/V cache only (KVCache, GroupedKVCache, PagedKVCache)
 DEFAULT_KERNEL = "fa_tc_int8_b"
 QMHA_OK = 0
 QMHA_FLAG_CAUSAL = 1  # qmha_solve_opts: query row r attends keys j <= r
@@ -42,6 +43,8 @@ SIGNATURES = {
     "qmha_kv_cache_tail_bytes": (_sz, [_vp]),
     "qmha_kv_cache_attach_tail": (_i, [_vp, _vp, _sz]),
     "qmha_kv_cache_append_tokens": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    # an fp8 cache's three host scales
+    "qmha_kv_cache_set_scales": (_i, [_vp, ctypes.c_float, ctypes.c_float, ctypes.c_float]),
     "qmha_attend_cached_tokens": (_i, [_vp, _vp, _vp, _i, _vp, ctypes.c_uint, _vp]),
     # paged caches: a pool of pages, and a device int32[B][max_pages] block table beside pos / lens
     "qmha_kv_cache_paged_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),

@@ -54,6 +54,8 @@ struct VariantRow {
     // built head sizes of the masked templates (qmha_fa_masked.hip): causal, rectangular and grouped-query calls and
     // the K/V cache are all instances of them and so are built together
     unsigned masked;
+    // a K/V cache variant: the head sizes its cache is built for; it has no solve entry point and no scratch
+    unsigned cache = 0;
 };
 constexpr VariantRow kVariants[] = {
     {QMHA_FA, "fa", nullptr, kEveryD, 0},
@@ -63,6 +65,7 @@ constexpr VariantRow kVariants[] = {
     {QMHA_UNFUSED, "unfused", qmha::unfused_workspace_bytes, kEveryD, 0},
     {QMHA_FA_MFMA, "fa_mfma", nullptr, kEveryD, 0},
     {QMHA_FA_TC_INT8_PT, "fa_tc_int8_pt", qmha::int8_pt_workspace_bytes, kTunedD, 0},  // no reference counterpart
+    {QMHA_FA_TC_FP8, "fa_tc_fp8", nullptr, 0, 0, d_mask(64, 128)},                      // e4m3 K/V cache only
 };
 
 const VariantRow* find_variant(int id) {
@@ -101,7 +104,7 @@ int check_shape(const void* Q, const void* K, const void* V, const void* O, int 
     if (D % 32 != 0) return fail(QMHA_ERR_INVALID, "head size d = d_model/h must be a multiple of 32");
     // the reference has no upper bound; here the int8 magic-biased accumulator's range
     if (D > 256) return fail(QMHA_ERR_NOSYS, "head size d = d_model/h above 256 is not built");
-    if (!built(v->plain, D))
+    if (!v->cache && !built(v->plain, D))  // a cache variant's head sizes: not_built
         return fail(QMHA_ERR_NOSYS, std::string(v->name) + " is built for d = " + d_list(v->plain) + " only");
     if ((size_t)B * N * d_model > (size_t)INT32_MAX * 4) return fail(QMHA_ERR_INVALID, "tensor too large");
     *D_out = D;
@@ -116,6 +119,11 @@ int check_flag_bits(unsigned flags) {
 
 // "<feature> is not built for variant X at d = D (<who has it>)" unless the table's `masked` column has D
 int not_built(const char* feature, int variant, int D) {
+    if (const VariantRow* v = find_variant(variant); v->cache) {
+        if (built(v->cache, D)) return QMHA_OK;
+        return fail(QMHA_ERR_NOSYS, std::string(feature) + " is not built for variant " + v->name + " at d = " + std::to_string(D) + " (" +
+                                        v->name + ": d = " + d_list(v->cache) + ")");
+    }
     if (built(find_variant(variant)->masked, D)) return QMHA_OK;
     std::string have;
     for (const VariantRow& r : kVariants)
@@ -149,6 +157,9 @@ struct Call {
 // Every check of a call but its workspace's size, run once and before any HIP call.  The order decides which
 // error a call that is wrong in several ways reports (tests/test_hostpath_cpu.py).
 int check_call(const Call& c, int* D) {
+    if (const VariantRow* v = find_variant(c.variant); v && v->cache)
+        return fail(QMHA_ERR_NOSYS, std::string(v->name) + " is a K/V cache variant (qmha_kv_cache_create, d = " + d_list(v->cache) +
+                                        "): it has no solve entry point");
     int st = check_shape(c.Q, c.K, c.V, c.O, c.B, c.Nq, c.d_model, c.h, c.variant, D, c.square ? "N" : "Nq");
     if (st == QMHA_OK) st = check_shape(c.Q, c.K, c.V, c.O, c.B, c.Nk, c.d_model, c.h, c.variant, D, c.square ? "N" : "Nk");
     if (st == QMHA_OK) st = check_kv_heads(c.h, c.h_kv);
@@ -528,6 +539,7 @@ struct qmha_kv_cache {
     int len;   // valid rows of every head slice
     // the raw rows of each sequence's open group (qmha_kv_cache_attach_tail; int8 only), caller-owned like `mem`
     void* tail = nullptr;
+    float q_scale = 1.0f, k_scale = 1.0f, v_scale = 1.0f;  // an fp8 cache's (qmha_kv_cache_set_scales), kernel arguments
     // a paged cache (qmha_kv_cache_create_paged): `mem` is a pool of num_pages pages of page_rows rows --
     // the variant's carve at B := num_pages, N := page_rows --, cap the logical capacity max_pages * page_rows of a
     // sequence, B the sequence slots (the tail's).  num_pages == 0: a contiguous cache.
@@ -542,6 +554,7 @@ namespace {
 template <class F>
 hipError_t with_carve(const qmha_kv_cache& c, F&& f) {
     const int slices = c.paged() ? c.num_pages : c.B, rows = c.paged() ? c.page_rows : c.cap;
+    if (c.variant == QMHA_FA_TC_FP8) return f(qmha::fp8_carve(c.mem, slices, rows, c.h_kv, c.D, c.q_scale, c.k_scale, c.v_scale));
     return c.variant == QMHA_FA_TC_INT8_B ? f(qmha::int8_carve(c.mem, slices, rows, c.h_kv, c.D))
                                           : f(qmha::f16_carve(c.mem, slices, rows, c.h_kv, c.D));
 }
@@ -562,6 +575,15 @@ int cache_enqueue(qmha_kv_cache* c, Marks ProfRec::*marks, void* stream, const c
     return st;
 }
 const auto kNoLenCheck = [](int) { return QMHA_OK; };
+
+// the bytes of a cache of `slices` slices (B * h_kv, or a pool's num_pages * h_kv) of `rows` rows.  For every variant with a
+// workspace this IS workspace_bytes (the size qmha_workspace_size reports: a cache is that carve at N = cap), and the two must
+// stay in step; only a cache-only variant, which has no workspace, brings a size of its own
+size_t cache_bytes(int slices, int rows, int H, int D, int variant) {
+    const VariantRow* v = find_variant(variant);
+    if (v && v->cache) return built(v->cache, D) ? qmha::fp8_cache_bytes(slices, rows, H, D) : 0;
+    return workspace_bytes(slices, rows, H, D, variant);
+}
 
 // the entry points of one kind of cache refuse the other kind
 int check_cache_kind(const qmha_kv_cache* c, bool paged_call, const char* what) {
@@ -617,6 +639,12 @@ struct CacheCall {
         return bad(std::string(name) + " = " + std::to_string(b) + ", needs 1 <= " + name + " <= min(total = " + std::to_string(total) + ", " +
                    cap() + ")");
     }
+    // the entry points an fp8 cache does not have, before any HIP call
+    int fp8_not_built(const char* feature) const {
+        if (c->variant != QMHA_FA_TC_FP8) return QMHA_OK;
+        return fail(QMHA_ERR_NOSYS, std::string(what) + ": " + feature + " is not built for a fa_tc_fp8 cache (built: append, append_at, "
+                                    "append_tokens, append_paged, attend, attend_varlen, attend_tokens, attend_paged)");
+    }
     // an append, under the mutex (attach_tail writes `tail` under it)
     int tail() const {
         if (c->variant == QMHA_FA_TC_INT8_B && !c->tail) return bad("an int8 cache needs its tail (qmha_kv_cache_attach_tail)");
@@ -648,6 +676,9 @@ int append_rows(const CacheCall& k, const float* K, const float* V, int n, const
 int attend_rows(const CacheCall& k, const float* Q, float* O, int Nq, const int32_t* lens, const int32_t* table, unsigned flags,
                 void* stream, const int* window = nullptr) {
     if (int st = k.operands(Q, O)) return st;
+    if (window) {
+        if (int st = k.fp8_not_built("a sliding window")) return st;
+    }
     if (int st = k.attend_words(lens, table, flags)) return st;
     if (int st = k.rows("Nq", Nq)) return st;
     if (window) {
@@ -721,7 +752,8 @@ size_t qmha_workspace_size(int B, int N, int d_model, int h, int variant) {
 
 // ---- persistent K/V cache: every check runs before any HIP call -------------------------------------
 size_t qmha_kv_cache_bytes(int B, int cap, int d_model, int h, int variant) {
-    return qmha_workspace_size(B, cap, d_model, h, variant);  // the variant's carve at N = cap
+    if (B < 1 || cap < 1 || h < 1 || d_model % h) return 0;
+    return cache_bytes(B, cap, h, d_model / h, variant);  // the variant's carve at N = cap
 }
 
 int qmha_kv_cache_create_gqa(qmha_kv_cache_t** out, void* mem, size_t bytes, int B, int cap, int d_model, int h, int h_kv,
@@ -735,7 +767,7 @@ int qmha_kv_cache_create_gqa(qmha_kv_cache_t** out, void* mem, size_t bytes, int
     if (st == QMHA_OK) st = not_built(h_kv < h ? kGroupedFeature : "the persistent K/V cache", variant, D);
     if (st != QMHA_OK) return st;
     if (reinterpret_cast<uintptr_t>(mem) % 256 != 0) return fail(QMHA_ERR_INVALID, "cache memory must be 256-byte aligned");
-    const size_t need = workspace_bytes(B, cap, h_kv, D, variant);
+    const size_t need = cache_bytes(B, cap, h_kv, D, variant);
     if (bytes < need)
         return fail(QMHA_ERR_INVALID, "cache memory too small: " + std::to_string(bytes) + " bytes, qmha_kv_cache_bytes is " +
                                           std::to_string(need));
@@ -872,6 +904,18 @@ int qmha_kv_cache_attach_tail(qmha_kv_cache_t* c, void* mem, size_t bytes) {
     return QMHA_OK;
 }
 
+int qmha_kv_cache_set_scales(qmha_kv_cache_t* c, float q_scale, float k_scale, float v_scale) {
+    if (!c) return fail(QMHA_ERR_INVALID, "null cache");
+    if (c->variant != QMHA_FA_TC_FP8)
+        return fail(QMHA_ERR_INVALID, std::string("set_scales: the cache is a ") + qmha_variant_name(c->variant) + " cache; only a fa_tc_fp8 cache has scales");
+    for (float s : {q_scale, k_scale, v_scale})
+        if (!(s > 0.0f) || !(s <= 3.402823466e38f))
+            return fail(QMHA_ERR_INVALID, "set_scales: q_scale, k_scale and v_scale must be finite and > 0");
+    std::lock_guard<std::mutex> lk(c->mu);  // host only: later enqueues carry the new values as kernel arguments
+    c->q_scale = q_scale, c->k_scale = k_scale, c->v_scale = v_scale;
+    return QMHA_OK;
+}
+
 int qmha_kv_cache_append_tokens(qmha_kv_cache_t* c, const float* K, const float* V, int n, const int32_t* pos, void* stream) {
     return append_rows({c, "append_tokens", false}, K, V, n, pos, nullptr, stream);
 }
@@ -884,7 +928,8 @@ int qmha_attend_cached_tokens(qmha_kv_cache_t* c, const float* Q, float* O, int 
 // ---- paged caches: a pool of pages and a block table read on the device --------------------
 size_t qmha_kv_cache_paged_bytes(int num_pages, int page_rows, int d_model, int h, int h_kv, int variant) {
     if (h < 1 || h_kv < 1 || d_model % h) return 0;
-    return qmha_workspace_size(num_pages, page_rows, h_kv * (d_model / h), h_kv, variant);  // the carve of num_pages slices of page_rows rows
+    if (num_pages < 1 || page_rows < 1) return 0;
+    return cache_bytes(num_pages, page_rows, h_kv, d_model / h, variant);  // the carve of num_pages slices of page_rows rows
 }
 
 int qmha_kv_cache_create_paged(qmha_kv_cache_t** out, void* mem, size_t bytes, int B, int num_pages, int page_rows, int max_pages,
@@ -905,7 +950,7 @@ int qmha_kv_cache_create_paged(qmha_kv_cache_t** out, void* mem, size_t bytes, i
     if (st == QMHA_OK) st = not_built(h_kv < h ? kGroupedFeature : "the persistent K/V cache", variant, D);
     if (st != QMHA_OK) return st;
     if (reinterpret_cast<uintptr_t>(mem) % 256 != 0) return fail(QMHA_ERR_INVALID, "cache memory must be 256-byte aligned");
-    const size_t need = workspace_bytes(num_pages, page_rows, h_kv, D, variant);
+    const size_t need = cache_bytes(num_pages, page_rows, h_kv, D, variant);
     if (bytes < need)
         return fail(QMHA_ERR_INVALID, "cache memory too small: " + std::to_string(bytes) + " bytes, qmha_kv_cache_paged_bytes is " +
                                           std::to_string(need));
@@ -953,6 +998,7 @@ int attend_split(qmha_kv_cache_t* c, const char* what, const float* Q, float* O,
                  bool paged, int chunk_rows, void* scratch, size_t scratch_bytes, unsigned flags, void* stream) {
     const CacheCall k{c, what, paged};
     if (int st = k.operands(Q, O)) return st;
+    if (int st = k.fp8_not_built("split-KV")) return st;
     if (int st = k.attend_words(lens, table, flags)) return st;
     if (int st = k.rows("Nq", Nq)) return st;
     if (!split_chunk_ok(c, chunk_rows))
@@ -993,6 +1039,7 @@ int append_packed(qmha_kv_cache_t* c, const char* what, const float* K, const fl
                   const int32_t* pos, const int32_t* table, bool paged, void* stream) {
     const CacheCall k{c, what, paged};
     if (int st = k.operands(K, V)) return st;
+    if (int st = k.fp8_not_built("a packed batch")) return st;
     if (int st = k.words(cu, "cu (a device int32[B + 1])")) return st;
     if (int st = k.words(pos, "pos (a device int32[B])")) return st;
     if (int st = k.table(table)) return st;
@@ -1009,6 +1056,7 @@ int attend_packed(qmha_kv_cache_t* c, const char* what, const float* Q, float* O
                   const int32_t* lens, const int32_t* table, bool paged, unsigned flags, void* stream) {
     const CacheCall k{c, what, paged};
     if (int st = k.operands(Q, O)) return st;
+    if (int st = k.fp8_not_built("a packed batch")) return st;
     if (int st = k.words(cu, "cu (a device int32[B + 1])")) return st;
     if (int st = k.attend_words(lens, table, flags)) return st;
     if (int st = k.bound("max_nq", total, max_nq)) return st;

@@ -299,6 +299,57 @@ template <class W>
 hipError_t launch_kv_packed(const float* K, const float* V, const W& w, float* tail, int B, int rows, int max_n, int cap, const int32_t* cu,
                             const int32_t* pos, int H, int D, int d_model, hipStream_t stream, const PageTable& pt = {});
 
+// ---- FP8 (fa_tc_fp8; qmha_fa_fp8.hip, qmha_kv_fp8.hip): a K/V cache variant only ----------------
+// The cache of B * H slices of N rows: K8 e4m3 rows [slice][N][D]; Vt8 per 32-row group a [D * 32]-byte block in the
+// operand order of the P@V MFMA (fp8_vt_offset).  The three scales are host floats that travel as kernel arguments.
+struct Fp8Workspace {
+    uint8_t* K8;
+    uint8_t* Vt8;
+    float q_scale, k_scale, v_scale;
+    size_t bytes;  // of the whole layout (set by the carve)
+};
+inline Fp8Workspace fp8_carve(void* ws, int B, int N, int H, int D, float q_scale = 1.0f, float k_scale = 1.0f, float v_scale = 1.0f) {
+    const size_t e = align_up((size_t)B * H * N * D, 256);
+    Carver c{static_cast<char*>(ws)};
+    Fp8Workspace w{};
+    w.K8 = c.take<uint8_t>(e);
+    w.Vt8 = c.take<uint8_t>(e);
+    w.q_scale = q_scale, w.k_scale = k_scale, w.v_scale = v_scale;
+    w.bytes = c.used;
+    return w;
+}
+inline size_t fp8_cache_bytes(int B, int N, int H, int D) { return fp8_carve(nullptr, B, N, H, D).bytes; }
+// Byte (d, kv) of a group's V^T block.  Both products run on v_mfma_f32_16x16x32_fp8_fp8, whose lane 16 grp + r16 holds
+// eight bytes: row r16, k = 8 grp .. +7.  Key kv sits in slot 8 grp + j = slot_of_kv_f16(kv), as in the f16 block; the
+// block is D / 2 lines of 64 bytes, line 16 mp + r16 holding for each grp a 16-byte chunk with the eight slots of V^T row
+// d = 16 (2 mp) + r16 and then those of row d + 16, so one ds_read_b128 gives a lane the operands of two d-blocks.
+__host__ __device__ constexpr int fp8_vt_offset(int d, int kv) {
+    const int slot = 16 * (kv >> 4) + 8 * ((kv >> 2) & 1) + (kv & 3) + 4 * ((kv >> 3) & 1);  // slot_of_kv_f16
+    return ((d >> 5) * 16 + (d & 15)) * 64 + (slot >> 3) * 16 + ((d >> 4) & 1) * 8 + (slot & 7);
+}
+template <class F>
+hipError_t fp8_cache_d(int D, F&& f) {
+    switch (D) {
+        case 64: return f(std::integral_constant<int, 64>{});
+        case 128: return f(std::integral_constant<int, 128>{});
+        default: return hipErrorInvalidValue;
+    }
+}
+// The attends of an fp8 cache: the cache modes of launch_fa_masked above (a host len, per-sequence lengths, token-granular
+// lengths, a paged pool), multi-head and grouped; a call of its own (len < 0, lens null) is hipErrorInvalidValue.
+hipError_t launch_fa_masked(const Fp8Workspace& w, const float* Qf, float* O, const MaskedCall& c, hipStream_t stream);
+// The appends, as launch_kv_append / launch_kv_tokens below; there is no tail (a row converts on its own)
+hipError_t launch_kv_append(const float* K, const float* V, const Fp8Workspace& w, int B, int n, int cap, int len, const int32_t* pos, int H,
+                            int D, int d_model, hipStream_t stream);
+hipError_t launch_kv_tokens(const float* K, const float* V, const Fp8Workspace& w, float* tail, int B, int n, int cap, const int32_t* pos,
+                            int H, int D, int d_model, hipStream_t stream, const PageTable& pt = {});
+// Not built on an fp8 cache (the C-ABI refuses these calls before it gets here): split-KV, windows, packed batches
+inline hipError_t launch_fa_split(const Fp8Workspace&, const float*, float*, const MaskedCall&, int, void*, hipStream_t) { return hipErrorNotSupported; }
+inline hipError_t launch_fa_window(const Fp8Workspace&, const float*, float*, const MaskedCall&, int, hipStream_t) { return hipErrorNotSupported; }
+inline hipError_t launch_fa_packed(const Fp8Workspace&, const float*, float*, const MaskedCall&, const int32_t*, int, hipStream_t) { return hipErrorNotSupported; }
+inline hipError_t launch_kv_packed(const float*, const float*, const Fp8Workspace&, float*, int, int, int, int, const int32_t*, const int32_t*, int, int,
+                                   int, hipStream_t, const PageTable& = {}) { return hipErrorNotSupported; }
+
 // ---- FP32 (fa: scalar VALU kernel; fa_mfma: the same contract on v_mfma_f32_32x32x2_f32) -----
 hipError_t launch_fa_f32(const float* Q, const float* K, const float* V, float* O, int B, int N, int H, int D,
                          int d_model, bool mfma, hipStream_t stream);

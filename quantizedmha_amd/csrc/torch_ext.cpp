@@ -297,6 +297,12 @@ public:
         TORCH_CHECK(st == QMHA_OK, "KVCache.truncate: ", qmha_status_string(st), ": ", qmha_last_error());
     }
 
+    // the three host scales of an fp8 cache (qmha_kv_cache_set_scales); host only
+    void set_scales(double q_scale, double k_scale, double v_scale) {
+        const int st = qmha_kv_cache_set_scales(handle_, static_cast<float>(q_scale), static_cast<float>(k_scale), static_cast<float>(v_scale));
+        TORCH_CHECK(st == QMHA_OK, "KVCache.set_scales", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+    }
+
     // append with a row per sequence (qmha_kv_cache_append_at): pos is int32 [B] on the device, read by the kernel
     void append_at(const Tensor& K, const Tensor& V, const Tensor& pos) {
         auto Kc = rows(K, "K", kv_model_), Vc = rows(V, "V", kv_model_);
@@ -322,7 +328,7 @@ public:
 
     // allocate and attach the tail of raw rows append_tokens needs (qmha_kv_cache_attach_tail); once, outside a capture
     void enable_tokens() {
-        if (tail_.defined()) return;
+        if (tail_.defined() || kernel_ == "fa_tc_fp8") return;  // an fp8 cache has no tail: nothing is allocated
         const size_t bytes = qmha_kv_cache_tail_bytes(handle_);
         tail_ = torch::zeros({static_cast<int64_t>(bytes > 0 ? bytes : 1)}, torch::TensorOptions().dtype(torch::kUInt8).device(mem_.device()));
         const int st = qmha_kv_cache_attach_tail(handle_, tail_.data_ptr(), bytes);
@@ -462,9 +468,15 @@ public:
     Tensor mem() const { return mem_; }
     std::optional<Tensor> tail() const { return tail_.defined() ? std::optional<Tensor>(tail_) : std::nullopt; }
 
+    // the three host scales of an fp8 cache (qmha_kv_cache_set_scales); host only
+    void set_scales(double q_scale, double k_scale, double v_scale) {
+        const int st = qmha_kv_cache_set_scales(handle_, static_cast<float>(q_scale), static_cast<float>(k_scale), static_cast<float>(v_scale));
+        TORCH_CHECK(st == QMHA_OK, "PagedKVCache.set_scales", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+    }
+
     // allocate and attach the tail of raw rows append_paged needs (int8); once, outside a capture
     void enable_tokens() {
-        if (tail_.defined()) return;
+        if (tail_.defined() || kernel_ == "fa_tc_fp8") return;  // an fp8 cache has no tail: nothing is allocated
         const size_t bytes = qmha_kv_cache_tail_bytes(handle_);
         tail_ = torch::zeros({static_cast<int64_t>(bytes > 0 ? bytes : 1)}, torch::TensorOptions().dtype(torch::kUInt8).device(mem_.device()));
         const int st = qmha_kv_cache_attach_tail(handle_, tail_.data_ptr(), bytes);
@@ -590,6 +602,8 @@ PYBIND11_MODULE(torch_ext, m) {
              pybind11::arg("B"), pybind11::arg("num_pages"), pybind11::arg("page_rows"), pybind11::arg("max_pages"), pybind11::arg("d_model"),
              pybind11::arg("num_heads"), pybind11::arg("num_kv_heads") = pybind11::none(), pybind11::arg("kernel") = "fa_tc_int8_b",
              pybind11::arg("device") = "cuda")
+        .def("set_scales", &PagedKVCache::set_scales, pybind11::arg("q_scale") = 1.0, pybind11::arg("k_scale") = 1.0, pybind11::arg("v_scale") = 1.0,
+             "the three host scales of a kernel='fa_tc_fp8' cache; host only, nothing is enqueued.")
         .def("enable_tokens", &PagedKVCache::enable_tokens,
              "allocate and attach the tail of raw rows append_paged needs (int8); once, outside a graph capture.")
         .def("append_paged", &PagedKVCache::append_paged, pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("pos"),
@@ -631,6 +645,8 @@ PYBIND11_MODULE(torch_ext, m) {
         .def("append", &KVCache::append, pybind11::arg("K"), pybind11::arg("V"))
         .def("attend", &KVCache::attend, pybind11::arg("Q"), pybind11::arg("causal") = true)
         .def("truncate", &KVCache::truncate, pybind11::arg("n"))
+        .def("set_scales", &KVCache::set_scales, pybind11::arg("q_scale") = 1.0, pybind11::arg("k_scale") = 1.0, pybind11::arg("v_scale") = 1.0,
+             "the three host scales of a kernel='fa_tc_fp8' cache; host only, nothing is enqueued.")
         .def("append_at", &KVCache::append_at, pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("pos"),
              "append with a row per sequence: sequence b's rows go to cache rows [pos[b], pos[b] + n); pos: int32 [B] on the\n"
              "device, read by the kernel; an invalid pos[b] writes nothing for that sequence.")

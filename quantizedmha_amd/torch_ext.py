@@ -163,7 +163,7 @@ class KVCache:
     """A persistent quantised K/V cache (qmha_kv_cache_*; additive, no reference counterpart): chunked prefill and
     decode without re-running the K/V pre-pass over rows an earlier call already quantised / converted.
 
-        cache = KVCache(B, cap, d_model, num_heads)          # fa_tc_int8_b (d = 32 / 64 / 128) or fa_tc_v1a (64 / 128)
+        cache = KVCache(B, cap, d_model, num_heads)          # fa_tc_int8_b (d = 32 / 64 / 128), fa_tc_v1a or fa_tc_fp8 (64 / 128)
         cache.append(K_chunk, V_chunk)                       # [B, n, d_model] (or [n, d_model] for B = 1), n % 32 == 0
         O = cache.attend(Q_chunk)                            # row r attends cache rows j <= r + (len - Nq)
 
@@ -219,7 +219,7 @@ class KVCache:
         self._handle = handle
 
     def __del__(self):
-        if getattr(self, "_handle", None):
+        if getattr(self, "_handle", None) and getattr(_lib, "load", None):  # at interpreter exit the module may be gone already
             _lib.load().qmha_kv_cache_destroy(self._handle)
             self._handle = None
 
@@ -262,6 +262,13 @@ class KVCache:
 
     def truncate(self, n: int) -> None:
         _lib.check(_lib.load().qmha_kv_cache_truncate(self._handle, int(n)), "KVCache.truncate")
+
+    def set_scales(self, q_scale: float = 1.0, k_scale: float = 1.0, v_scale: float = 1.0) -> None:
+        """The three host scales of a kernel="fa_tc_fp8" cache (qmha_kv_cache_set_scales): a cached element is
+        e4m3(clamp(x / scale, -448, 448)), Q converts with q_scale.  Host only, nothing is enqueued: rows appended before
+        keep their bytes.  Any other cache, or a scale that is not finite and > 0, raises."""
+        st = _lib.load().qmha_kv_cache_set_scales(self._handle, float(q_scale), float(k_scale), float(v_scale))
+        _lib.check(st, f"{type(self).__name__}.set_scales({self.kernel})")
 
     def _per_seq(self, t: torch.Tensor, name: str) -> torch.Tensor:
         """A per-sequence int32 [B] tensor on the cache's device, read by the kernel when it runs (not by the host)."""
@@ -309,7 +316,7 @@ class KVCache:
         """Allocate and attach the tail append_tokens needs (qmha_kv_cache_attach_tail): the raw rows of each sequence's
         open 32-row group, `.tail` (int8; an fp16 cache needs none).  Once, and outside a graph capture: append_tokens
         and attend_tokens themselves allocate nothing."""
-        if self.tail is not None:
+        if self.tail is not None or self.kernel == "fa_tc_fp8":  # an fp8 cache has no tail: nothing is allocated
             return
         lib = _lib.load()
         nbytes = lib.qmha_kv_cache_tail_bytes(self._handle)
@@ -531,6 +538,7 @@ class PagedKVCache:
     _rows = KVCache._rows
     _per_seq = KVCache._per_seq
     enable_tokens = KVCache.enable_tokens
+    set_scales = KVCache.set_scales
     enable_split = KVCache.enable_split
     _split_ready = KVCache._split_ready
     split_partials = KVCache.split_partials

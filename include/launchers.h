@@ -383,6 +383,39 @@ int qmha_attend_cached_paged_split(qmha_kv_cache_t *c, const float *Q, float *O,
                                    void *stream);
 
 /*
+ * The decode call of an fp8 cache -- attend_tokens / attend_paged on a fa_tc_fp8 cache for a decode step or a short
+ * speculative step, with a kernel of its own: the step's real query rows as MFMA columns, the key sweep in
+ * chunks over split-KV's scratch, split-KV's combine pass.  Device lens and table, causal only, the validity rules and the
+ * host checks are those of the split calls above; the split, packed and windowed entry points stay refused on an fp8 cache.
+ * A deterministic function of its own inside the fp8 accuracy contract; not attend_tokens' bits.
+ *
+ *   columns        G = h / h_kv.  Column c = g * Nq + r of K/V head kvh is query head kvh * G + g, row r; a call needs
+ *                  W = G * Nq <= 32 (two 16-column blocks), else QMHA_ERR_INVALID: attend_tokens is the call for longer
+ *                  query blocks.  Column (g, r) sees key j iff j <= lens[b] - Nq + r; Q converts as in attend_tokens.
+ *   chunk_rows     as above: a multiple of 64 in [64, cap], C = chunk_rows / 32, NC = ceil(cap / chunk_rows).
+ *   partial        first launch, a workgroup per (sequence, K/V head, chunk); chunks that start behind tile
+ *                  (lens[b] - 1) / 32, and invalid sequences, are left at once.  The chunk's even tiles are one stream and
+ *                  its odd tiles another; each runs attend_tokens' online softmax from the zero state over its tiles in
+ *                  ascending order (true running maximum m_i, p = exp2(s - m_i + 8) as e4m3 into P@V, l_i from the fp32 p,
+ *                  o_i the P@V sum).  The two merge in fp32: M = max(m0, m1), w_i = exp2(m_i - M) (0 for an empty stream),
+ *                  l = w0 l0 + w1 l1, Oc = l > 1e-10 ? v_scale * (w0 o0 + w1 o1) / l : 0, m = M.  Row r writes chunk c iff
+ *                  c <= ((lens[b] - Nq + r) / 32) / C -- the chunks the combine reads of it.
+ *   combine        the split calls' second launch as it is, thr = 1e-10.  An invalid sequence: Nq rows of positive zeros,
+ *                  its scratch untouched.
+ *   scratch        the split calls' layout and rules; qmha_attend_decode_bytes(c, Nq, chunk_rows) bytes (0 on invalid
+ *                  arguments, W > 32 and a cache of another variant among them).
+ *
+ * A cache that is not fa_tc_fp8: QMHA_ERR_NOSYS (use the split calls).  One qmha_profile main pair covers both launches;
+ * no allocation, no synchronisation, no atomics, no waiting between workgroups: capturable.
+ */
+size_t qmha_attend_decode_bytes(const qmha_kv_cache_t *c, int Nq, int chunk_rows);
+int qmha_attend_cached_decode(qmha_kv_cache_t *c, const float *Q, float *O, int Nq, const int32_t *lens, int chunk_rows,
+                              void *scratch, size_t scratch_bytes, unsigned flags, void *stream);
+int qmha_attend_cached_paged_decode(qmha_kv_cache_t *c, const float *Q, float *O, int Nq, const int32_t *lens,
+                                    const int32_t *table, int chunk_rows, void *scratch, size_t scratch_bytes, unsigned flags,
+                                    void *stream);
+
+/*
  * Packed batches -- a query count and an append count per sequence in one call, for a continuous-batching step that
  * mixes chunked prefill and decode.  The operands have no batch axis, in the cu_seqlens convention of varlen attention:
  *

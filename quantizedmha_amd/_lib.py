@@ -55,6 +55,10 @@ SIGNATURES = {
     "qmha_attend_split_bytes": (_sz, [_vp, _i, _i]),
     "qmha_attend_cached_tokens_split": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _sz, ctypes.c_uint, _vp]),
     "qmha_attend_cached_paged_split": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _sz, ctypes.c_uint, _vp]),
+    # an fp8 cache's decode call: the step's query rows as MFMA columns, the key sweep in chunks, over the caller's scratch
+    "qmha_attend_decode_bytes": (_sz, [_vp, _i, _i]),
+    "qmha_attend_cached_decode": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _sz, ctypes.c_uint, _vp]),
+    "qmha_attend_cached_paged_decode": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _sz, ctypes.c_uint, _vp]),
     # a sliding window: the two attends over the last `window` keys of a row (a host int, a multiple of 32)
     "qmha_attend_cached_tokens_window": (_i, [_vp, _vp, _vp, _i, _vp, _i, ctypes.c_uint, _vp]),
     "qmha_attend_cached_paged_window": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, ctypes.c_uint, _vp]),

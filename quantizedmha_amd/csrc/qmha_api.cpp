@@ -1031,6 +1031,60 @@ int qmha_attend_cached_paged_split(qmha_kv_cache_t* c, const float* Q, float* O,
     return attend_split(c, "attend_paged_split", Q, O, Nq, lens, table, true, chunk_rows, scratch, scratch_bytes, flags, stream);
 }
 
+// ---- the decode call of an fp8 cache: the step's G * Nq real query rows as MFMA columns, the key sweep in
+// chunks over split-KV's scratch, the same combine pass -----------
+namespace {
+
+constexpr int kDecodeColumns = 32;  // two 16-column MFMA blocks
+
+// both entry points: `table` null is the contiguous one.  The checks of attend_split, and the column limit
+int attend_decode(qmha_kv_cache_t* c, const char* what, const float* Q, float* O, int Nq, const int32_t* lens, const int32_t* table,
+                  bool paged, int chunk_rows, void* scratch, size_t scratch_bytes, unsigned flags, void* stream) {
+    const CacheCall k{c, what, paged};
+    if (int st = k.operands(Q, O)) return st;
+    if (c->variant != QMHA_FA_TC_FP8)
+        return fail(QMHA_ERR_NOSYS, std::string(what) + ": the decode call is built for a fa_tc_fp8 cache only; this cache is " +
+                                        qmha_variant_name(c->variant) + ": use attend_tokens_split / attend_paged_split");
+    if (int st = k.attend_words(lens, table, flags)) return st;
+    if (int st = k.rows("Nq", Nq)) return st;
+    const int G = c->h / c->h_kv;
+    if ((long long)Nq * G > kDecodeColumns)
+        return k.bad("Nq * (h / h_kv) = " + std::to_string(Nq) + " * " + std::to_string(G) + " = " + std::to_string((long long)Nq * G) +
+                     " query rows per K/V head, the limit is " + std::to_string(kDecodeColumns) +
+                     " (two 16-column MFMA blocks): use attend_tokens for longer query blocks");
+    if (!split_chunk_ok(c, chunk_rows))
+        return k.bad("chunk_rows = " + std::to_string(chunk_rows) + " must be a multiple of 64 with 64 <= chunk_rows <= cap = " +
+                     std::to_string(c->cap) + " (a chunk is a whole number of two-tile stages)");
+    if (!scratch) return k.bad("null scratch (qmha_attend_decode_bytes bytes of device memory)");
+    if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return k.bad("scratch must be 256-byte aligned");
+    const size_t need = split_bytes(c, Nq, chunk_rows);
+    if (scratch_bytes < need)
+        return k.bad("scratch too small: " + std::to_string(scratch_bytes) + " bytes, qmha_attend_decode_bytes is " + std::to_string(need));
+    return cache_enqueue(c, &ProfRec::main, stream, k.label().c_str(), kNoLenCheck, [&](const auto& ws, int) {  // one pair around both launches
+        if constexpr (std::is_same<std::decay_t<decltype(ws)>, qmha::Fp8Workspace>::value)
+            return qmha::launch_fp8_decode(ws, Q, O, k.attend(Nq, lens, table), chunk_rows, scratch, (hipStream_t)stream);
+        else
+            return hipErrorNotSupported;  // refused above
+    });
+}
+
+}  // namespace
+
+size_t qmha_attend_decode_bytes(const qmha_kv_cache_t* c, int Nq, int chunk_rows) {
+    if (!c || c->variant != QMHA_FA_TC_FP8 || Nq < 1 || (long long)Nq * (c->h / c->h_kv) > kDecodeColumns || !split_chunk_ok(c, chunk_rows)) return 0;
+    return split_bytes(c, Nq, chunk_rows);
+}
+
+int qmha_attend_cached_decode(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, const int32_t* lens, int chunk_rows, void* scratch,
+                              size_t scratch_bytes, unsigned flags, void* stream) {
+    return attend_decode(c, "attend_decode", Q, O, Nq, lens, nullptr, false, chunk_rows, scratch, scratch_bytes, flags, stream);
+}
+
+int qmha_attend_cached_paged_decode(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, const int32_t* lens, const int32_t* table,
+                                    int chunk_rows, void* scratch, size_t scratch_bytes, unsigned flags, void* stream) {
+    return attend_decode(c, "attend_paged_decode", Q, O, Nq, lens, table, true, chunk_rows, scratch, scratch_bytes, flags, stream);
+}
+
 // ---- packed batches: a query / append count per sequence from a device cu[B + 1], no batch axis -----------
 namespace {
 

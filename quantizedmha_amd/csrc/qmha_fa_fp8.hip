@@ -27,25 +27,11 @@
 //     and m = max(m, row maximum), alpha = exp2(m_old - m) rescales l and o (1 exactly for a row that did not move).  So m
 //     is the true running maximum after every tile, with no cross-lane traffic on a tile that leaves it alone.
 #include "qmha_fa_masked.hpp"
+#include "qmha_fp8.hpp"
 
 #include <utility>
 
 namespace qmha {
-
-typedef long fp8x8;  // eight e4m3 bytes: one MFMA operand
-typedef long v2l __attribute__((ext_vector_type(2)));  // a ds_read_b128: two operands
-
-// eight floats, already scaled and clamped, as one operand (RNE; two values per v_cvt_pk_fp8_f32)
-__device__ __forceinline__ fp8x8 fp8_pack8(const float (&x)[8]) {
-    int lo = 0, hi = 0;
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(x[0], x[1], lo, false);
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(x[2], x[3], lo, true);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(x[4], x[5], hi, false);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(x[6], x[7], hi, true);
-    return (fp8x8)(((unsigned long)(unsigned)hi << 32) | (unsigned)lo);
-}
-// the contract's element: clamp in fp32 ahead of the convert, so its overflow behaviour is never asked for
-__device__ __forceinline__ float fp8_prep(float x, float scale) { return fminf(fmaxf(x / scale, -448.0f), 448.0f); }
 
 template <class Geo, int D>
 __global__ __launch_bounds__(kWaves * 64, D > 64 ? 2 : 4) void qmha_fa_fp8_kernel(

@@ -207,6 +207,12 @@ struct Split : Geo {
     __device__ int first() const { return c * C; }
     __device__ int end() const { return c * C + C - 1; }
 };
+// The combine pass of a chunked sweep (qmha_split_combine_kernel, qmha_fa_split.hip), for the callers that fill the
+// scratch: the split kernels there and the fp8 decode call (qmha_fp8_decode.hip).  sg: the call's chunks over as_paged
+// of its geometry -- Split<Paged> for both kinds of cache, a null table for a contiguous one.
+hipError_t launch_split_combine(float* O, const Split<Paged>& sg, const MaskedCall& c, float thr, hipStream_t stream);
+inline Paged as_paged(const Ragged& r) { return Paged(r, nullptr, 2 * QMHA_GROUP, 1, 1); }  // the combine's argument: no table
+inline Paged as_paged(const Paged& p) { return p; }
 template <class T>
 struct IsSplit : std::false_type {};
 template <class Geo>

@@ -93,13 +93,11 @@ __global__ __launch_bounds__(256) void qmha_split_combine_kernel(float* __restri
     *reinterpret_cast<v4f*>(o) = out;
 }
 
-static hipError_t launch_split_combine(float* O, const Split<Paged>& sg, const MaskedCall& c, float thr, hipStream_t stream) {
+hipError_t launch_split_combine(float* O, const Split<Paged>& sg, const MaskedCall& c, float thr, hipStream_t stream) {
     const dim3 grid((unsigned)(((size_t)c.Nq * c.d_model / 4 + 255) / 256 * c.B)), block(256);  // split_shape_ok: it fits
     hipLaunchKernelGGL(qmha_split_combine_kernel, grid, block, 0, stream, O, sg, c.lens, c.H, c.D, thr);
     return hipGetLastError();
 }
-static Paged as_paged(const Ragged& r) { return Paged(r, nullptr, 2 * QMHA_GROUP, 1, 1); }  // the combine's argument: no table
-static Paged as_paged(const Paged& p) { return p; }
 
 // The chunks of a call, checked: chunk_rows a multiple of 64 in [64, Nk]; the grid fits
 static bool split_shape_ok(const MaskedCall& c, int chunk_rows, long long wgs_per_chunk) {

@@ -343,6 +343,12 @@ hipError_t launch_kv_append(const float* K, const float* V, const Fp8Workspace& 
                             int D, int d_model, hipStream_t stream);
 hipError_t launch_kv_tokens(const float* K, const float* V, const Fp8Workspace& w, float* tail, int B, int n, int cap, const int32_t* pos,
                             int H, int D, int d_model, hipStream_t stream, const PageTable& pt = {});
+// The decode call (qmha_fp8_decode.hip).  c: a token-granular call (ragged, with lens; a table: paged) with
+// W = Nq * (H / Hkv) <= 32.  Two launches on `stream`: a workgroup per (sequence, K/V head, chunk of chunk_rows key rows) packs
+// the W real query rows into MFMA columns and fills `scratch` (split_carve(..).bytes bytes, 256-byte aligned) with the chunk's
+// partials; qmha_split_combine_kernel writes O.  chunk_rows: a multiple of 64 in [64, Nk].
+hipError_t launch_fp8_decode(const Fp8Workspace& w, const float* Qf, float* O, const MaskedCall& c, int chunk_rows, void* scratch,
+                             hipStream_t stream);
 // Not built on an fp8 cache (the C-ABI refuses these calls before it gets here): split-KV, windows, packed batches
 inline hipError_t launch_fa_split(const Fp8Workspace&, const float*, float*, const MaskedCall&, int, void*, hipStream_t) { return hipErrorNotSupported; }
 inline hipError_t launch_fa_window(const Fp8Workspace&, const float*, float*, const MaskedCall&, int, hipStream_t) { return hipErrorNotSupported; }

@@ -237,6 +237,35 @@ struct SplitState {
     std::optional<Tensor> tensor() const { return scratch.defined() ? std::optional<Tensor>(scratch) : std::nullopt; }
 };
 
+// The scratch of an fp8 cache's decode call (enable_decode): what both cache classes keep for attend_decode /
+// attend_paged_decode.  `table` null is the contiguous call.
+struct DecodeState {
+    int64_t chunk_rows = 0, max_nq = 0;
+    Tensor scratch;
+
+    void enable(qmha_kv_cache_t* handle, int64_t chunk, int64_t nq, int64_t cap, const std::string& kernel, const c10::Device& device) {
+        const size_t bytes = qmha_attend_decode_bytes(handle, static_cast<int>(nq), static_cast<int>(chunk));
+        TORCH_CHECK(bytes > 0, "enable_decode: needs a fa_tc_fp8 cache (this one is ", kernel, "; other caches have enable_split / ",
+                    "attend_tokens_split), chunk_rows = ", chunk, " a multiple of 64 with 64 <= chunk_rows <= cap = ", cap,
+                    ", and 1 <= max_nq = ", nq, " with max_nq * (num_heads / num_kv_heads) <= 32");
+        chunk_rows = chunk, max_nq = nq;
+        scratch = torch::zeros({static_cast<int64_t>(bytes)}, torch::TensorOptions().dtype(torch::kUInt8).device(device));
+    }
+    int attend(qmha_kv_cache_t* handle, const char* what, const Tensor& Qc, Tensor& out, const Tensor& lens, const int32_t* table,
+               void* stream) const {
+        TORCH_CHECK(scratch.defined(), what, ": call enable_decode(chunk_rows) first");
+        TORCH_CHECK(Qc.size(1) <= max_nq, what, ": Nq = ", Qc.size(1), " rows exceed enable_decode's max_nq = ", max_nq);
+        const int Nq = static_cast<int>(Qc.size(1)), chunk = static_cast<int>(chunk_rows);
+        const size_t bytes = static_cast<size_t>(scratch.numel());
+        if (!table)
+            return qmha_attend_cached_decode(handle, Qc.data_ptr<float>(), out.data_ptr<float>(), Nq, lens.data_ptr<int32_t>(), chunk,
+                                             scratch.data_ptr(), bytes, QMHA_FLAG_CAUSAL, stream);
+        return qmha_attend_cached_paged_decode(handle, Qc.data_ptr<float>(), out.data_ptr<float>(), Nq, lens.data_ptr<int32_t>(), table, chunk,
+                                               scratch.data_ptr(), bytes, QMHA_FLAG_CAUSAL, stream);
+    }
+    std::optional<Tensor> tensor() const { return scratch.defined() ? std::optional<Tensor>(scratch) : std::nullopt; }
+};
+
 // A persistent quantised K/V cache (qmha_kv_cache_*): the compiled form of quantizedmha_amd/torch_ext.py's KVCache.
 // Owns a uint8 tensor of qmha_kv_cache_bytes and the host handle; append / attend run on PyTorch's current stream.
 class KVCache {
@@ -394,6 +423,19 @@ public:
         return out_opt ? out : out.view(Q.sizes());
     }
 
+    // an fp8 cache's decode call (qmha_attend_cached_decode): the scratch, once and outside a capture; then the attend
+    void enable_decode(int64_t chunk_rows, int64_t max_nq) { decode_.enable(handle_, chunk_rows, max_nq, cap_, kernel_, mem_.device()); }
+    std::optional<Tensor> decode_scratch() const { return decode_.tensor(); }
+    Tensor attend_decode(const Tensor& Q, const Tensor& lens, std::optional<Tensor> out_opt) {
+        auto Qc = rows(Q, "Q", d_model_);
+        per_seq(lens, "lens");
+        Tensor out = out_for(out_opt, Qc);
+        const OnStream on = current_stream(mem_.device());
+        const int st = decode_.attend(handle_, "attend_decode", Qc, out, lens, nullptr, on.stream);
+        TORCH_CHECK(st == QMHA_OK, "KVCache.attend_decode", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+        return out_opt ? out : out.view(Q.sizes());
+    }
+
     // append_tokens with a row count per sequence (qmha_kv_cache_append_packed): K, V [total, num_kv_heads * d], cu int32 [B + 1]
     void append_packed(const Tensor& K, const Tensor& V, const Tensor& cu, const Tensor& pos, int64_t max_n) {
         auto Kc = cache_packed_rows(K, "K", kv_model_, mem_.device()), Vc = cache_packed_rows(V, "V", kv_model_, mem_.device());
@@ -427,6 +469,7 @@ private:
     std::string kernel_;
     Tensor mem_, tail_;
     SplitState split_;
+    DecodeState decode_;
     qmha_kv_cache_t* handle_ = nullptr;
 };
 
@@ -546,6 +589,20 @@ public:
         return out_opt ? out : out.view(Q.sizes());
     }
 
+    // an fp8 cache's decode call through the block table (qmha_attend_cached_paged_decode); the scratch as KVCache's
+    void enable_decode(int64_t chunk_rows, int64_t max_nq) { decode_.enable(handle_, chunk_rows, max_nq, cap_, kernel_, mem_.device()); }
+    std::optional<Tensor> decode_scratch() const { return decode_.tensor(); }
+    Tensor attend_paged_decode(const Tensor& Q, const Tensor& lens, const Tensor& table, std::optional<Tensor> out_opt) {
+        auto Qc = cache_rows(Q, "Q", d_model_, B_, mem_.device());
+        cache_per_seq(lens, "lens", B_, mem_.device());
+        check_table(table);
+        Tensor out = out_for(out_opt, Qc);
+        const OnStream on = current_stream(mem_.device());
+        const int st = decode_.attend(handle_, "attend_paged_decode", Qc, out, lens, table.data_ptr<int32_t>(), on.stream);
+        TORCH_CHECK(st == QMHA_OK, "PagedKVCache.attend_paged_decode", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+        return out_opt ? out : out.view(Q.sizes());
+    }
+
     // append_packed through the block table (qmha_kv_cache_append_paged_packed)
     void append_paged_packed(const Tensor& K, const Tensor& V, const Tensor& cu, const Tensor& pos, const Tensor& table, int64_t max_n) {
         auto Kc = cache_packed_rows(K, "K", kv_model_, mem_.device()), Vc = cache_packed_rows(V, "V", kv_model_, mem_.device());
@@ -589,6 +646,7 @@ private:
     std::string kernel_;
     Tensor mem_, tail_;
     SplitState split_;
+    DecodeState decode_;
     qmha_kv_cache_t* handle_ = nullptr;
 };
 
@@ -632,6 +690,12 @@ PYBIND11_MODULE(torch_ext, m) {
              pybind11::arg("table"), pybind11::arg("max_nq"), pybind11::arg("out") = pybind11::none(),
              "attend_paged with a query count per sequence: Q [total, d_model], rows [cu[b], cu[b + 1]) are sequence b's;\n"
              "max_nq: an upper bound of the counts.")
+        .def("enable_decode", &PagedKVCache::enable_decode, pybind11::arg("chunk_rows"), pybind11::arg("max_nq") = 1,
+             "allocate the scratch of attend_paged_decode (a fa_tc_fp8 cache) for chunks of chunk_rows key rows (a multiple of 64)\n"
+             "and up to max_nq query rows, max_nq * (num_heads / num_kv_heads) <= 32; once, outside a graph capture.")
+        .def("attend_paged_decode", &PagedKVCache::attend_paged_decode, pybind11::arg("Q"), pybind11::arg("lens"), pybind11::arg("table"),
+             pybind11::arg("out") = pybind11::none(), "attend_decode through the table, bit for bit.")
+        .def_property_readonly("decode_scratch", &PagedKVCache::decode_scratch)
         .def_property_readonly("split_scratch", &PagedKVCache::split_scratch)
         .def_property_readonly("tail", &PagedKVCache::tail)
         .def_property_readonly("cap", &PagedKVCache::cap)
@@ -680,6 +744,13 @@ PYBIND11_MODULE(torch_ext, m) {
              pybind11::arg("max_nq"), pybind11::arg("out") = pybind11::none(),
              "attend_tokens with a query count per sequence: Q [total, d_model], rows [cu[b], cu[b + 1]) are sequence b's;\n"
              "max_nq: an upper bound of the counts.")
+        .def("enable_decode", &KVCache::enable_decode, pybind11::arg("chunk_rows"), pybind11::arg("max_nq") = 1,
+             "allocate the scratch of attend_decode (a fa_tc_fp8 cache) for chunks of chunk_rows key rows (a multiple of 64) and up\n"
+             "to max_nq query rows, max_nq * (num_heads / num_kv_heads) <= 32; once, outside a graph capture.")
+        .def("attend_decode", &KVCache::attend_decode, pybind11::arg("Q"), pybind11::arg("lens"), pybind11::arg("out") = pybind11::none(),
+             "attend_tokens of a fa_tc_fp8 cache for a decode or short speculative step: the step's query rows packed into MFMA\n"
+             "columns, the key sweep in chunks, split-KV's combine pass.")
+        .def_property_readonly("decode_scratch", &KVCache::decode_scratch)
         .def_property_readonly("split_scratch", &KVCache::split_scratch)
         .def_property_readonly("tail", &KVCache::tail)
         .def_property_readonly("len", &KVCache::len)

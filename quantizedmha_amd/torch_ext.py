@@ -202,6 +202,7 @@ class KVCache:
         self._handle = None
         self.tail = None  # enable_tokens()
         self.split_scratch = None  # enable_split()
+        self.decode_scratch = None  # enable_decode()
         if num_kv_heads is None:
             nbytes = lib.qmha_kv_cache_bytes(self.B, self.cap, self.d_model, self.num_heads, vid)
         else:  # the carve of num_kv_heads heads
@@ -417,6 +418,45 @@ class KVCache:
         _lib.check(st, f"KVCache.attend_tokens_split({self.kernel})")
         return out.view(Q.shape) if out.numel() == Q.numel() and out.dim() != Q.dim() else out
 
+    def enable_decode(self, chunk_rows: int, max_nq: int = 1) -> None:
+        """Allocate the scratch of an fp8 cache's decode call (qmha_attend_decode_bytes at Nq = max_nq), `.decode_scratch`,
+        for chunks of chunk_rows key rows: a multiple of 64 with 64 <= chunk_rows <= cap.  max_nq query rows per call need
+        max_nq * (num_heads / num_kv_heads) <= 32.  Once, and outside a graph capture: the call itself allocates nothing."""
+        chunk_rows, max_nq = int(chunk_rows), int(max_nq)
+        nbytes = _lib.load().qmha_attend_decode_bytes(self._handle, max_nq, chunk_rows)
+        if nbytes == 0:
+            raise RuntimeError(f"enable_decode: needs a fa_tc_fp8 cache (this one is {self.kernel}; other caches have enable_split / "
+                               f"attend_tokens_split), chunk_rows = {chunk_rows} a multiple of 64 with 64 <= chunk_rows <= cap = {self.cap}, "
+                               f"and 1 <= max_nq = {max_nq} with max_nq * (num_heads / num_kv_heads) <= 32")
+        self.decode_chunk_rows, self.decode_max_nq = chunk_rows, max_nq
+        self.decode_scratch = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+
+    def _decode(self, what: str, Q: torch.Tensor, lens: torch.Tensor, table: Optional[torch.Tensor], out: Optional[torch.Tensor]) -> torch.Tensor:
+        """Both decode calls: `table` None is the contiguous one."""
+        Qc = self._rows(Q, "Q")
+        lens = self._per_seq(lens, "lens")
+        if getattr(self, "decode_scratch", None) is None:
+            raise RuntimeError(f"{what}: call enable_decode(chunk_rows) first")
+        if Qc.shape[1] > self.decode_max_nq:
+            raise RuntimeError(f"{what}: Nq = {Qc.shape[1]} rows exceed enable_decode's max_nq = {self.decode_max_nq}")
+        out = _out_for(out, Qc, "size")
+        lib, tail = _lib.load(), (self.decode_chunk_rows, self.decode_scratch.data_ptr(), self.decode_scratch.numel(), _lib.QMHA_FLAG_CAUSAL)
+        with _current_stream(self.device) as stream:
+            if table is None:
+                st = lib.qmha_attend_cached_decode(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[1], lens.data_ptr(), *tail, stream)
+            else:
+                st = lib.qmha_attend_cached_paged_decode(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[1], lens.data_ptr(),
+                                                         table.data_ptr(), *tail, stream)
+        _lib.check(st, f"{type(self).__name__}.{what}({self.kernel})")
+        return out.view(Q.shape) if out.numel() == Q.numel() and out.dim() != Q.dim() else out
+
+    def attend_decode(self, Q: torch.Tensor, lens: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """attend_tokens of a fa_tc_fp8 cache for a decode step or a short speculative step (qmha_attend_cached_decode):
+        the Nq * (num_heads / num_kv_heads) <= 32 real query rows of a K/V head packed into MFMA columns, the key sweep in
+        chunks of enable_decode's chunk_rows, and split-KV's combine pass.  Same arguments and validity rules; a
+        deterministic result of its own inside the fp8 accuracy contract, not attend_tokens' bits."""
+        return self._decode("attend_decode", Q, lens, None, out)
+
     def _packed_rows(self, X: torch.Tensor, name: str, width: int) -> torch.Tensor:
         """A packed operand: float32 [total, width] on the cache's device, no batch axis."""
         if not isinstance(X, torch.Tensor) or not X.is_cuda:
@@ -526,6 +566,7 @@ class PagedKVCache:
         self._handle = None
         self.tail = None  # enable_tokens()
         self.split_scratch = None  # enable_split()
+        self.decode_scratch = None  # enable_decode()
         nbytes = lib.qmha_kv_cache_paged_bytes(self.num_pages, self.page_rows, self.d_model, self.num_heads, self.num_kv_heads, vid)
         self.mem = torch.zeros(max(nbytes, 1), dtype=torch.uint8, device=self.device)
         handle = ctypes.c_void_p()
@@ -609,6 +650,13 @@ class PagedKVCache:
                                                             self.split_scratch.numel(), _lib.QMHA_FLAG_CAUSAL, stream)
         _lib.check(st, f"PagedKVCache.attend_paged_split({self.kernel})")
         return out.view(Q.shape) if out.numel() == Q.numel() and out.dim() != Q.dim() else out
+
+    enable_decode = KVCache.enable_decode
+    _decode = KVCache._decode
+
+    def attend_paged_decode(self, Q: torch.Tensor, lens: torch.Tensor, table: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """attend_decode through the table (qmha_attend_cached_paged_decode), bit for bit; needs enable_decode()."""
+        return self._decode("attend_paged_decode", Q, lens, self._table(table), out)
 
     _packed_rows = KVCache._packed_rows
     _cu = KVCache._cu

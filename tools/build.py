@@ -32,7 +32,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
 KERNEL_SOURCES = ["qmha_fa_int8.hip", "qmha_fa_f16.hip", "qmha_fa_masked.hip", "qmha_fa_split.hip", "qmha_fa_packed.hip",
-                  "qmha_fa_window.hip", "qmha_fa_fp8.hip",
+                  "qmha_fa_window.hip", "qmha_fa_fp8.hip", "qmha_fp8_decode.hip",
                   "qmha_prepass.hip", "qmha_kv_fp8.hip",
                   "qmha_fa_f32.hip", "qmha_unfused.hip", "qmha_api.cpp"]
 # profiling builds (QMHA_EXTRA_FLAGS=-DQMHA_ABLATION) enable the tuning alternatives of the fp16 / fp32 / api
@@ -42,7 +42,7 @@ KERNEL_SOURCES = ["qmha_fa_int8.hip", "qmha_fa_f16.hip", "qmha_fa_masked.hip", "
 # (tools/ablation/qmha_fa_int8_ablation.hip).  Int8 ablation builds compile the production source.
 VARIANTS = {"fa": 0, "fa_tc_v1a": 1, "fa_tc_int8_b": 2, "unfused": 3, "fa_mfma": 4, "fa_tc_int8_pt": 5}
 DRIVER_SOURCES = ["driver/main.cpp", "driver/data.cpp", "driver/verify.cpp"]
-HEADERS = ["qmha_common.hpp", "qmha_kernels.hpp", "qmha_fa_masked.hpp", "qmha_fa_masked_int8.inc", "qmha_fa_masked_f16.inc",
+HEADERS = ["qmha_common.hpp", "qmha_kernels.hpp", "qmha_fa_masked.hpp", "qmha_fp8.hpp", "qmha_fa_masked_int8.inc", "qmha_fa_masked_f16.inc",
            "driver/data.h", "driver/verify.h"]
 
 COMMON_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
@@ -93,6 +93,7 @@ FILE_FLAGS = {"qmha_fa_int8.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + os
               "qmha_fa_packed.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + os.environ.get("QMHA_CAUSAL_FLAGS", "").split(),
               "qmha_fa_window.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + os.environ.get("QMHA_CAUSAL_FLAGS", "").split(),
               "qmha_fa_fp8.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + NO_PK_F32,
+              "qmha_fp8_decode.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + NO_PK_F32,
               "qmha_kv_fp8.hip": NO_PK_F32,
               "qmha_fa_f32.hip": os.environ.get("QMHA_F32_FLAGS", "").split()}
 

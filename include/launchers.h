@@ -416,6 +416,45 @@ int qmha_attend_cached_paged_decode(qmha_kv_cache_t *c, const float *Q, float *O
                                     void *stream);
 
 /*
+ * The windowed decode call of an fp8 cache, with attention sinks -- the decode call above for a sliding-window layer
+ * (Mistral, Gemma 2/3, gpt-oss), with kernels of its own.  Operands, device lens and table, causal only, the
+ * validity rules, positive zeros for an invalid sequence, W = Nq * (h / h_kv) <= 32 and the chunk_rows rules are the decode
+ * call's.  A deterministic function of its own inside the fp8 accuracy contract.
+ *
+ *   window         a host int >= 1, no multiple of anything (else QMHA_ERR_INVALID).  With e_r = lens[b] - Nq + r, row r
+ *                  sees key j iff e_r - window < j <= e_r.
+ *   sinks          null, or a DEVICE float32[h] of finite values in natural-log units of S / sqrt(d): head k's softmax has
+ *                  one more column sinks[k] with no value row, O = sum_j p_j v_j / (sum_j p_j + exp(sinks[k] - m)).  The
+ *                  term carries the 2^8 bias l carries and its log2 exponent is clamped at 120.  NaN or infinite sinks:
+ *                  unspecified.
+ *   sweep          lo = max(0, lens[b] - Nq - window + 1), t0 = 2 * (lo / 64): the tiles are t0 ... (lens[b] - 1) / 32,
+ *                  chunk c is tiles t0 + c * C ...; tiles before t0 are neither staged nor computed.  A sweep covers at most
+ *                  min(cap, Nq + window + 62) rows, so the grid and the scratch hold
+ *                  NCw = ceil(ceil(min(cap, Nq + window + 62) / 32) / C) <= ceil(cap / chunk_rows) chunks.
+ *   partial        the decode call's, the left edge a select to -inf before the maximum.  Row r writes chunk c iff
+ *                  c <= ((lens[b] - Nq + r) / 32 - t0) / C; a chunk that holds no key the row sees is written as l = 0,
+ *                  Oc = 0 with a finite m.  No NaN or infinity reaches the scratch or O.
+ *   two forms      NCw == 1: one launch, the sweep kernel adds the sink term and writes O; the scratch is not touched.
+ *                  NCw > 1: partials, then a combine kernel with the split combine's arithmetic and order, the sink term
+ *                  added to Ltot last -- for a sequence with window >= lens[b] and null sinks O is the decode call's at the
+ *                  same chunk_rows, bit for bit.
+ *   paged          only the table columns whose pages hold rows [32 * t0, lens[b]) are read and checked; the columns
+ *                  behind may hold anything and their pages may have been given back.
+ *   scratch        the decode call's layout at NCw chunks; qmha_attend_decode_window_bytes(c, Nq, window, chunk_rows) bytes
+ *                  (0 on invalid arguments), needed (non-null, 256-byte aligned, large enough) in both forms.
+ *
+ * A cache that is not fa_tc_fp8: QMHA_ERR_NOSYS (use attend_tokens_window / attend_paged_window).  One qmha_profile main
+ * pair covers the launches; no allocation, no synchronisation, no atomics, no waiting between workgroups: capturable.
+ */
+size_t qmha_attend_decode_window_bytes(const qmha_kv_cache_t *c, int Nq, int window, int chunk_rows);
+int qmha_attend_cached_decode_window(qmha_kv_cache_t *c, const float *Q, float *O, int Nq, const int32_t *lens, int window,
+                                     const float *sinks, int chunk_rows, void *scratch, size_t scratch_bytes, unsigned flags,
+                                     void *stream);
+int qmha_attend_cached_paged_decode_window(qmha_kv_cache_t *c, const float *Q, float *O, int Nq, const int32_t *lens,
+                                           const int32_t *table, int window, const float *sinks, int chunk_rows, void *scratch,
+                                           size_t scratch_bytes, unsigned flags, void *stream);
+
+/*
  * Packed batches -- a query count and an append count per sequence in one call, for a continuous-batching step that
  * mixes chunked prefill and decode.  The operands have no batch axis, in the cu_seqlens convention of varlen attention:
  *

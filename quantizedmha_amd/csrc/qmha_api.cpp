@@ -1085,6 +1085,70 @@ int qmha_attend_cached_paged_decode(qmha_kv_cache_t* c, const float* Q, float* O
     return attend_decode(c, "attend_paged_decode", Q, O, Nq, lens, table, true, chunk_rows, scratch, scratch_bytes, flags, stream);
 }
 
+// ---- the windowed decode call of an fp8 cache, with attention sinks: the decode call's columns and streams
+// over the chunks of the window's own sweep; one launch where that is a single chunk -----------
+namespace {
+
+size_t decode_window_bytes(const qmha_kv_cache* c, int Nq, int window, int chunk_rows) {
+    return qmha::split_carve(nullptr, c->B, qmha::decode_window_chunks(c->cap, Nq, window, chunk_rows), Nq, c->h, c->D).bytes;
+}
+
+// both entry points: `table` null is the contiguous one.  The checks of attend_decode, and the window
+int attend_decode_window(qmha_kv_cache_t* c, const char* what, const float* Q, float* O, int Nq, const int32_t* lens, const int32_t* table,
+                         bool paged, int window, const float* sinks, int chunk_rows, void* scratch, size_t scratch_bytes, unsigned flags,
+                         void* stream) {
+    const CacheCall k{c, what, paged};
+    if (int st = k.operands(Q, O)) return st;
+    if (c->variant != QMHA_FA_TC_FP8)
+        return fail(QMHA_ERR_NOSYS, std::string(what) + ": the windowed decode call is built for a fa_tc_fp8 cache only; this cache is " +
+                                        qmha_variant_name(c->variant) + ": use attend_tokens_window / attend_paged_window");
+    if (int st = k.attend_words(lens, table, flags)) return st;
+    if (int st = k.rows("Nq", Nq)) return st;
+    const int G = c->h / c->h_kv;
+    if ((long long)Nq * G > kDecodeColumns)
+        return k.bad("Nq * (h / h_kv) = " + std::to_string(Nq) + " * " + std::to_string(G) + " = " + std::to_string((long long)Nq * G) +
+                     " query rows per K/V head, the limit is " + std::to_string(kDecodeColumns) +
+                     " (two 16-column MFMA blocks): split a longer query block into calls of that many rows");
+    if (window < 1) return k.bad("window = " + std::to_string(window) + " keys, needs window >= 1 (any int: a row sees its last `window` keys)");
+    if (!split_chunk_ok(c, chunk_rows))
+        return k.bad("chunk_rows = " + std::to_string(chunk_rows) + " must be a multiple of 64 with 64 <= chunk_rows <= cap = " +
+                     std::to_string(c->cap) + " (a chunk is a whole number of two-tile stages)");
+    if (!scratch) return k.bad("null scratch (qmha_attend_decode_window_bytes bytes of device memory)");
+    if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return k.bad("scratch must be 256-byte aligned");
+    const size_t need = decode_window_bytes(c, Nq, window, chunk_rows);
+    if (scratch_bytes < need)
+        return k.bad("scratch too small: " + std::to_string(scratch_bytes) + " bytes, qmha_attend_decode_window_bytes is " +
+                     std::to_string(need));
+    return cache_enqueue(c, &ProfRec::main, stream, k.label().c_str(), kNoLenCheck, [&](const auto& ws, int) {  // one pair around the launches
+        if constexpr (std::is_same<std::decay_t<decltype(ws)>, qmha::Fp8Workspace>::value)
+            return qmha::launch_fp8_decode_window(ws, Q, O, k.attend(Nq, lens, table), window, sinks, chunk_rows, scratch, (hipStream_t)stream);
+        else
+            return hipErrorNotSupported;  // refused above
+    });
+}
+
+}  // namespace
+
+size_t qmha_attend_decode_window_bytes(const qmha_kv_cache_t* c, int Nq, int window, int chunk_rows) {
+    if (!c || c->variant != QMHA_FA_TC_FP8 || Nq < 1 || (long long)Nq * (c->h / c->h_kv) > kDecodeColumns || window < 1 ||
+        !split_chunk_ok(c, chunk_rows))
+        return 0;
+    return decode_window_bytes(c, Nq, window, chunk_rows);
+}
+
+int qmha_attend_cached_decode_window(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, const int32_t* lens, int window, const float* sinks,
+                                     int chunk_rows, void* scratch, size_t scratch_bytes, unsigned flags, void* stream) {
+    return attend_decode_window(c, "attend_decode_window", Q, O, Nq, lens, nullptr, false, window, sinks, chunk_rows, scratch, scratch_bytes,
+                                flags, stream);
+}
+
+int qmha_attend_cached_paged_decode_window(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, const int32_t* lens, const int32_t* table,
+                                           int window, const float* sinks, int chunk_rows, void* scratch, size_t scratch_bytes, unsigned flags,
+                                           void* stream) {
+    return attend_decode_window(c, "attend_paged_decode_window", Q, O, Nq, lens, table, true, window, sinks, chunk_rows, scratch,
+                                scratch_bytes, flags, stream);
+}
+
 // ---- packed batches: a query / append count per sequence from a device cu[B + 1], no batch axis -----------
 namespace {
 

@@ -349,6 +349,20 @@ hipError_t launch_kv_tokens(const float* K, const float* V, const Fp8Workspace& 
 // partials; qmha_split_combine_kernel writes O.  chunk_rows: a multiple of 64 in [64, Nk].
 hipError_t launch_fp8_decode(const Fp8Workspace& w, const float* Qf, float* O, const MaskedCall& c, int chunk_rows, void* scratch,
                              hipStream_t stream);
+// The windowed decode call with attention sinks (qmha_fp8_decode_window.hip).  launch_fp8_decode's call in
+// which row r sees key j iff e_r - window < j <= e_r, e_r = lens[b] - Nq + r, and head k's softmax has one more column
+// sinks[k] (a DEVICE float32[H] in natural-log units of S / sqrt(d), or null) with no value row.  The sweep starts at the
+// two-tile stage that holds row max(0, L - Nq - window + 1), so the chunks a grid needs follow the window, not the cache:
+// a sweep covers at most min(cap, Nq + window + 62) rows, decode_window_chunks of them.  One chunk: the
+// sweep kernel writes O itself, one launch, `scratch` untouched; more: partials into `scratch` (split_carve at that chunk
+// count) and a combine kernel of this unit's own.  window >= 1, any int.
+inline int decode_window_chunks(int cap, int Nq, int window, int chunk_rows) {
+    const long long span = (long long)Nq + window + 62, rows = span < cap ? span : cap;
+    const int tiles = (int)((rows + 31) / 32), C = chunk_rows / 32;  // 32-row key tiles
+    return (tiles + C - 1) / C;
+}
+hipError_t launch_fp8_decode_window(const Fp8Workspace& w, const float* Qf, float* O, const MaskedCall& c, int window, const float* sinks,
+                                    int chunk_rows, void* scratch, hipStream_t stream);
 // Not built on an fp8 cache (the C-ABI refuses these calls before it gets here): split-KV, windows, packed batches
 inline hipError_t launch_fa_split(const Fp8Workspace&, const float*, float*, const MaskedCall&, int, void*, hipStream_t) { return hipErrorNotSupported; }
 inline hipError_t launch_fa_window(const Fp8Workspace&, const float*, float*, const MaskedCall&, int, hipStream_t) { return hipErrorNotSupported; }

@@ -266,6 +266,45 @@ struct DecodeState {
     std::optional<Tensor> tensor() const { return scratch.defined() ? std::optional<Tensor>(scratch) : std::nullopt; }
 };
 
+// The scratch of an fp8 cache's windowed decode call (enable_decode_window): what both cache classes keep for
+// attend_decode_window / attend_paged_decode_window.  `table` null is the contiguous call; sinks: float32 [num_heads] or none.
+struct DecodeWindowState {
+    int64_t chunk_rows = 0, window = 0, max_nq = 0;
+    Tensor scratch;
+
+    static int clamp(int64_t w) { return static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(w, INT32_MAX))); }  // the C-ABI refuses 0
+    void enable(qmha_kv_cache_t* handle, int64_t chunk, int64_t win, int64_t nq, int64_t cap, const std::string& kernel, const c10::Device& device) {
+        const size_t bytes = win < 1 ? 0 : qmha_attend_decode_window_bytes(handle, static_cast<int>(nq), clamp(win), static_cast<int>(chunk));
+        TORCH_CHECK(bytes > 0, "enable_decode_window: needs a fa_tc_fp8 cache (this one is ", kernel, "; other caches have attend_tokens_window), ",
+                    "window = ", win, " >= 1, chunk_rows = ", chunk, " a multiple of 64 with 64 <= chunk_rows <= cap = ", cap,
+                    ", and 1 <= max_nq = ", nq, " with max_nq * (num_heads / num_kv_heads) <= 32");
+        chunk_rows = chunk, window = win, max_nq = nq;
+        scratch = torch::zeros({static_cast<int64_t>(bytes)}, torch::TensorOptions().dtype(torch::kUInt8).device(device));
+    }
+    int attend(qmha_kv_cache_t* handle, const char* what, const Tensor& Qc, Tensor& out, const Tensor& lens, const int32_t* table, int64_t win,
+               const std::optional<Tensor>& sinks, int64_t heads, void* stream) const {
+        TORCH_CHECK(scratch.defined(), what, ": call enable_decode_window(chunk_rows, window) first");
+        TORCH_CHECK(Qc.size(1) <= max_nq, what, ": Nq = ", Qc.size(1), " rows exceed enable_decode_window's max_nq = ", max_nq);
+        TORCH_CHECK(win <= window, what, ": window = ", win, " exceeds enable_decode_window's window = ", window);
+        const float* sp = nullptr;
+        Tensor sc;
+        if (sinks) {
+            TORCH_CHECK(sinks->is_cuda() && sinks->scalar_type() == torch::kFloat32 && sinks->device() == Qc.device() && sinks->numel() == heads,
+                        what, ": sinks must be a float32 CUDA tensor of num_heads = ", heads, " elements on the cache's device");
+            sc = sinks->contiguous();
+            sp = sc.data_ptr<float>();
+        }
+        const int Nq = static_cast<int>(Qc.size(1)), chunk = static_cast<int>(chunk_rows);
+        const size_t bytes = static_cast<size_t>(scratch.numel());
+        if (!table)
+            return qmha_attend_cached_decode_window(handle, Qc.data_ptr<float>(), out.data_ptr<float>(), Nq, lens.data_ptr<int32_t>(), clamp(win), sp,
+                                                    chunk, scratch.data_ptr(), bytes, QMHA_FLAG_CAUSAL, stream);
+        return qmha_attend_cached_paged_decode_window(handle, Qc.data_ptr<float>(), out.data_ptr<float>(), Nq, lens.data_ptr<int32_t>(), table,
+                                                      clamp(win), sp, chunk, scratch.data_ptr(), bytes, QMHA_FLAG_CAUSAL, stream);
+    }
+    std::optional<Tensor> tensor() const { return scratch.defined() ? std::optional<Tensor>(scratch) : std::nullopt; }
+};
+
 // A persistent quantised K/V cache (qmha_kv_cache_*): the compiled form of quantizedmha_amd/torch_ext.py's KVCache.
 // Owns a uint8 tensor of qmha_kv_cache_bytes and the host handle; append / attend run on PyTorch's current stream.
 class KVCache {
@@ -436,6 +475,21 @@ public:
         return out_opt ? out : out.view(Q.sizes());
     }
 
+    // an fp8 cache's windowed decode call with attention sinks (qmha_attend_cached_decode_window)
+    void enable_decode_window(int64_t chunk_rows, int64_t window, int64_t max_nq) {
+        decode_window_.enable(handle_, chunk_rows, window, max_nq, cap_, kernel_, mem_.device());
+    }
+    std::optional<Tensor> decode_window_scratch() const { return decode_window_.tensor(); }
+    Tensor attend_decode_window(const Tensor& Q, const Tensor& lens, int64_t window, std::optional<Tensor> sinks, std::optional<Tensor> out_opt) {
+        auto Qc = rows(Q, "Q", d_model_);
+        per_seq(lens, "lens");
+        Tensor out = out_for(out_opt, Qc);
+        const OnStream on = current_stream(mem_.device());
+        const int st = decode_window_.attend(handle_, "attend_decode_window", Qc, out, lens, nullptr, window, sinks, num_heads_, on.stream);
+        TORCH_CHECK(st == QMHA_OK, "KVCache.attend_decode_window", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+        return out_opt ? out : out.view(Q.sizes());
+    }
+
     // append_tokens with a row count per sequence (qmha_kv_cache_append_packed): K, V [total, num_kv_heads * d], cu int32 [B + 1]
     void append_packed(const Tensor& K, const Tensor& V, const Tensor& cu, const Tensor& pos, int64_t max_n) {
         auto Kc = cache_packed_rows(K, "K", kv_model_, mem_.device()), Vc = cache_packed_rows(V, "V", kv_model_, mem_.device());
@@ -470,6 +524,7 @@ private:
     Tensor mem_, tail_;
     SplitState split_;
     DecodeState decode_;
+    DecodeWindowState decode_window_;
     qmha_kv_cache_t* handle_ = nullptr;
 };
 
@@ -603,6 +658,24 @@ public:
         return out_opt ? out : out.view(Q.sizes());
     }
 
+    // the windowed decode call through the block table (qmha_attend_cached_paged_decode_window); the scratch as KVCache's
+    void enable_decode_window(int64_t chunk_rows, int64_t window, int64_t max_nq) {
+        decode_window_.enable(handle_, chunk_rows, window, max_nq, cap_, kernel_, mem_.device());
+    }
+    std::optional<Tensor> decode_window_scratch() const { return decode_window_.tensor(); }
+    Tensor attend_paged_decode_window(const Tensor& Q, const Tensor& lens, const Tensor& table, int64_t window, std::optional<Tensor> sinks,
+                                      std::optional<Tensor> out_opt) {
+        auto Qc = cache_rows(Q, "Q", d_model_, B_, mem_.device());
+        cache_per_seq(lens, "lens", B_, mem_.device());
+        check_table(table);
+        Tensor out = out_for(out_opt, Qc);
+        const OnStream on = current_stream(mem_.device());
+        const int st = decode_window_.attend(handle_, "attend_paged_decode_window", Qc, out, lens, table.data_ptr<int32_t>(), window, sinks,
+                                             num_heads_, on.stream);
+        TORCH_CHECK(st == QMHA_OK, "PagedKVCache.attend_paged_decode_window", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+        return out_opt ? out : out.view(Q.sizes());
+    }
+
     // append_packed through the block table (qmha_kv_cache_append_paged_packed)
     void append_paged_packed(const Tensor& K, const Tensor& V, const Tensor& cu, const Tensor& pos, const Tensor& table, int64_t max_n) {
         auto Kc = cache_packed_rows(K, "K", kv_model_, mem_.device()), Vc = cache_packed_rows(V, "V", kv_model_, mem_.device());
@@ -647,6 +720,7 @@ private:
     Tensor mem_, tail_;
     SplitState split_;
     DecodeState decode_;
+    DecodeWindowState decode_window_;
     qmha_kv_cache_t* handle_ = nullptr;
 };
 
@@ -696,6 +770,14 @@ PYBIND11_MODULE(torch_ext, m) {
         .def("attend_paged_decode", &PagedKVCache::attend_paged_decode, pybind11::arg("Q"), pybind11::arg("lens"), pybind11::arg("table"),
              pybind11::arg("out") = pybind11::none(), "attend_decode through the table, bit for bit.")
         .def_property_readonly("decode_scratch", &PagedKVCache::decode_scratch)
+        .def("enable_decode_window", &PagedKVCache::enable_decode_window, pybind11::arg("chunk_rows"), pybind11::arg("window"),
+             pybind11::arg("max_nq") = 1,
+             "allocate the scratch of attend_paged_decode_window (a fa_tc_fp8 cache) for windows of up to `window` keys, chunks of\n"
+             "chunk_rows key rows (a multiple of 64) and up to max_nq query rows per call; once, outside a graph capture.")
+        .def("attend_paged_decode_window", &PagedKVCache::attend_paged_decode_window, pybind11::arg("Q"), pybind11::arg("lens"),
+             pybind11::arg("table"), pybind11::arg("window"), pybind11::arg("sinks") = pybind11::none(), pybind11::arg("out") = pybind11::none(),
+             "attend_decode_window through the table, bit for bit; only the columns of the swept rows' pages are read.")
+        .def_property_readonly("decode_window_scratch", &PagedKVCache::decode_window_scratch)
         .def_property_readonly("split_scratch", &PagedKVCache::split_scratch)
         .def_property_readonly("tail", &PagedKVCache::tail)
         .def_property_readonly("cap", &PagedKVCache::cap)
@@ -751,6 +833,15 @@ PYBIND11_MODULE(torch_ext, m) {
              "attend_tokens of a fa_tc_fp8 cache for a decode or short speculative step: the step's query rows packed into MFMA\n"
              "columns, the key sweep in chunks, split-KV's combine pass.")
         .def_property_readonly("decode_scratch", &KVCache::decode_scratch)
+        .def("enable_decode_window", &KVCache::enable_decode_window, pybind11::arg("chunk_rows"), pybind11::arg("window"),
+             pybind11::arg("max_nq") = 1,
+             "allocate the scratch of attend_decode_window (a fa_tc_fp8 cache) for windows of up to `window` keys, chunks of chunk_rows\n"
+             "key rows (a multiple of 64) and up to max_nq query rows per call; once, outside a graph capture.")
+        .def("attend_decode_window", &KVCache::attend_decode_window, pybind11::arg("Q"), pybind11::arg("lens"), pybind11::arg("window"),
+             pybind11::arg("sinks") = pybind11::none(), pybind11::arg("out") = pybind11::none(),
+             "attend_decode for a sliding-window layer: a row sees its last `window` keys and the sweep follows the window, not the\n"
+             "sequence; sinks: None or a float32 [num_heads] tensor of attention sinks, one more softmax column per head.")
+        .def_property_readonly("decode_window_scratch", &KVCache::decode_window_scratch)
         .def_property_readonly("split_scratch", &KVCache::split_scratch)
         .def_property_readonly("tail", &KVCache::tail)
         .def_property_readonly("len", &KVCache::len)

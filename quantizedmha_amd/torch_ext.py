@@ -203,6 +203,7 @@ class KVCache:
         self.tail = None  # enable_tokens()
         self.split_scratch = None  # enable_split()
         self.decode_scratch = None  # enable_decode()
+        self.decode_window_scratch = None  # enable_decode_window()
         if num_kv_heads is None:
             nbytes = lib.qmha_kv_cache_bytes(self.B, self.cap, self.d_model, self.num_heads, vid)
         else:  # the carve of num_kv_heads heads
@@ -457,6 +458,60 @@ class KVCache:
         deterministic result of its own inside the fp8 accuracy contract, not attend_tokens' bits."""
         return self._decode("attend_decode", Q, lens, None, out)
 
+    def enable_decode_window(self, chunk_rows: int, window: int, max_nq: int = 1) -> None:
+        """Allocate the scratch of an fp8 cache's windowed decode call (qmha_attend_decode_window_bytes at Nq = max_nq),
+        `.decode_window_scratch`, for windows of up to `window` keys (any int >= 1) and chunks of chunk_rows key rows: a
+        multiple of 64 with 64 <= chunk_rows <= cap.  The sweep follows the window, so the scratch holds
+        ceil(ceil(min(cap, max_nq + window + 62) / 32) / (chunk_rows / 32)) chunks; where that is one chunk the call is a
+        single launch that leaves the scratch alone.  max_nq * (num_heads / num_kv_heads) <= 32.  Once, and outside a graph
+        capture: the call itself allocates nothing."""
+        chunk_rows, window, max_nq = int(chunk_rows), int(window), int(max_nq)
+        nbytes = _lib.load().qmha_attend_decode_window_bytes(self._handle, max_nq, max(0, min(window, 2 ** 31 - 1)), chunk_rows)
+        if nbytes == 0:
+            raise RuntimeError(f"enable_decode_window: needs a fa_tc_fp8 cache (this one is {self.kernel}; other caches have "
+                               f"attend_tokens_window), window = {window} >= 1, chunk_rows = {chunk_rows} a multiple of 64 with 64 <= "
+                               f"chunk_rows <= cap = {self.cap}, and 1 <= max_nq = {max_nq} with max_nq * (num_heads / num_kv_heads) <= 32")
+        self.decode_window_chunk_rows, self.decode_window_max, self.decode_window_max_nq = chunk_rows, window, max_nq
+        self.decode_window_scratch = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+
+    def _decode_window(self, what: str, Q: torch.Tensor, lens: torch.Tensor, table: Optional[torch.Tensor], window: int,
+                       sinks: Optional[torch.Tensor], out: Optional[torch.Tensor]) -> torch.Tensor:
+        """Both windowed decode calls: `table` None is the contiguous one."""
+        Qc = self._rows(Q, "Q")
+        lens = self._per_seq(lens, "lens")
+        if getattr(self, "decode_window_scratch", None) is None:
+            raise RuntimeError(f"{what}: call enable_decode_window(chunk_rows, window) first")
+        if Qc.shape[1] > self.decode_window_max_nq:
+            raise RuntimeError(f"{what}: Nq = {Qc.shape[1]} rows exceed enable_decode_window's max_nq = {self.decode_window_max_nq}")
+        window = max(0, min(int(window), 2 ** 31 - 1))  # the C-ABI refuses 0
+        if window > self.decode_window_max:
+            raise RuntimeError(f"{what}: window = {window} exceeds enable_decode_window's window = {self.decode_window_max}")
+        if sinks is not None:
+            if not isinstance(sinks, torch.Tensor) or sinks.dtype != torch.float32 or sinks.device != self.device or sinks.numel() != self.num_heads:
+                raise RuntimeError(f"{what}: sinks must be a float32 CUDA tensor of num_heads = {self.num_heads} elements on the cache's device")
+            sinks = sinks.contiguous()
+        out = _out_for(out, Qc, "size")
+        lib, scratch = _lib.load(), self.decode_window_scratch
+        tail = (window, None if sinks is None else sinks.data_ptr(), self.decode_window_chunk_rows, scratch.data_ptr(), scratch.numel(),
+                _lib.QMHA_FLAG_CAUSAL)
+        with _current_stream(self.device) as stream:
+            if table is None:
+                st = lib.qmha_attend_cached_decode_window(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[1], lens.data_ptr(), *tail, stream)
+            else:
+                st = lib.qmha_attend_cached_paged_decode_window(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[1], lens.data_ptr(),
+                                                                table.data_ptr(), *tail, stream)
+        _lib.check(st, f"{type(self).__name__}.{what}({self.kernel})")
+        return out.view(Q.shape) if out.numel() == Q.numel() and out.dim() != Q.dim() else out
+
+    def attend_decode_window(self, Q: torch.Tensor, lens: torch.Tensor, window: int, sinks: Optional[torch.Tensor] = None,
+                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """attend_decode for a sliding-window layer (qmha_attend_cached_decode_window): row r of sequence b sees the last
+        `window` keys up to lens[b] - Nq + r, and the sweep starts at the two-tile stage that holds the first of them,
+        whatever the length is.  sinks: None, or a float32 [num_heads] tensor of attention sinks (natural-log units of
+        S / sqrt(d)): one more softmax column per head with no value row.  Needs enable_decode_window(); same arguments and
+        validity rules as attend_decode, a deterministic result of its own inside the fp8 accuracy contract."""
+        return self._decode_window("attend_decode_window", Q, lens, None, window, sinks, out)
+
     def _packed_rows(self, X: torch.Tensor, name: str, width: int) -> torch.Tensor:
         """A packed operand: float32 [total, width] on the cache's device, no batch axis."""
         if not isinstance(X, torch.Tensor) or not X.is_cuda:
@@ -567,6 +622,7 @@ class PagedKVCache:
         self.tail = None  # enable_tokens()
         self.split_scratch = None  # enable_split()
         self.decode_scratch = None  # enable_decode()
+        self.decode_window_scratch = None  # enable_decode_window()
         nbytes = lib.qmha_kv_cache_paged_bytes(self.num_pages, self.page_rows, self.d_model, self.num_heads, self.num_kv_heads, vid)
         self.mem = torch.zeros(max(nbytes, 1), dtype=torch.uint8, device=self.device)
         handle = ctypes.c_void_p()
@@ -657,6 +713,16 @@ class PagedKVCache:
     def attend_paged_decode(self, Q: torch.Tensor, lens: torch.Tensor, table: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """attend_decode through the table (qmha_attend_cached_paged_decode), bit for bit; needs enable_decode()."""
         return self._decode("attend_paged_decode", Q, lens, self._table(table), out)
+
+    enable_decode_window = KVCache.enable_decode_window
+    _decode_window = KVCache._decode_window
+
+    def attend_paged_decode_window(self, Q: torch.Tensor, lens: torch.Tensor, table: torch.Tensor, window: int,
+                                   sinks: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """attend_decode_window through the table (qmha_attend_cached_paged_decode_window), bit for bit: only the table columns
+        whose pages hold the swept rows are read, so the pages behind the window can be given back.  Needs
+        enable_decode_window()."""
+        return self._decode_window("attend_paged_decode_window", Q, lens, self._table(table), window, sinks, out)
 
     _packed_rows = KVCache._packed_rows
     _cu = KVCache._cu

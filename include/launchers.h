@@ -455,6 +455,41 @@ int qmha_attend_cached_paged_decode_window(qmha_kv_cache_t *c, const float *Q, f
                                            size_t scratch_bytes, unsigned flags, void *stream);
 
 /*
+ * The windowed prefill call of an fp8 cache, with attention sinks -- attend_tokens / attend_paged for a sliding-window layer
+ * (Mistral, Gemma 2/3, gpt-oss) at any number of query rows, with a kernel of its own.  Operands, device lens
+ * and table, causal only (flags must be QMHA_FLAG_CAUSAL) and the validity rules are attend_tokens' / attend_paged's: any
+ * Nq >= 1, Nq <= lens[b] <= cap; an invalid sequence gets positive zeros in its Nq rows of O and none of its K/V is read.
+ * No scratch and no enable step.  A deterministic function of its own inside the fp8 accuracy contract.
+ *
+ *   window         a host int >= 1, no multiple of anything (else QMHA_ERR_INVALID).  With e_r = lens[b] - Nq + r, row r
+ *                  sees key j iff e_r - window < j <= e_r.
+ *   sinks          null, or a DEVICE float32[h] of finite values in natural-log units of S / sqrt(d): head k's softmax has
+ *                  one more column sinks[k] with no value row, O = v_scale * o / (l + 2^(min(sinks[k] * log2(e) - m + 8, 120))),
+ *                  m the row's true running maximum after its last tile, the term added to the row sum last; O = 0 where
+ *                  that sum is not above 1e-10.  NaN or infinite sinks: unspecified.
+ *   arithmetic     attend_tokens' per row: key tiles of 32 in ascending order from the zero state, the true running maximum,
+ *                  p = exp2(s - m + 8) as e4m3 into P@V, l from the fp32 p; the left edge is a select to -inf before the
+ *                  maximum.  A row with no visible key in a tile keeps its state.  No NaN or infinity reaches O.
+ *   sweep          in the padded block of the token-granular calls (absolute rows keep their 32-row groups) the query group
+ *                  whose rows end in key tile dg sweeps tiles max(0, 32 * dg - window + 1) / 32 ... dg.  A workgroup stages
+ *                  from the two-tile stage that holds the first tile of its first query group; tiles before it are neither
+ *                  staged nor computed.
+ *   paged          only the table columns whose pages hold rows [32 * t0, lens[b]) are read and checked, t0 the first staged
+ *                  tile of the sequence's first query rows; the columns behind may hold anything (-1) and their pages may
+ *                  have been given back.  A checked entry outside [0, num_pages): zeros for that sequence.
+ *   identity       for a sequence with window >= lens[b] and null sinks, O is attend_tokens' / attend_paged's on the same
+ *                  cache, bit for bit; the paged call is the contiguous call, bit for bit.
+ *
+ * A cache that is not fa_tc_fp8: QMHA_ERR_NOSYS (use attend_tokens_window / attend_paged_window), before any HIP call.  One
+ * qmha_profile main pair around one plain launch; no allocation, no synchronisation, no atomics, no waiting between
+ * workgroups: capturable.
+ */
+int qmha_attend_cached_prefill_window(qmha_kv_cache_t *c, const float *Q, float *O, int Nq, const int32_t *lens, int window,
+                                      const float *sinks, unsigned flags, void *stream);
+int qmha_attend_cached_paged_prefill_window(qmha_kv_cache_t *c, const float *Q, float *O, int Nq, const int32_t *lens,
+                                            const int32_t *table, int window, const float *sinks, unsigned flags, void *stream);
+
+/*
  * Packed batches -- a query count and an append count per sequence in one call, for a continuous-batching step that
  * mixes chunked prefill and decode.  The operands have no batch axis, in the cu_seqlens convention of varlen attention:
  *

@@ -63,6 +63,8 @@ SIGNATURES = {
     "qmha_attend_decode_window_bytes": (_sz, [_vp, _i, _i, _i]),
     "qmha_attend_cached_decode_window": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _sz, ctypes.c_uint, _vp]),
     "qmha_attend_cached_paged_decode_window": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _sz, ctypes.c_uint, _vp]),
+    "qmha_attend_cached_prefill_window": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, ctypes.c_uint, _vp]),
+    "qmha_attend_cached_paged_prefill_window": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, ctypes.c_uint, _vp]),
     # a sliding window: the two attends over the last `window` keys of a row (a host int, a multiple of 32)
     "qmha_attend_cached_tokens_window": (_i, [_vp, _vp, _vp, _i, _vp, _i, ctypes.c_uint, _vp]),
     "qmha_attend_cached_paged_window": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, ctypes.c_uint, _vp]),

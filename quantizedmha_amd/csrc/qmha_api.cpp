@@ -1149,6 +1149,41 @@ int qmha_attend_cached_paged_decode_window(qmha_kv_cache_t* c, const float* Q, f
                                 scratch_bytes, flags, stream);
 }
 
+// ---- the windowed prefill call of an fp8 cache, with attention sinks: attend_tokens' rows and grid over the
+// band of each query group; one launch, no scratch -----------
+namespace {
+
+// both entry points: `table` null is the contiguous one.  The checks of attend_rows, and the window
+int attend_prefill_window(qmha_kv_cache_t* c, const char* what, const float* Q, float* O, int Nq, const int32_t* lens, const int32_t* table,
+                          bool paged, int window, const float* sinks, unsigned flags, void* stream) {
+    const CacheCall k{c, what, paged};
+    if (int st = k.operands(Q, O)) return st;
+    if (c->variant != QMHA_FA_TC_FP8)
+        return fail(QMHA_ERR_NOSYS, std::string(what) + ": the windowed prefill call is built for a fa_tc_fp8 cache only; this cache is " +
+                                        qmha_variant_name(c->variant) + ": use attend_tokens_window / attend_paged_window");
+    if (int st = k.attend_words(lens, table, flags)) return st;
+    if (int st = k.rows("Nq", Nq)) return st;
+    if (window < 1) return k.bad("window = " + std::to_string(window) + " keys, needs window >= 1 (any int: a row sees its last `window` keys)");
+    return cache_enqueue(c, &ProfRec::main, stream, k.label().c_str(), kNoLenCheck, [&](const auto& ws, int) {
+        if constexpr (std::is_same<std::decay_t<decltype(ws)>, qmha::Fp8Workspace>::value)
+            return qmha::launch_fp8_band(ws, Q, O, k.attend(Nq, lens, table), window, sinks, (hipStream_t)stream);
+        else
+            return hipErrorNotSupported;  // refused above
+    });
+}
+
+}  // namespace
+
+int qmha_attend_cached_prefill_window(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, const int32_t* lens, int window, const float* sinks,
+                                      unsigned flags, void* stream) {
+    return attend_prefill_window(c, "attend_prefill_window", Q, O, Nq, lens, nullptr, false, window, sinks, flags, stream);
+}
+
+int qmha_attend_cached_paged_prefill_window(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, const int32_t* lens, const int32_t* table,
+                                            int window, const float* sinks, unsigned flags, void* stream) {
+    return attend_prefill_window(c, "attend_paged_prefill_window", Q, O, Nq, lens, table, true, window, sinks, flags, stream);
+}
+
 // ---- packed batches: a query / append count per sequence from a device cu[B + 1], no batch axis -----------
 namespace {
 

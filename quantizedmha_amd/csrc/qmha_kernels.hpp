@@ -363,6 +363,13 @@ inline int decode_window_chunks(int cap, int Nq, int window, int chunk_rows) {
 }
 hipError_t launch_fp8_decode_window(const Fp8Workspace& w, const float* Qf, float* O, const MaskedCall& c, int window, const float* sinks,
                                     int chunk_rows, void* scratch, hipStream_t stream);
+// The windowed prefill call with attention sinks (qmha_fp8_band.hip).  launch_fa_masked's token-granular call
+// (ragged, with lens; a table: paged; any Nq) in which row r sees key j iff e_r - window < j <= e_r, e_r = lens[b] - Nq + r, and
+// head k's softmax has one more column sinks[k] (a DEVICE float32[H] in natural-log units of S / sqrt(d), or null) with no
+// value row.  That call's grid; a workgroup's sweep starts at the two-tile stage that holds the first key its first query
+// group sees.  One launch, no scratch.  window >= 1, any int.
+hipError_t launch_fp8_band(const Fp8Workspace& w, const float* Qf, float* O, const MaskedCall& c, int window, const float* sinks,
+                           hipStream_t stream);
 // Not built on an fp8 cache (the C-ABI refuses these calls before it gets here): split-KV, windows, packed batches
 inline hipError_t launch_fa_split(const Fp8Workspace&, const float*, float*, const MaskedCall&, int, void*, hipStream_t) { return hipErrorNotSupported; }
 inline hipError_t launch_fa_window(const Fp8Workspace&, const float*, float*, const MaskedCall&, int, hipStream_t) { return hipErrorNotSupported; }

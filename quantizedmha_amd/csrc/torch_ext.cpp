@@ -305,6 +305,27 @@ struct DecodeWindowState {
     std::optional<Tensor> tensor() const { return scratch.defined() ? std::optional<Tensor>(scratch) : std::nullopt; }
 };
 
+// An fp8 cache's windowed prefill call (qmha_attend_cached_prefill_window / _paged_prefill_window): no scratch, no state.
+// `table` null is the contiguous call; sinks: float32 [num_heads] or none.
+static int prefill_window_attend(qmha_kv_cache_t* handle, const char* what, const Tensor& Qc, Tensor& out, const Tensor& lens,
+                                 const int32_t* table, int64_t win, const std::optional<Tensor>& sinks, int64_t heads, void* stream) {
+    const float* sp = nullptr;
+    Tensor sc;
+    if (sinks) {
+        TORCH_CHECK(sinks->is_cuda() && sinks->scalar_type() == torch::kFloat32 && sinks->device() == Qc.device() && sinks->numel() == heads,
+                    what, ": sinks must be a float32 CUDA tensor of num_heads = ", heads, " elements on the cache's device");
+        sc = sinks->contiguous();
+        sp = sc.data_ptr<float>();
+    }
+    const int Nq = static_cast<int>(Qc.size(1));
+    const int w = static_cast<int>(std::max<int64_t>(-1, std::min<int64_t>(win, INT32_MAX)));  // the C-ABI refuses anything below 1
+    if (!table)
+        return qmha_attend_cached_prefill_window(handle, Qc.data_ptr<float>(), out.data_ptr<float>(), Nq, lens.data_ptr<int32_t>(), w, sp,
+                                                 QMHA_FLAG_CAUSAL, stream);
+    return qmha_attend_cached_paged_prefill_window(handle, Qc.data_ptr<float>(), out.data_ptr<float>(), Nq, lens.data_ptr<int32_t>(), table, w, sp,
+                                                   QMHA_FLAG_CAUSAL, stream);
+}
+
 // A persistent quantised K/V cache (qmha_kv_cache_*): the compiled form of quantizedmha_amd/torch_ext.py's KVCache.
 // Owns a uint8 tensor of qmha_kv_cache_bytes and the host handle; append / attend run on PyTorch's current stream.
 class KVCache {
@@ -487,6 +508,17 @@ public:
         const OnStream on = current_stream(mem_.device());
         const int st = decode_window_.attend(handle_, "attend_decode_window", Qc, out, lens, nullptr, window, sinks, num_heads_, on.stream);
         TORCH_CHECK(st == QMHA_OK, "KVCache.attend_decode_window", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+        return out_opt ? out : out.view(Q.sizes());
+    }
+
+    // an fp8 cache's windowed prefill call with attention sinks (qmha_attend_cached_prefill_window): any Nq, no scratch
+    Tensor attend_prefill_window(const Tensor& Q, const Tensor& lens, int64_t window, std::optional<Tensor> sinks, std::optional<Tensor> out_opt) {
+        auto Qc = rows(Q, "Q", d_model_);
+        per_seq(lens, "lens");
+        Tensor out = out_for(out_opt, Qc);
+        const OnStream on = current_stream(mem_.device());
+        const int st = prefill_window_attend(handle_, "attend_prefill_window", Qc, out, lens, nullptr, window, sinks, num_heads_, on.stream);
+        TORCH_CHECK(st == QMHA_OK, "KVCache.attend_prefill_window", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
         return out_opt ? out : out.view(Q.sizes());
     }
 
@@ -676,6 +708,20 @@ public:
         return out_opt ? out : out.view(Q.sizes());
     }
 
+    // the windowed prefill call through the block table (qmha_attend_cached_paged_prefill_window)
+    Tensor attend_paged_prefill_window(const Tensor& Q, const Tensor& lens, const Tensor& table, int64_t window, std::optional<Tensor> sinks,
+                                       std::optional<Tensor> out_opt) {
+        auto Qc = cache_rows(Q, "Q", d_model_, B_, mem_.device());
+        cache_per_seq(lens, "lens", B_, mem_.device());
+        check_table(table);
+        Tensor out = out_for(out_opt, Qc);
+        const OnStream on = current_stream(mem_.device());
+        const int st = prefill_window_attend(handle_, "attend_paged_prefill_window", Qc, out, lens, table.data_ptr<int32_t>(), window, sinks,
+                                             num_heads_, on.stream);
+        TORCH_CHECK(st == QMHA_OK, "PagedKVCache.attend_paged_prefill_window", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+        return out_opt ? out : out.view(Q.sizes());
+    }
+
     // append_packed through the block table (qmha_kv_cache_append_paged_packed)
     void append_paged_packed(const Tensor& K, const Tensor& V, const Tensor& cu, const Tensor& pos, const Tensor& table, int64_t max_n) {
         auto Kc = cache_packed_rows(K, "K", kv_model_, mem_.device()), Vc = cache_packed_rows(V, "V", kv_model_, mem_.device());
@@ -778,6 +824,9 @@ PYBIND11_MODULE(torch_ext, m) {
              pybind11::arg("table"), pybind11::arg("window"), pybind11::arg("sinks") = pybind11::none(), pybind11::arg("out") = pybind11::none(),
              "attend_decode_window through the table, bit for bit; only the columns of the swept rows' pages are read.")
         .def_property_readonly("decode_window_scratch", &PagedKVCache::decode_window_scratch)
+        .def("attend_paged_prefill_window", &PagedKVCache::attend_paged_prefill_window, pybind11::arg("Q"), pybind11::arg("lens"),
+             pybind11::arg("table"), pybind11::arg("window"), pybind11::arg("sinks") = pybind11::none(), pybind11::arg("out") = pybind11::none(),
+             "attend_prefill_window through the table, bit for bit; only the columns of the swept rows' pages are read.")
         .def_property_readonly("split_scratch", &PagedKVCache::split_scratch)
         .def_property_readonly("tail", &PagedKVCache::tail)
         .def_property_readonly("cap", &PagedKVCache::cap)
@@ -842,6 +891,10 @@ PYBIND11_MODULE(torch_ext, m) {
              "attend_decode for a sliding-window layer: a row sees its last `window` keys and the sweep follows the window, not the\n"
              "sequence; sinks: None or a float32 [num_heads] tensor of attention sinks, one more softmax column per head.")
         .def_property_readonly("decode_window_scratch", &KVCache::decode_window_scratch)
+        .def("attend_prefill_window", &KVCache::attend_prefill_window, pybind11::arg("Q"), pybind11::arg("lens"), pybind11::arg("window"),
+             pybind11::arg("sinks") = pybind11::none(), pybind11::arg("out") = pybind11::none(),
+             "attend_tokens of a fa_tc_fp8 cache for a sliding-window layer, any Nq: a row sees its last `window` keys and each query\n"
+             "group's sweep follows its band; sinks: None or a float32 [num_heads] tensor of attention sinks.  No scratch.")
         .def_property_readonly("split_scratch", &KVCache::split_scratch)
         .def_property_readonly("tail", &KVCache::tail)
         .def_property_readonly("len", &KVCache::len)

@@ -512,6 +512,36 @@ class KVCache:
         validity rules as attend_decode, a deterministic result of its own inside the fp8 accuracy contract."""
         return self._decode_window("attend_decode_window", Q, lens, None, window, sinks, out)
 
+    def _prefill_window(self, what: str, Q: torch.Tensor, lens: torch.Tensor, table: Optional[torch.Tensor], window: int,
+                        sinks: Optional[torch.Tensor], out: Optional[torch.Tensor]) -> torch.Tensor:
+        """Both windowed prefill calls: `table` None is the contiguous one."""
+        Qc = self._rows(Q, "Q")
+        lens = self._per_seq(lens, "lens")
+        window = max(-1, min(int(window), 2 ** 31 - 1))  # the C-ABI refuses anything below 1
+        if sinks is not None:
+            if not isinstance(sinks, torch.Tensor) or sinks.dtype != torch.float32 or sinks.device != self.device or sinks.numel() != self.num_heads:
+                raise RuntimeError(f"{what}: sinks must be a float32 CUDA tensor of num_heads = {self.num_heads} elements on the cache's device")
+            sinks = sinks.contiguous()
+        out = _out_for(out, Qc, "size")
+        lib, tail = _lib.load(), (window, None if sinks is None else sinks.data_ptr(), _lib.QMHA_FLAG_CAUSAL)
+        with _current_stream(self.device) as stream:
+            if table is None:
+                st = lib.qmha_attend_cached_prefill_window(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[1], lens.data_ptr(), *tail, stream)
+            else:
+                st = lib.qmha_attend_cached_paged_prefill_window(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[1], lens.data_ptr(),
+                                                                 table.data_ptr(), *tail, stream)
+        _lib.check(st, f"{type(self).__name__}.{what}({self.kernel})")
+        return out.view(Q.shape) if out.numel() == Q.numel() and out.dim() != Q.dim() else out
+
+    def attend_prefill_window(self, Q: torch.Tensor, lens: torch.Tensor, window: int, sinks: Optional[torch.Tensor] = None,
+                              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """attend_tokens of a fa_tc_fp8 cache for a sliding-window layer (qmha_attend_cached_prefill_window), any Nq >= 1: row r
+        of sequence b sees the last `window` keys (any int >= 1) up to lens[b] - Nq + r, and each query group's sweep starts at
+        the key tile that holds the first of them.  sinks: None, or a float32 [num_heads] tensor of attention sinks
+        (natural-log units of S / sqrt(d)): one more softmax column per head with no value row.  No scratch, no enable step;
+        attend_tokens' validity rules.  window >= lens[b] without sinks gives attend_tokens' bits."""
+        return self._prefill_window("attend_prefill_window", Q, lens, None, window, sinks, out)
+
     def _packed_rows(self, X: torch.Tensor, name: str, width: int) -> torch.Tensor:
         """A packed operand: float32 [total, width] on the cache's device, no batch axis."""
         if not isinstance(X, torch.Tensor) or not X.is_cuda:
@@ -723,6 +753,14 @@ class PagedKVCache:
         whose pages hold the swept rows are read, so the pages behind the window can be given back.  Needs
         enable_decode_window()."""
         return self._decode_window("attend_paged_decode_window", Q, lens, self._table(table), window, sinks, out)
+
+    _prefill_window = KVCache._prefill_window
+
+    def attend_paged_prefill_window(self, Q: torch.Tensor, lens: torch.Tensor, table: torch.Tensor, window: int,
+                                    sinks: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """attend_prefill_window through the table (qmha_attend_cached_paged_prefill_window), bit for bit: only the table columns
+        whose pages hold the swept rows are read, so the columns behind the band may hold -1 and their pages can be given back."""
+        return self._prefill_window("attend_paged_prefill_window", Q, lens, self._table(table), window, sinks, out)
 
     _packed_rows = KVCache._packed_rows
     _cu = KVCache._cu

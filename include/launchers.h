@@ -490,6 +490,49 @@ int qmha_attend_cached_paged_prefill_window(qmha_kv_cache_t *c, const float *Q, 
                                             const int32_t *table, int window, const float *sinks, unsigned flags, void *stream);
 
 /*
+ * The mixed-step calls of an fp8 cache -- a continuous-batching step (a few sequences in chunked prefill beside many that
+ * decode one row) as one append and one attend, with kernels and a work split of their own.  The operands
+ * follow the packed convention below: Q, O [total, d_model], K, V [total, h_kv * d], cu a DEVICE int32 [B + 1] read by the
+ * kernels when they run; lens, pos and table as in the token calls.  There is no max_nq / max_n: the grids are sized from
+ * total and B alone, so a captured step follows any mix the caller writes into cu.
+ *
+ *   kinds          nq_b = cu[b + 1] - cu[b], G = h / h_kv, decided on the device.  G * nq_b <= 32, the decode kind: the
+ *                  sequence's rows of O are, bit for bit, attend_decode_window's / attend_paged_decode_window's for a
+ *                  one-sequence batch of Nq = nq_b on the same cache bytes, length, window, sinks and chunk_rows (its
+ *                  one-launch form where that call has one chunk).  Otherwise the prefill kind: attend_prefill_window's /
+ *                  attend_paged_prefill_window's bits at Nq = nq_b.
+ *   append         n_b rows at pos[b] leave in the cache, bit for bit, what append_tokens / append_paged with n = n_b
+ *                  leaves; no other group is written.
+ *   window, sinks  as in the two windowed calls: any host int >= 1 (a global layer passes >= cap); null or a DEVICE
+ *                  float32[h].
+ *   chunk_rows     the decode kind's chunks: a multiple of 64 in [64, cap].
+ *   validity       per sequence, on the device, the packed calls' table without its max rows: a range outside
+ *                  0 <= cu[b] <= cu[b + 1] <= total never becomes an address; an empty range sits out, its lens[b] / pos[b]
+ *                  is not examined; attend with lens[b] outside [nq_b, cap], or (paged) a bad table entry among the columns
+ *                  the shipped call of its kind would read: positive zeros in its rows of O, none of its K/V is read;
+ *                  append with pos[b] outside [0, cap - n_b], or (paged) a bad touched table entry: nothing is written.
+ *                  Rows of O outside every range are never written.  A cu whose ranges overlap stays in bounds; the
+ *                  content of the overlapping rows, and which of such sequences are served, is unspecified.
+ *   scratch        qmha_attend_mixed_bytes(c, window, chunk_rows) bytes (0 on invalid arguments), non-null, 256-byte
+ *                  aligned.  Its layout belongs to the call; only O is contractual.
+ *
+ * A cache that is not fa_tc_fp8: QMHA_ERR_NOSYS (use attend_packed / append_packed).  The host checks run before any HIP
+ * call.  One launch, and a combine launch when a decode-kind sequence can have more than one chunk; no allocation, no
+ * synchronisation, no atomics, no waiting between workgroups: capturable.
+ */
+size_t qmha_attend_mixed_bytes(const qmha_kv_cache_t *c, int window, int chunk_rows);
+int qmha_kv_cache_append_mixed(qmha_kv_cache_t *c, const float *K, const float *V, int total, const int32_t *cu, const int32_t *pos,
+                               void *stream);
+int qmha_kv_cache_append_paged_mixed(qmha_kv_cache_t *c, const float *K, const float *V, int total, const int32_t *cu,
+                                     const int32_t *pos, const int32_t *table, void *stream);
+int qmha_attend_cached_mixed(qmha_kv_cache_t *c, const float *Q, float *O, int total, const int32_t *cu, const int32_t *lens,
+                             int window, const float *sinks, int chunk_rows, void *scratch, size_t scratch_bytes, unsigned flags,
+                             void *stream);
+int qmha_attend_cached_paged_mixed(qmha_kv_cache_t *c, const float *Q, float *O, int total, const int32_t *cu, const int32_t *lens,
+                                   const int32_t *table, int window, const float *sinks, int chunk_rows, void *scratch,
+                                   size_t scratch_bytes, unsigned flags, void *stream);
+
+/*
  * Packed batches -- a query count and an append count per sequence in one call, for a continuous-batching step that
  * mixes chunked prefill and decode.  The operands have no batch axis, in the cu_seqlens convention of varlen attention:
  *

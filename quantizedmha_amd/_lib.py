@@ -65,6 +65,12 @@ SIGNATURES = {
     "qmha_attend_cached_paged_decode_window": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _sz, ctypes.c_uint, _vp]),
     "qmha_attend_cached_prefill_window": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, ctypes.c_uint, _vp]),
     "qmha_attend_cached_paged_prefill_window": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, ctypes.c_uint, _vp]),
+    # the mixed-step calls of an fp8 cache: packed operands, a device cu, no bound on a sequence's rows
+    "qmha_attend_mixed_bytes": (_sz, [_vp, _i, _i]),
+    "qmha_kv_cache_append_mixed": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "qmha_kv_cache_append_paged_mixed": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "qmha_attend_cached_mixed": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _sz, ctypes.c_uint, _vp]),
+    "qmha_attend_cached_paged_mixed": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _sz, ctypes.c_uint, _vp]),
     # a sliding window: the two attends over the last `window` keys of a row (a host int, a multiple of 32)
     "qmha_attend_cached_tokens_window": (_i, [_vp, _vp, _vp, _i, _vp, _i, ctypes.c_uint, _vp]),
     "qmha_attend_cached_paged_window": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, ctypes.c_uint, _vp]),

@@ -1184,6 +1184,95 @@ int qmha_attend_cached_paged_prefill_window(qmha_kv_cache_t* c, const float* Q, 
     return attend_prefill_window(c, "attend_paged_prefill_window", Q, O, Nq, lens, table, true, window, sinks, flags, stream);
 }
 
+// ---- the mixed-step calls of an fp8 cache: packed operands, the kind of a sequence decided on the device,
+// grids from total and B alone -----------
+namespace {
+
+size_t mixed_bytes(const qmha_kv_cache* c, int window, int chunk_rows) {
+    const int G = c->h / c->h_kv;
+    return qmha::split_carve(nullptr, c->B, qmha::mixed_chunks(c->cap, G, window, chunk_rows), qmha::mixed_rows(G), c->h, c->D).bytes;
+}
+
+// the checks both mixed calls share, after the operands: the variant, cu and total
+int mixed_call(const CacheCall& k, const char* packed_name, const int32_t* cu, int total) {
+    if (k.c->variant != QMHA_FA_TC_FP8)
+        return fail(QMHA_ERR_NOSYS, std::string(k.what) + ": the mixed-step calls are built for a fa_tc_fp8 cache only; this cache is " +
+                                        qmha_variant_name(k.c->variant) + ": use " + packed_name);
+    if (int st = k.words(cu, "cu (a device int32[B + 1])")) return st;
+    if (total < 1) return k.bad("total = " + std::to_string(total) + " rows, needs total >= 1");
+    return QMHA_OK;
+}
+
+// both append entry points: `table` null is the contiguous one
+int append_mixed(qmha_kv_cache_t* c, const char* what, const float* K, const float* V, int total, const int32_t* cu, const int32_t* pos,
+                 const int32_t* table, bool paged, void* stream) {
+    const CacheCall k{c, what, paged};
+    if (int st = k.operands(K, V)) return st;
+    if (int st = mixed_call(k, paged ? "append_paged_packed" : "append_packed", cu, total)) return st;
+    if (int st = k.words(pos, "pos (a device int32[B])")) return st;
+    if (int st = k.table(table)) return st;
+    return cache_enqueue(c, &ProfRec::pre, stream, k.label().c_str(), kNoLenCheck, [&](const auto& ws, int) {
+        if constexpr (std::is_same<std::decay_t<decltype(ws)>, qmha::Fp8Workspace>::value)
+            return qmha::launch_kv_mixed(K, V, ws, c->B, total, c->cap, cu, pos, c->h_kv, c->D, c->h_kv * c->D, (hipStream_t)stream, c->pages(table));
+        else
+            return hipErrorNotSupported;  // refused above
+    });
+}
+
+int attend_mixed(qmha_kv_cache_t* c, const char* what, const float* Q, float* O, int total, const int32_t* cu, const int32_t* lens,
+                 const int32_t* table, bool paged, int window, const float* sinks, int chunk_rows, void* scratch, size_t scratch_bytes,
+                 unsigned flags, void* stream) {
+    const CacheCall k{c, what, paged};
+    if (int st = k.operands(Q, O)) return st;
+    if (int st = mixed_call(k, paged ? "attend_paged_packed" : "attend_packed", cu, total)) return st;
+    if (int st = k.attend_words(lens, table, flags)) return st;
+    if (window < 1) return k.bad("window = " + std::to_string(window) + " keys, needs window >= 1 (any int: a row sees its last `window` keys)");
+    if (!split_chunk_ok(c, chunk_rows))
+        return k.bad("chunk_rows = " + std::to_string(chunk_rows) + " must be a multiple of 64 with 64 <= chunk_rows <= cap = " +
+                     std::to_string(c->cap) + " (a chunk is a whole number of two-tile stages)");
+    if (!scratch) return k.bad("null scratch (qmha_attend_mixed_bytes bytes of device memory)");
+    if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return k.bad("scratch must be 256-byte aligned");
+    const size_t need = mixed_bytes(c, window, chunk_rows);
+    if (scratch_bytes < need)
+        return k.bad("scratch too small: " + std::to_string(scratch_bytes) + " bytes, qmha_attend_mixed_bytes is " + std::to_string(need));
+    return cache_enqueue(c, &ProfRec::main, stream, k.label().c_str(), kNoLenCheck, [&](const auto& ws, int) {  // one pair around the launches
+        if constexpr (std::is_same<std::decay_t<decltype(ws)>, qmha::Fp8Workspace>::value)
+            return qmha::launch_fp8_mixed(ws, Q, O, k.attend(1, lens, table), cu, total, window, sinks, chunk_rows, scratch, (hipStream_t)stream);
+        else
+            return hipErrorNotSupported;  // refused above
+    });
+}
+
+}  // namespace
+
+size_t qmha_attend_mixed_bytes(const qmha_kv_cache_t* c, int window, int chunk_rows) {
+    if (!c || c->variant != QMHA_FA_TC_FP8 || window < 1 || !split_chunk_ok(c, chunk_rows)) return 0;
+    return mixed_bytes(c, window, chunk_rows);
+}
+
+int qmha_kv_cache_append_mixed(qmha_kv_cache_t* c, const float* K, const float* V, int total, const int32_t* cu, const int32_t* pos,
+                               void* stream) {
+    return append_mixed(c, "append_mixed", K, V, total, cu, pos, nullptr, false, stream);
+}
+
+int qmha_kv_cache_append_paged_mixed(qmha_kv_cache_t* c, const float* K, const float* V, int total, const int32_t* cu, const int32_t* pos,
+                                     const int32_t* table, void* stream) {
+    return append_mixed(c, "append_paged_mixed", K, V, total, cu, pos, table, true, stream);
+}
+
+int qmha_attend_cached_mixed(qmha_kv_cache_t* c, const float* Q, float* O, int total, const int32_t* cu, const int32_t* lens, int window,
+                             const float* sinks, int chunk_rows, void* scratch, size_t scratch_bytes, unsigned flags, void* stream) {
+    return attend_mixed(c, "attend_mixed", Q, O, total, cu, lens, nullptr, false, window, sinks, chunk_rows, scratch, scratch_bytes, flags,
+                        stream);
+}
+
+int qmha_attend_cached_paged_mixed(qmha_kv_cache_t* c, const float* Q, float* O, int total, const int32_t* cu, const int32_t* lens,
+                                   const int32_t* table, int window, const float* sinks, int chunk_rows, void* scratch, size_t scratch_bytes,
+                                   unsigned flags, void* stream) {
+    return attend_mixed(c, "attend_paged_mixed", Q, O, total, cu, lens, table, true, window, sinks, chunk_rows, scratch, scratch_bytes, flags,
+                        stream);
+}
+
 // ---- packed batches: a query / append count per sequence from a device cu[B + 1], no batch axis -----------
 namespace {
 

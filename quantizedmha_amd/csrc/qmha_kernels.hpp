@@ -370,6 +370,23 @@ hipError_t launch_fp8_decode_window(const Fp8Workspace& w, const float* Qf, floa
 // group sees.  One launch, no scratch.  window >= 1, any int.
 hipError_t launch_fp8_band(const Fp8Workspace& w, const float* Qf, float* O, const MaskedCall& c, int window, const float* sinks,
                            hipStream_t stream);
+// The mixed-step calls (qmha_fp8_mixed.hip): packed operands without a batch axis (Q, O [total, d_model]; K, V
+// [total, Hkv * D]; cu a DEVICE int32 [B + 1], read by the kernels) and no bound on a sequence's rows: the grids follow
+// `total` and B alone.  Attend: c is a token-granular call (ragged, with lens; a table: paged) whose Nq is not looked at.  A
+// sequence with G * nq_b <= 32 gets launch_fp8_decode_window's bits at Nq = nq_b, any other launch_fp8_band's; the validity
+// table is launch_fa_packed's without its max_nq row.  One launch, and the combine kernel when mixed_chunks(..) > 1;
+// `scratch`: split_carve(B, mixed_chunks(..), mixed_rows(G), H, D).bytes bytes, 256-byte aligned.
+// Append: launch_kv_tokens with n_b = cu[b + 1] - cu[b] rows for sequence b.
+inline int mixed_rows(int G) { return G < 32 ? 32 / G : 1; }  // the widest decode-kind query block
+inline int mixed_chunks(int cap, int G, int window, int chunk_rows) { return decode_window_chunks(cap, mixed_rows(G), window, chunk_rows); }
+// unit blocks of all prefill-kind sequences of a K/V head: sum ceil(Ga_b G / 4), Ga_b <= nq_b / 32 + 2
+inline long long mixed_prefill_blocks(int total, int B, int G) { return ((total / 32 + 2LL * B) * G + 3) / 4 + B; }
+// 32-row groups all sequences touch in an append: n rows touch at most n / 32 + 2
+inline long long mixed_append_groups(int total, int B) { return total / 32 + 2LL * B; }
+hipError_t launch_fp8_mixed(const Fp8Workspace& w, const float* Qf, float* O, const MaskedCall& c, const int32_t* cu, int total, int window,
+                            const float* sinks, int chunk_rows, void* scratch, hipStream_t stream);
+hipError_t launch_kv_mixed(const float* K, const float* V, const Fp8Workspace& w, int B, int total, int cap, const int32_t* cu, const int32_t* pos,
+                           int H, int D, int d_model, hipStream_t stream, const PageTable& pt = {});
 // Not built on an fp8 cache (the C-ABI refuses these calls before it gets here): split-KV, windows, packed batches
 inline hipError_t launch_fa_split(const Fp8Workspace&, const float*, float*, const MaskedCall&, int, void*, hipStream_t) { return hipErrorNotSupported; }
 inline hipError_t launch_fa_window(const Fp8Workspace&, const float*, float*, const MaskedCall&, int, hipStream_t) { return hipErrorNotSupported; }

@@ -326,6 +326,51 @@ static int prefill_window_attend(qmha_kv_cache_t* handle, const char* what, cons
                                                    QMHA_FLAG_CAUSAL, stream);
 }
 
+// The scratch of an fp8 cache's mixed-step attend (enable_mixed) and both cache classes' mixed calls: packed
+// operands, a device cu, the kind of a sequence decided on the device.  `table` null is the contiguous call.
+struct MixedState {
+    int64_t chunk_rows = 0, window = 0;
+    Tensor scratch;
+
+    void enable(qmha_kv_cache_t* handle, int64_t chunk, int64_t win, int64_t cap, const std::string& kernel, const c10::Device& device) {
+        const size_t bytes = win < 1 ? 0 : qmha_attend_mixed_bytes(handle, DecodeWindowState::clamp(win), static_cast<int>(chunk));
+        TORCH_CHECK(bytes > 0, "enable_mixed: needs a fa_tc_fp8 cache (this one is ", kernel, "; other caches have attend_packed), window = ", win,
+                    " >= 1 and chunk_rows = ", chunk, " a multiple of 64 with 64 <= chunk_rows <= cap = ", cap);
+        chunk_rows = chunk, window = win;
+        scratch = torch::zeros({static_cast<int64_t>(bytes)}, torch::TensorOptions().dtype(torch::kUInt8).device(device));
+    }
+    static int append(qmha_kv_cache_t* handle, const Tensor& Kc, const Tensor& Vc, const Tensor& cu, const Tensor& pos, const int32_t* table,
+                      void* stream) {
+        const int total = static_cast<int>(Kc.size(0));
+        if (!table)
+            return qmha_kv_cache_append_mixed(handle, Kc.data_ptr<float>(), Vc.data_ptr<float>(), total, cu.data_ptr<int32_t>(),
+                                              pos.data_ptr<int32_t>(), stream);
+        return qmha_kv_cache_append_paged_mixed(handle, Kc.data_ptr<float>(), Vc.data_ptr<float>(), total, cu.data_ptr<int32_t>(),
+                                                pos.data_ptr<int32_t>(), table, stream);
+    }
+    int attend(qmha_kv_cache_t* handle, const char* what, const Tensor& Qc, Tensor& out, const Tensor& cu, const Tensor& lens, const int32_t* table,
+               int64_t win, const std::optional<Tensor>& sinks, int64_t heads, void* stream) const {
+        TORCH_CHECK(scratch.defined(), what, ": call enable_mixed(chunk_rows, window) first");
+        TORCH_CHECK(win <= window, what, ": window = ", win, " exceeds enable_mixed's window = ", window);
+        const float* sp = nullptr;
+        Tensor sc;
+        if (sinks) {
+            TORCH_CHECK(sinks->is_cuda() && sinks->scalar_type() == torch::kFloat32 && sinks->device() == Qc.device() && sinks->numel() == heads,
+                        what, ": sinks must be a float32 CUDA tensor of num_heads = ", heads, " elements on the cache's device");
+            sc = sinks->contiguous();
+            sp = sc.data_ptr<float>();
+        }
+        const int total = static_cast<int>(Qc.size(0)), chunk = static_cast<int>(chunk_rows), w = DecodeWindowState::clamp(win);
+        const size_t bytes = static_cast<size_t>(scratch.numel());
+        if (!table)
+            return qmha_attend_cached_mixed(handle, Qc.data_ptr<float>(), out.data_ptr<float>(), total, cu.data_ptr<int32_t>(),
+                                            lens.data_ptr<int32_t>(), w, sp, chunk, scratch.data_ptr(), bytes, QMHA_FLAG_CAUSAL, stream);
+        return qmha_attend_cached_paged_mixed(handle, Qc.data_ptr<float>(), out.data_ptr<float>(), total, cu.data_ptr<int32_t>(),
+                                              lens.data_ptr<int32_t>(), table, w, sp, chunk, scratch.data_ptr(), bytes, QMHA_FLAG_CAUSAL, stream);
+    }
+    std::optional<Tensor> tensor() const { return scratch.defined() ? std::optional<Tensor>(scratch) : std::nullopt; }
+};
+
 // A persistent quantised K/V cache (qmha_kv_cache_*): the compiled form of quantizedmha_amd/torch_ext.py's KVCache.
 // Owns a uint8 tensor of qmha_kv_cache_bytes and the host handle; append / attend run on PyTorch's current stream.
 class KVCache {
@@ -548,7 +593,32 @@ public:
         return out;
     }
 
+    // an fp8 cache's mixed-step calls (qmha_kv_cache_append_mixed / qmha_attend_cached_mixed)
+    void enable_mixed(int64_t chunk_rows, int64_t window) { mixed_.enable(handle_, chunk_rows, window, cap_, kernel_, mem_.device()); }
+    std::optional<Tensor> mixed_scratch() const { return mixed_.tensor(); }
+    void append_mixed(const Tensor& K, const Tensor& V, const Tensor& cu, const Tensor& pos) {
+        auto Kc = cache_packed_rows(K, "K", kv_model_, mem_.device()), Vc = cache_packed_rows(V, "V", kv_model_, mem_.device());
+        TORCH_CHECK(Kc.sizes() == Vc.sizes(), "K and V must have the same shape");
+        cache_cu(cu, B_, mem_.device());
+        per_seq(pos, "pos");
+        const OnStream on = current_stream(mem_.device());
+        const int st = MixedState::append(handle_, Kc, Vc, cu, pos, nullptr, on.stream);
+        TORCH_CHECK(st == QMHA_OK, "KVCache.append_mixed", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+    }
+    Tensor attend_mixed(const Tensor& Q, const Tensor& cu, const Tensor& lens, int64_t window, std::optional<Tensor> sinks,
+                        std::optional<Tensor> out_opt) {
+        auto Qc = cache_packed_rows(Q, "Q", d_model_, mem_.device());
+        cache_cu(cu, B_, mem_.device());
+        per_seq(lens, "lens");
+        Tensor out = packed_out(out_opt, Qc);
+        const OnStream on = current_stream(mem_.device());
+        const int st = mixed_.attend(handle_, "attend_mixed", Qc, out, cu, lens, nullptr, window, sinks, num_heads_, on.stream);
+        TORCH_CHECK(st == QMHA_OK, "KVCache.attend_mixed", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+        return out;
+    }
+
 private:
+    MixedState mixed_;
     void per_seq(const Tensor& t, const char* name) const { cache_per_seq(t, name, B_, mem_.device()); }
     Tensor rows(const Tensor& X, const char* name, int64_t width) const { return cache_rows(X, name, width, B_, mem_.device()); }
     int64_t B_, cap_, d_model_, kv_model_, num_heads_;
@@ -752,7 +822,34 @@ public:
         return out;
     }
 
+    // the mixed-step calls through the block table (qmha_kv_cache_append_paged_mixed / qmha_attend_cached_paged_mixed)
+    void enable_mixed(int64_t chunk_rows, int64_t window) { mixed_.enable(handle_, chunk_rows, window, cap_, kernel_, mem_.device()); }
+    std::optional<Tensor> mixed_scratch() const { return mixed_.tensor(); }
+    void append_paged_mixed(const Tensor& K, const Tensor& V, const Tensor& cu, const Tensor& pos, const Tensor& table) {
+        auto Kc = cache_packed_rows(K, "K", kv_model_, mem_.device()), Vc = cache_packed_rows(V, "V", kv_model_, mem_.device());
+        TORCH_CHECK(Kc.sizes() == Vc.sizes(), "K and V must have the same shape");
+        cache_cu(cu, B_, mem_.device());
+        cache_per_seq(pos, "pos", B_, mem_.device());
+        check_table(table);
+        const OnStream on = current_stream(mem_.device());
+        const int st = MixedState::append(handle_, Kc, Vc, cu, pos, table.data_ptr<int32_t>(), on.stream);
+        TORCH_CHECK(st == QMHA_OK, "PagedKVCache.append_paged_mixed", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+    }
+    Tensor attend_paged_mixed(const Tensor& Q, const Tensor& cu, const Tensor& lens, const Tensor& table, int64_t window,
+                              std::optional<Tensor> sinks, std::optional<Tensor> out_opt) {
+        auto Qc = cache_packed_rows(Q, "Q", d_model_, mem_.device());
+        cache_cu(cu, B_, mem_.device());
+        cache_per_seq(lens, "lens", B_, mem_.device());
+        check_table(table);
+        Tensor out = packed_out(out_opt, Qc);
+        const OnStream on = current_stream(mem_.device());
+        const int st = mixed_.attend(handle_, "attend_paged_mixed", Qc, out, cu, lens, table.data_ptr<int32_t>(), window, sinks, num_heads_, on.stream);
+        TORCH_CHECK(st == QMHA_OK, "PagedKVCache.attend_paged_mixed", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+        return out;
+    }
+
 private:
+    MixedState mixed_;
     // the block table: int32 [B, max_pages] on the cache's device, contiguous: the kernel reads it, the host does not
     void check_table(const Tensor& t) const {
         TORCH_CHECK(t.is_cuda(), "table must be a CUDA tensor");
@@ -827,6 +924,15 @@ PYBIND11_MODULE(torch_ext, m) {
         .def("attend_paged_prefill_window", &PagedKVCache::attend_paged_prefill_window, pybind11::arg("Q"), pybind11::arg("lens"),
              pybind11::arg("table"), pybind11::arg("window"), pybind11::arg("sinks") = pybind11::none(), pybind11::arg("out") = pybind11::none(),
              "attend_prefill_window through the table, bit for bit; only the columns of the swept rows' pages are read.")
+        .def("enable_mixed", &PagedKVCache::enable_mixed, pybind11::arg("chunk_rows"), pybind11::arg("window"),
+             "allocate the scratch of attend_paged_mixed (a fa_tc_fp8 cache) for windows of up to `window` keys and decode chunks of\n"
+             "chunk_rows key rows (a multiple of 64); once, outside a graph capture.")
+        .def("append_paged_mixed", &PagedKVCache::append_paged_mixed, pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("cu"),
+             pybind11::arg("pos"), pybind11::arg("table"), "append_mixed through the table: append_paged's bytes per sequence.")
+        .def("attend_paged_mixed", &PagedKVCache::attend_paged_mixed, pybind11::arg("Q"), pybind11::arg("cu"), pybind11::arg("lens"),
+             pybind11::arg("table"), pybind11::arg("window"), pybind11::arg("sinks") = pybind11::none(), pybind11::arg("out") = pybind11::none(),
+             "attend_mixed through the table, bit for bit.")
+        .def_property_readonly("mixed_scratch", &PagedKVCache::mixed_scratch)
         .def_property_readonly("split_scratch", &PagedKVCache::split_scratch)
         .def_property_readonly("tail", &PagedKVCache::tail)
         .def_property_readonly("cap", &PagedKVCache::cap)
@@ -895,6 +1001,17 @@ PYBIND11_MODULE(torch_ext, m) {
              pybind11::arg("sinks") = pybind11::none(), pybind11::arg("out") = pybind11::none(),
              "attend_tokens of a fa_tc_fp8 cache for a sliding-window layer, any Nq: a row sees its last `window` keys and each query\n"
              "group's sweep follows its band; sinks: None or a float32 [num_heads] tensor of attention sinks.  No scratch.")
+        .def("enable_mixed", &KVCache::enable_mixed, pybind11::arg("chunk_rows"), pybind11::arg("window"),
+             "allocate the scratch of attend_mixed (a fa_tc_fp8 cache) for windows of up to `window` keys and decode chunks of chunk_rows\n"
+             "key rows (a multiple of 64); once, outside a graph capture.")
+        .def("append_mixed", &KVCache::append_mixed, pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("cu"), pybind11::arg("pos"),
+             "the append of a continuous-batching step: K, V [total, num_kv_heads * d], rows [cu[b], cu[b + 1]) go to cache rows\n"
+             "[pos[b], ...); append_tokens' bytes per sequence, no bound on a sequence's rows.")
+        .def("attend_mixed", &KVCache::attend_mixed, pybind11::arg("Q"), pybind11::arg("cu"), pybind11::arg("lens"), pybind11::arg("window"),
+             pybind11::arg("sinks") = pybind11::none(), pybind11::arg("out") = pybind11::none(),
+             "the attend of a continuous-batching step: Q [total, d_model]; a sequence with (num_heads / num_kv_heads) * nq_b <= 32 gets\n"
+             "attend_decode_window's bits, any other attend_prefill_window's; the kind is decided on the device.")
+        .def_property_readonly("mixed_scratch", &KVCache::mixed_scratch)
         .def_property_readonly("split_scratch", &KVCache::split_scratch)
         .def_property_readonly("tail", &KVCache::tail)
         .def_property_readonly("len", &KVCache::len)

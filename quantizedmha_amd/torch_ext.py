@@ -604,6 +604,77 @@ class KVCache:
         _lib.check(st, f"KVCache.attend_packed({self.kernel})")
         return out
 
+    def enable_mixed(self, chunk_rows: int, window: int) -> None:
+        """Allocate the scratch of an fp8 cache's mixed-step attend (qmha_attend_mixed_bytes), `.mixed_scratch`, for windows
+        of up to `window` keys (any int >= 1; a global layer: >= cap) and decode chunks of chunk_rows key rows, a multiple of
+        64 with 64 <= chunk_rows <= cap.  Once, and outside a graph capture: the calls themselves allocate nothing."""
+        chunk_rows, window = int(chunk_rows), int(window)
+        nbytes = _lib.load().qmha_attend_mixed_bytes(self._handle, max(0, min(window, 2 ** 31 - 1)), chunk_rows)
+        if nbytes == 0:
+            raise RuntimeError(f"enable_mixed: needs a fa_tc_fp8 cache (this one is {self.kernel}; other caches have attend_packed), "
+                               f"window = {window} >= 1 and chunk_rows = {chunk_rows} a multiple of 64 with 64 <= chunk_rows <= cap = {self.cap}")
+        self.mixed_chunk_rows, self.mixed_window = chunk_rows, window
+        self.mixed_scratch = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+
+    def _append_mixed(self, what: str, K: torch.Tensor, V: torch.Tensor, cu: torch.Tensor, pos: torch.Tensor,
+                      table: Optional[torch.Tensor]) -> None:
+        """Both mixed-step appends: `table` None is the contiguous one."""
+        Kc, Vc = self._packed_rows(K, "K", self.kv_model), self._packed_rows(V, "V", self.kv_model)
+        if Kc.shape != Vc.shape:
+            raise RuntimeError("K and V must have the same shape")
+        cu, pos, lib = self._cu(cu), self._per_seq(pos, "pos"), _lib.load()
+        with _current_stream(self.device) as stream:
+            if table is None:
+                st = lib.qmha_kv_cache_append_mixed(self._handle, Kc.data_ptr(), Vc.data_ptr(), Kc.shape[0], cu.data_ptr(), pos.data_ptr(), stream)
+            else:
+                st = lib.qmha_kv_cache_append_paged_mixed(self._handle, Kc.data_ptr(), Vc.data_ptr(), Kc.shape[0], cu.data_ptr(), pos.data_ptr(),
+                                                          table.data_ptr(), stream)
+        _lib.check(st, f"{type(self).__name__}.{what}({self.kernel})")
+
+    def _attend_mixed(self, what: str, Q: torch.Tensor, cu: torch.Tensor, lens: torch.Tensor, table: Optional[torch.Tensor], window: int,
+                      sinks: Optional[torch.Tensor], out: Optional[torch.Tensor]) -> torch.Tensor:
+        """Both mixed-step attends: `table` None is the contiguous one."""
+        Qc = self._packed_rows(Q, "Q", self.d_model)
+        cu, lens = self._cu(cu), self._per_seq(lens, "lens")
+        if getattr(self, "mixed_scratch", None) is None:
+            raise RuntimeError(f"{what}: call enable_mixed(chunk_rows, window) first")
+        window = max(0, min(int(window), 2 ** 31 - 1))  # the C-ABI refuses 0
+        if window > self.mixed_window:
+            raise RuntimeError(f"{what}: window = {window} exceeds enable_mixed's window = {self.mixed_window}")
+        if sinks is not None:
+            if not isinstance(sinks, torch.Tensor) or sinks.dtype != torch.float32 or sinks.device != self.device or sinks.numel() != self.num_heads:
+                raise RuntimeError(f"{what}: sinks must be a float32 CUDA tensor of num_heads = {self.num_heads} elements on the cache's device")
+            sinks = sinks.contiguous()
+        out = self._packed_out(out, Qc)
+        lib, scratch = _lib.load(), self.mixed_scratch
+        tail = (window, None if sinks is None else sinks.data_ptr(), self.mixed_chunk_rows, scratch.data_ptr(), scratch.numel(),
+                _lib.QMHA_FLAG_CAUSAL)
+        with _current_stream(self.device) as stream:
+            if table is None:
+                st = lib.qmha_attend_cached_mixed(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[0], cu.data_ptr(), lens.data_ptr(), *tail,
+                                                  stream)
+            else:
+                st = lib.qmha_attend_cached_paged_mixed(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[0], cu.data_ptr(), lens.data_ptr(),
+                                                        table.data_ptr(), *tail, stream)
+        _lib.check(st, f"{type(self).__name__}.{what}({self.kernel})")
+        return out
+
+    def append_mixed(self, K: torch.Tensor, V: torch.Tensor, cu: torch.Tensor, pos: torch.Tensor) -> None:
+        """The append of a continuous-batching step on a fa_tc_fp8 cache (qmha_kv_cache_append_mixed): K, V are
+        [total, num_kv_heads * d] with no batch axis, sequence b brings the rows [cu[b], cu[b + 1]) to cache rows
+        [pos[b], ...) and leaves append_tokens' bytes.  No bound on a sequence's rows: the grid follows total and B.  An empty
+        sequence sits out; a range outside [0, total] or an invalid pos[b] writes nothing."""
+        self._append_mixed("append_mixed", K, V, cu, pos, None)
+
+    def attend_mixed(self, Q: torch.Tensor, cu: torch.Tensor, lens: torch.Tensor, window: int, sinks: Optional[torch.Tensor] = None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The attend of a continuous-batching step on a fa_tc_fp8 cache (qmha_attend_cached_mixed): Q is [total, d_model]
+        with no batch axis, rows [cu[b], cu[b + 1]) are sequence b's.  A sequence with (num_heads / num_kv_heads) * nq_b <= 32
+        gets attend_decode_window's bits at Nq = nq_b, any other attend_prefill_window's; the kind is decided on the device,
+        so a captured step follows the mix in cu.  window: any int >= 1 up to enable_mixed's; sinks as in those calls.  An
+        empty sequence sits out, an invalid lens[b] gives zeros, rows outside every range are not written."""
+        return self._attend_mixed("attend_mixed", Q, cu, lens, None, window, sinks, out)
+
 
 class GroupedKVCache(KVCache):
     """KVCache for grouped-query attention (qmha_kv_cache_create_gqa): the cache holds num_kv_heads K/V heads shared
@@ -792,6 +863,20 @@ class PagedKVCache:
                                                              stream)
         _lib.check(st, f"PagedKVCache.attend_paged_packed({self.kernel})")
         return out
+
+    enable_mixed = KVCache.enable_mixed
+    _append_mixed = KVCache._append_mixed
+    _attend_mixed = KVCache._attend_mixed
+
+    def append_paged_mixed(self, K: torch.Tensor, V: torch.Tensor, cu: torch.Tensor, pos: torch.Tensor, table: torch.Tensor) -> None:
+        """append_mixed through the table (qmha_kv_cache_append_paged_mixed): append_paged's bytes and rules per sequence."""
+        self._append_mixed("append_paged_mixed", K, V, cu, pos, self._table(table))
+
+    def attend_paged_mixed(self, Q: torch.Tensor, cu: torch.Tensor, lens: torch.Tensor, table: torch.Tensor, window: int,
+                           sinks: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """attend_mixed through the table (qmha_attend_cached_paged_mixed), bit for bit: only the table columns the shipped
+        call of a sequence's kind would read are read and checked."""
+        return self._attend_mixed("attend_paged_mixed", Q, cu, lens, self._table(table), window, sinks, out)
 
 
 def quantize_int8(X: torch.Tensor, d_model: int, num_heads: int, layout: int = 0):

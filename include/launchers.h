@@ -416,6 +416,36 @@ int qmha_attend_cached_paged_decode(qmha_kv_cache_t *c, const float *Q, float *O
                                     void *stream);
 
 /*
+ * The shared-prefix decode call of an fp8 cache -- the decode call above for a batch whose sequences begin with the same
+ * rows, a system prompt stored once.  The first prefix_rows cache rows of EVERY sequence of the call are
+ * those of slot 0: on a contiguous cache rows [0, prefix_rows) of sequence 0's slice, on a pool the pages table[0][j] that
+ * hold a row below prefix_rows -- read there whether or not lens[0] is valid.  They are swept once for the batch, with the
+ * batch's query rows as the MFMA columns; the rows from prefix_rows on are swept per sequence as the decode call does.
+ * The decode call's scratch (qmha_attend_decode_bytes), chunk_rows rules, W = Nq * (h / h_kv) <= 32 and host checks.
+ *
+ *   prefix_rows    a host int, a multiple of chunk_rows with chunk_rows <= prefix_rows <= cap, else QMHA_ERR_INVALID before
+ *                  any HIP call: attend_decode is the call where no whole chunk is shared.
+ *   not read       for b > 0 sequence b's own slice below prefix_rows, and its table columns that hold only such rows: the
+ *                  rows may hold anything, the columns may be -1 and their pages unallocated.
+ *   validity       the decode call's rules and prefix_rows <= lens[b] - Nq; on a pool only the columns of table row b that
+ *                  hold a row in [prefix_rows, lens[b]) are looked at.  Any other sequence is left out: Nq rows of positive
+ *                  zeros, nothing read through its lens or table.  An entry of table row 0 that holds prefix rows and lies
+ *                  outside the pool leaves every sequence out; it never becomes an address.
+ *   result         bit for bit the decode call's at the same chunk_rows on a cache in which every sequence holds its own
+ *                  copy of the prefix rows: a prefix chunk is a chunk of the decode call's grid, its partial goes to the same
+ *                  scratch slot, and the combine pass has the split calls' arithmetic in their order.
+ *
+ * A cache that is not fa_tc_fp8: QMHA_ERR_NOSYS (use attend_tokens_split / attend_paged_split).  Two plain launches under one
+ * qmha_profile main pair; no allocation, no synchronisation, no atomics, no waiting between workgroups: capturable, with
+ * prefix_rows baked into the captured step and lens and the table read on the device.
+ */
+int qmha_attend_cached_decode_shared(qmha_kv_cache_t *c, const float *Q, float *O, int Nq, const int32_t *lens, int prefix_rows,
+                                     int chunk_rows, void *scratch, size_t scratch_bytes, unsigned flags, void *stream);
+int qmha_attend_cached_paged_decode_shared(qmha_kv_cache_t *c, const float *Q, float *O, int Nq, const int32_t *lens,
+                                           const int32_t *table, int prefix_rows, int chunk_rows, void *scratch,
+                                           size_t scratch_bytes, unsigned flags, void *stream);
+
+/*
  * The windowed decode call of an fp8 cache, with attention sinks -- the decode call above for a sliding-window layer
  * (Mistral, Gemma 2/3, gpt-oss), with kernels of its own.  Operands, device lens and table, causal only, the
  * validity rules, positive zeros for an invalid sequence, W = Nq * (h / h_kv) <= 32 and the chunk_rows rules are the decode

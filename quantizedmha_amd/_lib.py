@@ -59,6 +59,9 @@ SIGNATURES = {
     "qmha_attend_decode_bytes": (_sz, [_vp, _i, _i]),
     "qmha_attend_cached_decode": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _sz, ctypes.c_uint, _vp]),
     "qmha_attend_cached_paged_decode": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _sz, ctypes.c_uint, _vp]),
+    # an fp8 cache's shared-prefix decode call: the decode call with a host prefix_rows ahead of chunk_rows
+    "qmha_attend_cached_decode_shared": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _sz, ctypes.c_uint, _vp]),
+    "qmha_attend_cached_paged_decode_shared": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _sz, ctypes.c_uint, _vp]),
     # an fp8 cache's windowed decode call: a host window (any int >= 1) and a device float32[h] of attention sinks (or null)
     "qmha_attend_decode_window_bytes": (_sz, [_vp, _i, _i, _i]),
     "qmha_attend_cached_decode_window": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _sz, ctypes.c_uint, _vp]),

@@ -1085,6 +1085,58 @@ int qmha_attend_cached_paged_decode(qmha_kv_cache_t* c, const float* Q, float* O
     return attend_decode(c, "attend_paged_decode", Q, O, Nq, lens, table, true, chunk_rows, scratch, scratch_bytes, flags, stream);
 }
 
+// ---- the shared-prefix decode call of an fp8 cache: the decode call over the decode call's scratch, with the
+// first prefix_rows cache rows of every sequence read in slot 0 and swept once for the batch -----------
+namespace {
+
+// both entry points: `table` null is the contiguous one.  The checks of attend_decode, and the prefix
+int attend_decode_shared(qmha_kv_cache_t* c, const char* what, const float* Q, float* O, int Nq, const int32_t* lens, const int32_t* table,
+                         bool paged, int prefix_rows, int chunk_rows, void* scratch, size_t scratch_bytes, unsigned flags, void* stream) {
+    const CacheCall k{c, what, paged};
+    if (int st = k.operands(Q, O)) return st;
+    if (c->variant != QMHA_FA_TC_FP8)
+        return fail(QMHA_ERR_NOSYS, std::string(what) + ": the shared-prefix decode call is built for a fa_tc_fp8 cache only; this cache is " +
+                                        qmha_variant_name(c->variant) + ": use attend_tokens_split / attend_paged_split");
+    if (int st = k.attend_words(lens, table, flags)) return st;
+    if (int st = k.rows("Nq", Nq)) return st;
+    const int G = c->h / c->h_kv;
+    if ((long long)Nq * G > kDecodeColumns)
+        return k.bad("Nq * (h / h_kv) = " + std::to_string(Nq) + " * " + std::to_string(G) + " = " + std::to_string((long long)Nq * G) +
+                     " query rows per K/V head, the limit is " + std::to_string(kDecodeColumns) +
+                     " (two 16-column MFMA blocks): use attend_tokens for longer query blocks");
+    if (!split_chunk_ok(c, chunk_rows))
+        return k.bad("chunk_rows = " + std::to_string(chunk_rows) + " must be a multiple of 64 with 64 <= chunk_rows <= cap = " +
+                     std::to_string(c->cap) + " (a chunk is a whole number of two-tile stages)");
+    if (prefix_rows < chunk_rows || prefix_rows > c->cap || prefix_rows % chunk_rows != 0)
+        return k.bad("prefix_rows = " + std::to_string(prefix_rows) + " must be a multiple of chunk_rows = " + std::to_string(chunk_rows) +
+                     " with chunk_rows <= prefix_rows <= " + k.cap() + " (the shared rows are whole chunks): use attend_decode / attend_paged_decode where no whole chunk is shared");
+    if (!scratch) return k.bad("null scratch (qmha_attend_decode_bytes bytes of device memory)");
+    if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return k.bad("scratch must be 256-byte aligned");
+    const size_t need = split_bytes(c, Nq, chunk_rows);
+    if (scratch_bytes < need)
+        return k.bad("scratch too small: " + std::to_string(scratch_bytes) + " bytes, qmha_attend_decode_bytes is " + std::to_string(need));
+    return cache_enqueue(c, &ProfRec::main, stream, k.label().c_str(), kNoLenCheck, [&](const auto& ws, int) {  // one pair around both launches
+        if constexpr (std::is_same<std::decay_t<decltype(ws)>, qmha::Fp8Workspace>::value)
+            return qmha::launch_fp8_decode_shared(ws, Q, O, k.attend(Nq, lens, table), prefix_rows, chunk_rows, scratch, (hipStream_t)stream);
+        else
+            return hipErrorNotSupported;  // refused above
+    });
+}
+
+}  // namespace
+
+int qmha_attend_cached_decode_shared(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, const int32_t* lens, int prefix_rows, int chunk_rows,
+                                     void* scratch, size_t scratch_bytes, unsigned flags, void* stream) {
+    return attend_decode_shared(c, "attend_decode_shared", Q, O, Nq, lens, nullptr, false, prefix_rows, chunk_rows, scratch, scratch_bytes, flags,
+                                stream);
+}
+
+int qmha_attend_cached_paged_decode_shared(qmha_kv_cache_t* c, const float* Q, float* O, int Nq, const int32_t* lens, const int32_t* table,
+                                           int prefix_rows, int chunk_rows, void* scratch, size_t scratch_bytes, unsigned flags, void* stream) {
+    return attend_decode_shared(c, "attend_paged_decode_shared", Q, O, Nq, lens, table, true, prefix_rows, chunk_rows, scratch, scratch_bytes,
+                                flags, stream);
+}
+
 // ---- the windowed decode call of an fp8 cache, with attention sinks: the decode call's columns and streams
 // over the chunks of the window's own sweep; one launch where that is a single chunk -----------
 namespace {

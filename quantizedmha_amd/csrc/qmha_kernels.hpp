@@ -349,6 +349,14 @@ hipError_t launch_kv_tokens(const float* K, const float* V, const Fp8Workspace& 
 // partials; qmha_split_combine_kernel writes O.  chunk_rows: a multiple of 64 in [64, Nk].
 hipError_t launch_fp8_decode(const Fp8Workspace& w, const float* Qf, float* O, const MaskedCall& c, int chunk_rows, void* scratch,
                              hipStream_t stream);
+// The shared-prefix decode call (qmha_fp8_shared.hip).  launch_fp8_decode's call and scratch where the first
+// prefix_rows cache rows of every sequence are those of slot 0 (a contiguous cache: sequence 0's slice; a pool: the pages of
+// table row 0): those rows are swept once with the batch's B W query rows as the MFMA columns, the rows from prefix_rows on
+// per sequence as launch_fp8_decode does.  A sequence also needs prefix_rows <= lens[b] - Nq.  prefix_rows: a multiple of
+// chunk_rows in [chunk_rows, Nk].  Two launches on `stream`; the bits of launch_fp8_decode on a cache whose every slice
+// holds the prefix rows.
+hipError_t launch_fp8_decode_shared(const Fp8Workspace& w, const float* Qf, float* O, const MaskedCall& c, int prefix_rows, int chunk_rows,
+                                    void* scratch, hipStream_t stream);
 // The windowed decode call with attention sinks (qmha_fp8_decode_window.hip).  launch_fp8_decode's call in
 // which row r sees key j iff e_r - window < j <= e_r, e_r = lens[b] - Nq + r, and head k's softmax has one more column
 // sinks[k] (a DEVICE float32[H] in natural-log units of S / sqrt(d), or null) with no value row.  The sweep starts at the

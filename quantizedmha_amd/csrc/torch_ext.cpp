@@ -263,6 +263,20 @@ struct DecodeState {
         return qmha_attend_cached_paged_decode(handle, Qc.data_ptr<float>(), out.data_ptr<float>(), Nq, lens.data_ptr<int32_t>(), table, chunk,
                                                scratch.data_ptr(), bytes, QMHA_FLAG_CAUSAL, stream);
     }
+    // the shared-prefix calls (attend_decode_shared / attend_paged_decode_shared) over the same scratch
+    int attend_shared(qmha_kv_cache_t* handle, const char* what, const Tensor& Qc, Tensor& out, const Tensor& lens, const int32_t* table,
+                      int64_t prefix_rows, void* stream) const {
+        TORCH_CHECK(scratch.defined(), what, ": call enable_decode(chunk_rows) first");
+        TORCH_CHECK(Qc.size(1) <= max_nq, what, ": Nq = ", Qc.size(1), " rows exceed enable_decode's max_nq = ", max_nq);
+        const int Nq = static_cast<int>(Qc.size(1)), chunk = static_cast<int>(chunk_rows);
+        const int prefix = static_cast<int>(std::max<int64_t>(-1, std::min<int64_t>(prefix_rows, INT_MAX)));  // the library refuses the rest
+        const size_t bytes = static_cast<size_t>(scratch.numel());
+        if (!table)
+            return qmha_attend_cached_decode_shared(handle, Qc.data_ptr<float>(), out.data_ptr<float>(), Nq, lens.data_ptr<int32_t>(), prefix, chunk,
+                                                    scratch.data_ptr(), bytes, QMHA_FLAG_CAUSAL, stream);
+        return qmha_attend_cached_paged_decode_shared(handle, Qc.data_ptr<float>(), out.data_ptr<float>(), Nq, lens.data_ptr<int32_t>(), table,
+                                                      prefix, chunk, scratch.data_ptr(), bytes, QMHA_FLAG_CAUSAL, stream);
+    }
     std::optional<Tensor> tensor() const { return scratch.defined() ? std::optional<Tensor>(scratch) : std::nullopt; }
 };
 
@@ -540,6 +554,16 @@ public:
         TORCH_CHECK(st == QMHA_OK, "KVCache.attend_decode", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
         return out_opt ? out : out.view(Q.sizes());
     }
+    // the shared-prefix decode call (qmha_attend_cached_decode_shared): the first prefix_rows rows are sequence 0's
+    Tensor attend_decode_shared(const Tensor& Q, const Tensor& lens, int64_t prefix_rows, std::optional<Tensor> out_opt) {
+        auto Qc = rows(Q, "Q", d_model_);
+        per_seq(lens, "lens");
+        Tensor out = out_for(out_opt, Qc);
+        const OnStream on = current_stream(mem_.device());
+        const int st = decode_.attend_shared(handle_, "attend_decode_shared", Qc, out, lens, nullptr, prefix_rows, on.stream);
+        TORCH_CHECK(st == QMHA_OK, "KVCache.attend_decode_shared", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+        return out_opt ? out : out.view(Q.sizes());
+    }
 
     // an fp8 cache's windowed decode call with attention sinks (qmha_attend_cached_decode_window)
     void enable_decode_window(int64_t chunk_rows, int64_t window, int64_t max_nq) {
@@ -759,6 +783,18 @@ public:
         TORCH_CHECK(st == QMHA_OK, "PagedKVCache.attend_paged_decode", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
         return out_opt ? out : out.view(Q.sizes());
     }
+    // the shared-prefix decode call through the block table (qmha_attend_cached_paged_decode_shared): the prefix is row 0's pages
+    Tensor attend_paged_decode_shared(const Tensor& Q, const Tensor& lens, const Tensor& table, int64_t prefix_rows,
+                                      std::optional<Tensor> out_opt) {
+        auto Qc = cache_rows(Q, "Q", d_model_, B_, mem_.device());
+        cache_per_seq(lens, "lens", B_, mem_.device());
+        check_table(table);
+        Tensor out = out_for(out_opt, Qc);
+        const OnStream on = current_stream(mem_.device());
+        const int st = decode_.attend_shared(handle_, "attend_paged_decode_shared", Qc, out, lens, table.data_ptr<int32_t>(), prefix_rows, on.stream);
+        TORCH_CHECK(st == QMHA_OK, "PagedKVCache.attend_paged_decode_shared", "(", kernel_, "): ", qmha_status_string(st), ": ", qmha_last_error());
+        return out_opt ? out : out.view(Q.sizes());
+    }
 
     // the windowed decode call through the block table (qmha_attend_cached_paged_decode_window); the scratch as KVCache's
     void enable_decode_window(int64_t chunk_rows, int64_t window, int64_t max_nq) {
@@ -912,6 +948,10 @@ PYBIND11_MODULE(torch_ext, m) {
              "and up to max_nq query rows, max_nq * (num_heads / num_kv_heads) <= 32; once, outside a graph capture.")
         .def("attend_paged_decode", &PagedKVCache::attend_paged_decode, pybind11::arg("Q"), pybind11::arg("lens"), pybind11::arg("table"),
              pybind11::arg("out") = pybind11::none(), "attend_decode through the table, bit for bit.")
+        .def("attend_paged_decode_shared", &PagedKVCache::attend_paged_decode_shared, pybind11::arg("Q"), pybind11::arg("lens"),
+             pybind11::arg("table"), pybind11::arg("prefix_rows"), pybind11::arg("out") = pybind11::none(),
+             "attend_decode_shared through the table, bit for bit: the prefix rows are the pages of table row 0, and of row b only\n"
+             "the columns that hold a row in [prefix_rows, lens[b]) are read.")
         .def_property_readonly("decode_scratch", &PagedKVCache::decode_scratch)
         .def("enable_decode_window", &PagedKVCache::enable_decode_window, pybind11::arg("chunk_rows"), pybind11::arg("window"),
              pybind11::arg("max_nq") = 1,
@@ -987,6 +1027,10 @@ PYBIND11_MODULE(torch_ext, m) {
         .def("attend_decode", &KVCache::attend_decode, pybind11::arg("Q"), pybind11::arg("lens"), pybind11::arg("out") = pybind11::none(),
              "attend_tokens of a fa_tc_fp8 cache for a decode or short speculative step: the step's query rows packed into MFMA\n"
              "columns, the key sweep in chunks, split-KV's combine pass.")
+        .def("attend_decode_shared", &KVCache::attend_decode_shared, pybind11::arg("Q"), pybind11::arg("lens"), pybind11::arg("prefix_rows"),
+             pybind11::arg("out") = pybind11::none(),
+             "attend_decode for a batch that shares its first prefix_rows cache rows (a multiple of chunk_rows): they are read in\n"
+             "sequence 0's slice and swept once, with the batch's query rows as the MFMA columns.  attend_decode's bits.")
         .def_property_readonly("decode_scratch", &KVCache::decode_scratch)
         .def("enable_decode_window", &KVCache::enable_decode_window, pybind11::arg("chunk_rows"), pybind11::arg("window"),
              pybind11::arg("max_nq") = 1,

@@ -458,6 +458,36 @@ class KVCache:
         deterministic result of its own inside the fp8 accuracy contract, not attend_tokens' bits."""
         return self._decode("attend_decode", Q, lens, None, out)
 
+    def _decode_shared(self, what: str, Q: torch.Tensor, lens: torch.Tensor, table: Optional[torch.Tensor], prefix_rows: int,
+                       out: Optional[torch.Tensor]) -> torch.Tensor:
+        """Both shared-prefix decode calls: `table` None is the contiguous one."""
+        Qc = self._rows(Q, "Q")
+        lens = self._per_seq(lens, "lens")
+        if getattr(self, "decode_scratch", None) is None:
+            raise RuntimeError(f"{what}: call enable_decode(chunk_rows) first")
+        if Qc.shape[1] > self.decode_max_nq:
+            raise RuntimeError(f"{what}: Nq = {Qc.shape[1]} rows exceed enable_decode's max_nq = {self.decode_max_nq}")
+        out = _out_for(out, Qc, "size")
+        prefix_rows = max(-1, min(int(prefix_rows), 2 ** 31 - 1))  # the library refuses what is out of range
+        lib = _lib.load()
+        tail = (prefix_rows, self.decode_chunk_rows, self.decode_scratch.data_ptr(), self.decode_scratch.numel(), _lib.QMHA_FLAG_CAUSAL)
+        with _current_stream(self.device) as stream:
+            if table is None:
+                st = lib.qmha_attend_cached_decode_shared(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[1], lens.data_ptr(), *tail, stream)
+            else:
+                st = lib.qmha_attend_cached_paged_decode_shared(self._handle, Qc.data_ptr(), out.data_ptr(), Qc.shape[1], lens.data_ptr(),
+                                                                table.data_ptr(), *tail, stream)
+        _lib.check(st, f"{type(self).__name__}.{what}({self.kernel})")
+        return out.view(Q.shape) if out.numel() == Q.numel() and out.dim() != Q.dim() else out
+
+    def attend_decode_shared(self, Q: torch.Tensor, lens: torch.Tensor, prefix_rows: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """attend_decode for a batch whose sequences begin with the same rows (qmha_attend_cached_decode_shared): the first
+        prefix_rows cache rows of every sequence are read in sequence 0's slice and swept once, with the batch's query rows
+        as the MFMA columns; sequence b > 0's own slice below prefix_rows is not read.  prefix_rows: a host int, a multiple
+        of enable_decode's chunk_rows in [chunk_rows, cap]; a sequence also needs prefix_rows <= lens[b] - Nq, any other gets
+        zeros.  attend_decode's bits on a cache where every sequence holds a copy of the prefix rows."""
+        return self._decode_shared("attend_decode_shared", Q, lens, None, prefix_rows, out)
+
     def enable_decode_window(self, chunk_rows: int, window: int, max_nq: int = 1) -> None:
         """Allocate the scratch of an fp8 cache's windowed decode call (qmha_attend_decode_window_bytes at Nq = max_nq),
         `.decode_window_scratch`, for windows of up to `window` keys (any int >= 1) and chunks of chunk_rows key rows: a
@@ -814,6 +844,15 @@ class PagedKVCache:
     def attend_paged_decode(self, Q: torch.Tensor, lens: torch.Tensor, table: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """attend_decode through the table (qmha_attend_cached_paged_decode), bit for bit; needs enable_decode()."""
         return self._decode("attend_paged_decode", Q, lens, self._table(table), out)
+
+    _decode_shared = KVCache._decode_shared
+
+    def attend_paged_decode_shared(self, Q: torch.Tensor, lens: torch.Tensor, table: torch.Tensor, prefix_rows: int,
+                                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """attend_decode_shared through the table (qmha_attend_cached_paged_decode_shared), bit for bit: the prefix rows are
+        the pages of table row 0; of row b only the columns that hold a row in [prefix_rows, lens[b]) are read, the others
+        may be -1.  An entry of row 0 that holds prefix rows and lies outside the pool gives zeros for every sequence."""
+        return self._decode_shared("attend_paged_decode_shared", Q, lens, self._table(table), prefix_rows, out)
 
     enable_decode_window = KVCache.enable_decode_window
     _decode_window = KVCache._decode_window

@@ -32,8 +32,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
 KERNEL_SOURCES = ["qmha_fa_int8.hip", "qmha_fa_f16.hip", "qmha_fa_masked.hip", "qmha_fa_split.hip", "qmha_fa_packed.hip",
-                  "qmha_fa_window.hip", "qmha_fa_fp8.hip", "qmha_fp8_decode.hip", "qmha_fp8_decode_window.hip",
-                  "qmha_fp8_band.hip", "qmha_fp8_mixed.hip", "qmha_prepass.hip", "qmha_kv_fp8.hip",
+                  "qmha_fa_window.hip", "qmha_fa_fp8.hip", "qmha_fp8_decode.hip", "qmha_fp8_shared.hip",
+                  "qmha_fp8_decode_window.hip", "qmha_fp8_band.hip", "qmha_fp8_mixed.hip", "qmha_prepass.hip", "qmha_kv_fp8.hip",
                   "qmha_fa_f32.hip", "qmha_unfused.hip", "qmha_api.cpp"]
 # profiling builds (QMHA_EXTRA_FLAGS=-DQMHA_ABLATION) enable the tuning alternatives of the fp16 / fp32 / api
 # sources.  The r01-r03 int8 experiment source (ablation perturbations, ring / DMA-split / TSHADOW / ACC1
@@ -94,6 +94,7 @@ FILE_FLAGS = {"qmha_fa_int8.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + os
               "qmha_fa_window.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + os.environ.get("QMHA_CAUSAL_FLAGS", "").split(),
               "qmha_fa_fp8.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + NO_PK_F32,
               "qmha_fp8_decode.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + NO_PK_F32,
+              "qmha_fp8_shared.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + NO_PK_F32,
               "qmha_fp8_decode_window.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + NO_PK_F32,
               "qmha_fp8_band.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + NO_PK_F32,
               "qmha_fp8_mixed.hip": ["-fno-slp-vectorize", "-fno-honor-nans"] + NO_PK_F32,
